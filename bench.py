@@ -1,14 +1,16 @@
 #!/usr/bin/env python
-"""Headline benchmark: U-NO training samples/s on synthetic 421x421 Darcy (BASELINE.json configs[1]) + the HBM-roofline
-fraction of the spectral block, measured live, + the CPU baseline timed beside it.
+"""Headline benchmark: U-NO training samples/s on synthetic 421x421 Darcy (BASELINE.json configs[1]); with --full also the
+HBM-roofline fraction of the spectral block, measured live, the secondary workloads and the CPU baseline timed beside it.
 
-    python bench.py --gpus N --steps K --warmup W          (N > 1 re-launches itself under torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+                                                           (N > 1 re-launches itself under torch.distributed.run)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
 A step = forward + relative-L2 loss + backward + gradient all-reduce (N > 1, RCCL) + complex-modulus Adam update on one
 minibatch of 16 synthetic samples per GPU (weak scaling; --strong splits a global batch of 16).  Inputs are resident in
-HBM before the timed region.  Rank 0 prints ONE JSON line.
+HBM before the timed region.  A plain run sets up, runs W untimed and K timed steps, writes the last timed step's outputs
+(--dump-outputs) and prints the result line; everything else it can measure runs only with --full.  Rank 0 prints ONE JSON line.
 """
 from __future__ import annotations
 
@@ -41,14 +43,52 @@ def parse():
     ap.add_argument("--comm-dtype", choices=("f32", "bf16"), default="f32",
                     help="gradient buckets on the links: f32 (default; equals one process on the global batch) or bf16 (half the bytes: "
                          "--workload c4 at width 32 moves 3.8 GB per step; float32 buffer, optimiser state and update)")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the host CPU leg (developer runs)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary workloads (C3 / C4 / C5, reference-style caller)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the per-kernel table of the step, spectral / operator block rooflines, copy ceiling, 3-D block, "
+                         "secondary workloads, CPU baseline and (N > 1) exchange timings")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned as DIR/<name>.npy: the loss and fixed seeded samples of the gradients "
+                         "and of the updated parameters")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the host CPU leg (developer runs)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the secondary workloads (C3 / C4 / C5, reference-style caller)")
     ap.add_argument("--cpu-batch", type=int, default=16, help="samples per CPU-baseline step")
     ap.add_argument("--cpu-steps", type=int, default=3, help="timed CPU-baseline steps")
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-threads", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--cpu-config", choices=("c1", "c2"), default="c2", help=argparse.SUPPRESS)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+# ----------------------------------------------------------------------------------------------- outputs of the timed step
+DUMP_SAMPLE = 1 << 22       # entries kept of a larger array: 2 arrays x 16 MB stay inside the 64 MB a dump may take
+
+
+def _sample(v):
+    """v (1-D, on the device) itself, or DUMP_SAMPLE of its entries at positions drawn from a fixed seed (sorted, with repeats)"""
+    import torch
+    if v.numel() <= DUMP_SAMPLE:
+        return v.cpu().numpy()
+    idx = torch.randint(0, v.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+    return v[idx.to(v.device)].cpu().numpy()
+
+
+def dump_outputs(path, loss, trainer):
+    """What a caller of the timed step holds after the last timed step: the returned loss, the gradients and the updated parameters
+    (model.parameters() order, complex ones as interleaved re / im, float32).  The headline model has 65 M parameters, so the last two
+    are sampled (_sample): the positions depend only on the parameter count, so two builds compare entry for entry."""
+    import numpy as np
+    import torch
+    params = list(trainer.model.parameters())
+
+    def flat(ts):
+        return torch.cat([(torch.view_as_real(t) if t.is_complex() else t).detach().reshape(-1).float() for t in ts])
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "loss.npy"), np.asarray([float(loss)], dtype=np.float64))
+    np.save(os.path.join(path, "grad_sample.npy"), _sample(flat(p.grad if p.grad is not None else torch.zeros_like(p) for p in params)))
+    np.save(os.path.join(path, "param_sample.npy"), _sample(flat(params)))
 
 
 # ----------------------------------------------------------------------------------------------- CPU baseline
@@ -715,8 +755,10 @@ def run_secondary(args, dev, world, rank, backend):
     lv = float(loss)
     assert lv == lv, "training produced NaN"
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, loss, w.trainer)
         roofline = None
-        if world == 1:
+        if world == 1 and args.full:
             if args.workload == "c4":
                 b = spectral_block3d_roofline(dev)
                 roofline = {"bound": "hbm", "kernel": "3-D spectral block forward = " + " + ".join(sorted(b["fwd_kernels"])),
@@ -786,7 +828,6 @@ def main():
             dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)     # nccl == RCCL on ROCm
         backend = dist.get_backend()
 
-    from uno_amd import _native
     from uno_amd.harness import DarcyTrainer, UNO_9, synthetic_darcy_batch
 
     if args.workload != "c2":
@@ -806,6 +847,7 @@ def main():
             dist.barrier()
         torch.cuda.synchronize(dev)
 
+    # N > 1: the exchange is checked before anything is timed - a wrong exchange never produces a throughput number
     selfcheck = dp_selfcheck(dev, world, rank) if world > 1 else None
     for _ in range(args.warmup):
         trainer.step(a, u)
@@ -818,28 +860,68 @@ def main():
         dist.barrier()
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, loss, trainer)
+    loss_val = float(loss)
+    assert loss_val == loss_val, "training produced NaN"
+    comm = None
+    if world > 1:
+        t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+        comm = {"backend": backend, "ranks": dist.get_world_size(), "grad_bytes": trainer.grads.flat.numel() * 4,
+                "buckets": len(trainer.grads.buckets), "bucket_mb": 32.0, "comm_dtype": args.comm_dtype, "reserved_cus": trainer.comm_cus,
+                "selfcheck": selfcheck}
+    gb = world * per_rank
+    value = gb * args.steps / elapsed
+    out = {
+        "metric": "UNO training samples/s (421^2 Darcy)", "value": value,
+        "unit": "samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "strong" if args.strong else "weak",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"Darcy 2D {S}x{S}, UNO_9(3,{WIDTH},pad={PAD}) 64ch, batch {per_rank}/GPU, train step "
+                               "(fwd+loss+bwd+allreduce+Adam)", "global_batch": gb,
+                   "parallelism": f"dp{world}", "final_loss": loss_val},
+        "comm": comm, "rccl_ranks": comm["ranks"] if comm and backend == "nccl" else (1 if world == 1 else None),
+    }
+    if args.full:
+        full_figures(args, dev, world, rank, trainer, a, u, out)
+    if rank == 0:
+        print(json.dumps(out))
+    if world > 1:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def full_figures(args, dev, world, rank, trainer, a, u, out):
+    """--full: everything the result line carries beyond the headline figure, measured after the timed steps (the trainer's state
+    moves on from there).  Every rank runs the training steps in here so that the collectives stay matched."""
+    import torch
+    import torch.distributed as dist
+    from uno_amd import _native
+
+    def sync_all():
+        if world > 1:
+            dist.barrier()
+        torch.cuda.synchronize(dev)
+
     # Per-kernel durations of the training step: the same K steps once more with the library's HIP events on the launch
-    # stream around every kernel.  Kept out of the timed region above because the event pairs serialise the queue (~10 us per
+    # stream around every kernel.  Kept out of the timed region because the event pairs serialise the queue (~10 us per
     # kernel, ~5 % of the step); every rank runs it so the collectives stay matched.
     _native.profile_begin(200000)
     for _ in range(args.steps):
         trainer.step(a, u)
     sync_all()
     records = _native.profile_end()
-    comm = None
+    comm = out["comm"]
     if world > 1:
-        t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
         # the exchange alone: one blocking SUM over the flat gradient buffer (not overlapped with anything)
         sync_all()
         tc = time.perf_counter()
         for _ in range(5):
             trainer.grads.all_reduce_sum()
         sync_all()
-        comm = {"backend": backend, "ranks": dist.get_world_size(), "grad_bytes": trainer.grads.flat.numel() * 4,
-                "buckets": len(trainer.grads.buckets), "bucket_mb": 32.0, "comm_dtype": args.comm_dtype, "reserved_cus": trainer.comm_cus,
-                "blocking_allreduce_ms": (time.perf_counter() - tc) / 5 * 1e3}
+        comm["blocking_allreduce_ms"] = (time.perf_counter() - tc) / 5 * 1e3
         # overlapped vs blocking exchange: the same K steps with the bucket hooks off and ONE blocking all-reduce after the
         # backward pass; and the issue time of every bucket relative to the start of a backward pass (host clock, rank 0)
         sync_all()
@@ -848,15 +930,12 @@ def main():
             trainer.step_blocking(a, u)
         sync_all()
         comm["ms_per_step_blocking_allreduce"] = (time.perf_counter() - tc) / args.steps * 1e3
-        comm["ms_per_step_overlapped"] = elapsed / args.steps * 1e3
+        comm["ms_per_step_overlapped"] = out["ms_per_step"]
         trainer.grads.trace = []
         trainer.step(a, u)
         sync_all()
         comm["bucket_issue_ms_after_backward_start"] = [round(t * 1e3, 3) for t in trainer.grads.trace]
         trainer.grads.trace = None
-        comm["selfcheck"] = selfcheck
-    loss_val = float(loss)
-    assert loss_val == loss_val, "training produced NaN"
 
     if rank == 0:
         agg = {}
@@ -912,27 +991,12 @@ def main():
         cpu = None
         if world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline_bounded(args.cpu_batch, args.cpu_steps)
-        gb = world * per_rank
-        value = gb * args.steps / elapsed
         # BASELINE.md holds no published number for this metric (section 1: "None exist"), so vs_baseline stays null; the north-star
         # target is relative to the CPU path timed on this host (>= 10 x), reported beside it
-        vs_cpu = (value / cpu["value"]) if (cpu and cpu.get("value")) else None
-        out = {
-            "metric": "UNO training samples/s (421^2 Darcy)", "value": value,
-            "unit": "samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "strong" if args.strong else "weak",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"Darcy 2D {S}x{S}, UNO_9(3,{WIDTH},pad={PAD}) 64ch, batch {per_rank}/GPU, train step "
-                                   "(fwd+loss+bwd+allreduce+Adam)", "global_batch": gb,
-                       "parallelism": f"dp{world}", "final_loss": loss_val},
-            "roofline": roofline, "spectral_block": {k: v for k, v in block.items() if not k.endswith("_kernels")},
-            "spectral_block_3d": block3d, "comm": comm, "rccl_ranks": comm["ranks"] if comm and backend == "nccl" else (1 if world == 1 else None),
-            "extras": extras, "cpu_baseline": cpu, "vs_cpu_baseline": vs_cpu, "target_vs_cpu_baseline": 10.0,
-        }
-        print(json.dumps(out))
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+        vs_cpu = (out["value"] / cpu["value"]) if (cpu and cpu.get("value")) else None
+        out.update({"roofline": roofline, "spectral_block": {k: v for k, v in block.items() if not k.endswith("_kernels")},
+                    "spectral_block_3d": block3d, "extras": extras, "cpu_baseline": cpu, "vs_cpu_baseline": vs_cpu,
+                    "target_vs_cpu_baseline": 10.0})
 
 
 if __name__ == "__main__":

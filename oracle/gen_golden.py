@@ -168,10 +168,15 @@ def uno9_case(ref_dir):
     return out
 
 
-def _checksums(model):
+def _checksums(model, exact=False):
+    """[sum |p|, ||p||_2] of every parameter; exact=True accumulates in float64, so that the value does not depend on the
+    summation order (the host's thread count decides it for float32 sums over the large 3-D weights)."""
     out = {}
     for k, p in model.named_parameters():
-        out[k] = np.array([float(p.detach().abs().sum()), float(torch.linalg.vector_norm(p.detach()))])
+        q = p.detach()
+        if exact:
+            q = q.to(torch.complex128 if q.is_complex() else torch.float64)
+        out[k] = np.array([float(q.abs().sum()), float(torch.linalg.vector_norm(q))])
     return out
 
 
@@ -184,6 +189,7 @@ def ns2d_case():
     torch.manual_seed(21)
     model = n2.UNO(14, 4)
     out = {f"ns2d.ck.{k}": v for k, v in _checksums(model).items()}
+    out.update({f"ns2d.ck64.{k}": v for k, v in _checksums(model, exact=True).items()})
     g = torch.Generator().manual_seed(22)
     xx = torch.randn(1, 64, 64, 10, generator=g)
     yy = torch.randn(1, 64, 64, 2, generator=g)
@@ -213,6 +219,7 @@ def ns3d_case():
     torch.manual_seed(31)
     model = n3.Uno3D_T20(6, 2, pad=3)
     out = {f"ns3d.ck.{k}": v for k, v in _checksums(model).items()}
+    out.update({f"ns3d.ck64.{k}": v for k, v in _checksums(model, exact=True).items()})
     g = torch.Generator().manual_seed(32)
     x = torch.randn(1, 32, 32, 10, 1, generator=g)
     y = torch.randn(1, 32, 32, 20, generator=g)

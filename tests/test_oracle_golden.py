@@ -108,8 +108,16 @@ def test_block2d(name):
     assert rel_err(y.detach().numpy(), c.y) < 1e-5
     y.backward(torch.from_numpy(c.gy))
     assert rel_err(x.grad.numpy(), c.gx) < 1e-5
-    for k, g in c.sub("grad").items():
-        assert rel_err(dict(blk.named_parameters())[k].grad.numpy(), g) < 2e-5, k
+    grads = c.sub("grad")
+    scale = np.sqrt(sum(np.linalg.norm(g) ** 2 for g in grads.values()))
+    for k, g in grads.items():
+        got = dict(blk.named_parameters())[k].grad.numpy()
+        if np.linalg.norm(g) < 1e-5 * scale:
+            # zero in exact arithmetic (the 1x1 convolution's bias ahead of InstanceNorm: the mean subtraction cancels it), so the
+            # reference's value is float32 roundoff of the host's summation order; the oracle's must be roundoff as well
+            assert np.linalg.norm(got) < 1e-5 * scale, k
+        else:
+            assert rel_err(got, g) < 2e-5, k
 
 
 @pytest.mark.parametrize("name", B3D)

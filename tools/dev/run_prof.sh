@@ -10,8 +10,8 @@ cp $(ls gpurun_out/ns3d_prof/*/*kernel_stats.csv | head -1) profiles/${tag}_ns3d
 rm -rf gpurun_out/ns2d_prof gpurun_out/ns3d_prof
 python tools/dev/steplaunches.py > profiles/${tag}_step_launches.txt 2>&1
 python tools/dev/fusetime.py 20 > profiles/${tag}_fuse_ab.txt 2>&1
-python bench.py > gpurun_out/bench_${tag}.json 2> gpurun_out/bench_${tag}.err
-grep '^{' gpurun_out/bench_${tag}.json | tail -1 > profiles/${tag}_bench_n1.json
+python bench.py --full > "$TMPDIR/bench_${tag}.json" 2> "$TMPDIR/bench_${tag}.err"
+grep '^{' "$TMPDIR/bench_${tag}.json" | tail -1 > profiles/${tag}_bench_n1.json
 mkdir -p gpurun_out/profiles_$tag; cp profiles/${tag}_* profiles/block_rocprof.json profiles/block_traffic.json profiles/hbm_traffic.json gpurun_out/profiles_$tag/ 2>/dev/null
 find gpurun_out/prof_$tag -name "*.db" -delete; find gpurun_out/prof_$tag -name "*_agent_info.csv" -delete
 du -sh gpurun_out/prof_$tag; ls -la profiles/ | grep $tag; head -c 400 profiles/${tag}_bench_n1.json

@@ -31,6 +31,6 @@ bash tools/block_traffic.sh $out $tag
 # the training step
 bash tools/pmc_traffic.sh $out/pmc_bench
 python tools/traffic_json.py $out/pmc_bench profiles/hbm_traffic.json profiles/${tag}_bench_pmc_traffic.txt > /dev/null
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/bench_stats -- python bench.py --no-cpu-baseline --no-extras > $out/bench_stats.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/bench_stats -- python bench.py --full --no-cpu-baseline --no-extras > $out/bench_stats.log 2>&1
 cp $(ls $out/bench_stats/*/*kernel_stats.csv | head -1) profiles/${tag}_bench_kernel_stats.csv
 ls -la profiles/

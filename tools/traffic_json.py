@@ -30,7 +30,7 @@ for k in sorted(acc):
                     "launches": n, "method": method}
     lines.append(f"{k}\n   FETCH_SIZE {fs:16.0f} KiB (n={len(acc[k]['FETCH_SIZE'])})\n   WRITE_SIZE {ws:16.0f} KiB (n={len(acc[k]['WRITE_SIZE'])})")
 json.dump(js, open(out_json, "w"), indent=1)
-open(out_txt, "w").write("# rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline\n"
+open(out_txt, "w").write("# rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extras\n"
                          "# mean counter value per launch, per kernel.  gfx950 correction (MI355X_MICROARCH.md, HBM): FETCH_SIZE counts 128-B\n"
                          "# requests as 64 B -> read bytes = 2 * FETCH_SIZE * 1024; WRITE_SIZE taken as is.\n" + "\n".join(lines) + "\n")
 print("\n".join(lines))
