@@ -231,7 +231,7 @@ def test_bf16_gradient_buckets_match_float32_exchange(tmp_path):
 def test_aborted_backward_leaves_gradient_buckets_and_pass_state_clean():
     """A backward pass that raises under arm() (an out-of-memory error the training loop catches): the trainer waits for what was
     issued, resets the bucket counters and releases the library's pass state - the next step runs as if nothing had happened."""
-    import uno_amd.integral_operators as io
+    import uno_amd._param_grads as pg
     from uno_amd.harness.train import FlatGradients
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()))
     dist.init_process_group("gloo", rank=0, world_size=1)
@@ -250,12 +250,12 @@ def test_aborted_backward_leaves_gradient_buckets_and_pass_state_clean():
             def backward(ctx, g):
                 raise RuntimeError("boom")
         x = torch.ones(3, 6)
-        io._PASSES[424242] = {"id": 424242, "acc": {}, "stacks": {}, "uses": {}, "born": 0.0}      # what a failed pass leaves behind
+        pg._PASSES[424242] = {"id": 424242, "acc": {}, "stacks": {}, "uses": {}, "born": 0.0}      # what a failed pass leaves behind
         with pytest.raises(RuntimeError, match="boom"):
             tr.step_with(lambda: lin2(Boom.apply(lin1(x))).sum())          # lin2's buckets are issued, then the pass dies
         g = tr.grads
         assert not g._armed and g._works == [] and g._next == 0 and g._pending == list(g._bucket_params)
-        assert not io._PASSES
+        assert not pg._PASSES
         ref1, ref2 = torch.nn.Linear(6, 5), torch.nn.Linear(5, 1)
         ref1.load_state_dict(lin1.state_dict()); ref2.load_state_dict(lin2.state_dict())
         tr.grads.zero_()

@@ -243,7 +243,7 @@ def test_c3_ns2d_accumulating_weight_gradient(cfg):
 @pytest.mark.parametrize("cfg", C3_LAYERS, ids=lambda c: "x".join(map(str, c)))
 def test_c3_ns2d_weight_gradient_batched_over_the_rollout(cfg):
     """From the second training step on the roll-out's 40 weight gradients of a layer are ONE per-mode GEMM with K = 40 x 32 over
-    the layer's stacked spectra (integral_operators.TIME_BATCHED_WGRAD): the kernels that call dispatches at the full-width layer
+    the layer's stacked spectra (_param_grads.TIME_BATCHED_WGRAD): the kernels that call dispatches at the full-width layer
     shapes, against float64 on the host."""
     from uno_amd import _native
     Ci, Co, H, Ho, m = cfg
@@ -301,7 +301,7 @@ def test_c4_ns3d_pointwise_resample_full_size(w, layer):
     """The FFT crop / resample of pointwise_op_3D (reference integral_operators.py:448-463) at the NS-3D model's own shapes - it runs
     on the same pruned-DFT kernel families (plane transforms + leading-axis cdft kernels with explicit frequency tables), which the
     bench's kernel lists therefore name: forward and input gradient against the reference's op sequence in float64 on the host."""
-    from uno_amd.integral_operators import _FftResample3dFn, _resample3d_plan
+    from uno_amd.spectral3d import _FftResample3dFn, _resample3d_plan
     _, Co, din, dout, _ = _t20_layers(w)[layer]
     plan = _resample3d_plan(din, dout, dev())
     if plan is None:
@@ -337,7 +337,7 @@ def test_c4_ns3d_pointwise_resample_accumulating_full_size(w, layer):
     branch's last transform adds into the spectral branch's output and writes the GELU in the same pass, reference
     integral_operators.py:506-512) at the NS-3D model's shapes: s + resample(t) and gelu(s + resample(t)) against float64 on the host."""
     from uno_amd import _native
-    from uno_amd.integral_operators import _resample3d_plan
+    from uno_amd.spectral3d import _resample3d_plan
     _, Co, din, dout, _ = _t20_layers(w)[layer]
     plan = _resample3d_plan(din, dout, dev())
     if plan is None:

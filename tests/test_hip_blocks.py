@@ -45,7 +45,8 @@ def test_pointwise_op_3d_golden(name):
     """The product pointwise_op_3D (K8 1x1x1 convolution + bug-compatible FFT crop / resample) against the reference's output:
     `pw3d_grow` runs on the pruned-DFT kernels (uno_fft_resample3d), `pw3d_shrink` has an odd kept-row count and takes the
     stock-FFT branch of the same module - both must reproduce reference integral_operators.py:448-467."""
-    from uno_amd.integral_operators import pointwise_op_3D, _resample3d_plan
+    from uno_amd.integral_operators import pointwise_op_3D
+    from uno_amd.spectral3d import _resample3d_plan
     c = Case(ZB, name)
     B, Ci, Co, *dims = [int(v) for v in c.meta]
     din, dout = tuple(dims[:3]), tuple(dims[3:])
@@ -294,7 +295,7 @@ def test_weight_gradients_are_written_in_place():
     """(a) with a FlatGradients buffer the weight-gradient kernels write each gradient into its view and autograd adopts an alias
     of it (no copy, no add); (b) a layer used several times in one graph (roll-out) accumulates into .grad in place; both give the
     gradients of the ordinary path (fresh tensors + autograd sums)."""
-    import uno_amd.integral_operators as io
+    import uno_amd._param_grads as pg
     from uno_amd.harness.train import FlatGradients
     from uno_amd.integral_operators import OperatorBlock_2D, channel_mix, gelu_channel_mix
     torch.manual_seed(1)
@@ -312,7 +313,7 @@ def test_weight_gradients_are_written_in_place():
 
     ref = {}
     for mode in (False, True):
-        io.INPLACE_PARAM_GRADS = mode
+        pg.INPLACE_PARAM_GRADS = mode
         try:
             for p in params:
                 p.grad = None
@@ -327,7 +328,7 @@ def test_weight_gradients_are_written_in_place():
                     ar, br = (torch.view_as_real(t) if t.is_complex() else t for t in (a, b))
                     assert float((ar - br).norm()) <= 2e-6 * float(ar.norm()) + 1e-12
         finally:
-            io.INPLACE_PARAM_GRADS = True
+            pg.INPLACE_PARAM_GRADS = True
     # (a) flat buffer: one use per parameter, every gradient lands in its view without a copy
     fg = FlatGradients(params)
     fg.zero_()
@@ -336,7 +337,7 @@ def test_weight_gradients_are_written_in_place():
         if p.grad is not None:
             assert p.grad.data_ptr() == v.data_ptr(), "gradient was not written into the flat buffer"
     single = [None if p.grad is None else p.grad.clone() for p in params]
-    io.INPLACE_PARAM_GRADS = False
+    pg.INPLACE_PARAM_GRADS = False
     try:
         for p in params:
             p.grad = None
@@ -346,7 +347,7 @@ def test_weight_gradients_are_written_in_place():
                 ar, br = (torch.view_as_real(t) if t.is_complex() else t for t in (a, p.grad))
                 assert float((ar - br).norm()) <= 2e-6 * float(br.norm()) + 1e-12
     finally:
-        io.INPLACE_PARAM_GRADS = True
+        pg.INPLACE_PARAM_GRADS = True
         for p in params:
             if hasattr(p, "_uno_grad_buffer"):
                 del p._uno_grad_buffer
@@ -359,7 +360,7 @@ def test_weight_gradient_batched_over_the_uses_of_a_layer():
     in ONE per-mode GEMM with K = T x batch.  Same gradients as T separate weight gradients summed by autograd; a changing number
     of uses, a second backward over a retained graph and a pass that reaches only some of the uses stay correct."""
     import warnings
-    import uno_amd.integral_operators as io
+    import uno_amd._param_grads as pg
     from uno_amd.harness.train import FlatGradients
     from uno_amd.integral_operators import OperatorBlock_2D, SpectralConv2d_Uno
     torch.manual_seed(3)
@@ -377,14 +378,14 @@ def test_weight_gradient_batched_over_the_uses_of_a_layer():
         return sum(o.square().sum() for o in sel)
 
     def grads(T, batched, keep=None):
-        io.TIME_BATCHED_WGRAD = batched
+        pg.TIME_BATCHED_WGRAD = batched
         try:
             for p in params:
                 p.grad = None
             rollout(T, keep).backward()
             return [p.grad.clone() for p in params]
         finally:
-            io.TIME_BATCHED_WGRAD = True
+            pg.TIME_BATCHED_WGRAD = True
 
     def same(a, b, tol=3e-6):
         for u, v in zip(a, b):
@@ -430,11 +431,11 @@ def test_weight_gradient_batched_over_the_uses_of_a_layer():
         return h.square().sum()
     for p in params:
         p.grad = None
-    io.TIME_BATCHED_WGRAD = False
+    pg.TIME_BATCHED_WGRAD = False
     try:
         zigzag().backward()
     finally:
-        io.TIME_BATCHED_WGRAD = True
+        pg.TIME_BATCHED_WGRAD = True
     refz = [None if p.grad is None else p.grad.clone() for p in params[:len(list(blk.parameters()))]]
     for rep in range(2):
         for p in params:
@@ -471,7 +472,7 @@ def test_weight_gradient_batched_over_the_uses_of_a_layer():
 def test_weight_gradient_batched_over_the_uses_of_a_two_source_block():
     """The same batching for a block that consumes a skip connection's two tensors (forward_cat): its spectral weight gradient
     is computed once per pass over the stacked spectra; equal to the use-by-use gradients."""
-    import uno_amd.integral_operators as io
+    import uno_amd._param_grads as pg
     from uno_amd.integral_operators import OperatorBlock_2D
     torch.manual_seed(4)
     blk = OperatorBlock_2D(32, 16, 24, 24, 5, 4).to(dev())
@@ -486,14 +487,14 @@ def test_weight_gradient_batched_over_the_uses_of_a_two_source_block():
         return h.square().sum()
 
     def grads(batched):
-        io.TIME_BATCHED_WGRAD = batched
+        pg.TIME_BATCHED_WGRAD = batched
         try:
             for p in params + [a, b]:
                 p.grad = None
             loss_fn().backward()
             return [p.grad.clone() for p in params + [a, b]]
         finally:
-            io.TIME_BATCHED_WGRAD = True
+            pg.TIME_BATCHED_WGRAD = True
 
     w1 = blk.conv.weights1
     for attr in ("_uno_uses", "_uno_stack", "_uno_nostack"):
@@ -514,7 +515,7 @@ def test_inplace_weight_gradients_never_lose_a_contribution_silently():
     """A weight that receives gradients from the library's kernels (in place) AND from a stock torch op in the same backward pass:
     autograd may add the stock gradient out of place and so replace the tensor the kernels keep accumulating into.  The library
     must then either still produce the right gradient or fail loudly - never train on a partial sum."""
-    import uno_amd.integral_operators as io
+    import uno_amd._param_grads as pg
     from uno_amd.integral_operators import channel_mix
     torch.manual_seed(2)
     lin = torch.nn.Linear(8, 8).to(dev())
@@ -525,13 +526,13 @@ def test_inplace_weight_gradients_never_lose_a_contribution_silently():
         y = y + torch.matmul(lin.weight, y)                    # the same weight through a stock op
         return channel_mix(y, lin.weight, lin.bias).square().sum()
 
-    io.INPLACE_PARAM_GRADS = False
+    pg.INPLACE_PARAM_GRADS = False
     try:
         lin.zero_grad(set_to_none=True)
         loss_fn().backward()
         ref = lin.weight.grad.clone()
     finally:
-        io.INPLACE_PARAM_GRADS = True
+        pg.INPLACE_PARAM_GRADS = True
     lin.zero_grad(set_to_none=True)
     try:
         loss_fn().backward()
@@ -599,6 +600,7 @@ def test_inplace_gradients_under_reentrant_checkpoint(flat):
     inner pass runs.  Same gradients as the ordinary path (INPLACE_PARAM_GRADS = False), with and without a registered flat buffer."""
     import torch.utils.checkpoint as cp
     import uno_amd.integral_operators as io
+    import uno_amd._param_grads as pg
     from uno_amd.harness.train import FlatGradients
     torch.manual_seed(3)
     blk = io.OperatorBlock_2D(8, 8, 20, 20, 4, 4).to(dev())
@@ -615,7 +617,7 @@ def test_inplace_gradients_under_reentrant_checkpoint(flat):
 
     res = {}
     for mode in (False, True):
-        io.INPLACE_PARAM_GRADS = mode
+        pg.INPLACE_PARAM_GRADS = mode
         try:
             for p in params:
                 p.grad = None
@@ -628,11 +630,11 @@ def test_inplace_gradients_under_reentrant_checkpoint(flat):
                 fg.finish()
             res[mode] = _grads_of(params) + [x.grad.clone()]
         finally:
-            io.INPLACE_PARAM_GRADS = True
+            pg.INPLACE_PARAM_GRADS = True
             for p in params:
                 if hasattr(p, "_uno_grad_buffer"):
                     del p._uno_grad_buffer
-    assert not io._PASSES, "a finished backward pass left its state behind"
+    assert not pg._PASSES, "a finished backward pass left its state behind"
     _assert_same_grads(res[False], res[True])
 
 
@@ -641,6 +643,7 @@ def test_inplace_gradients_with_autograd_grad_inside_a_hook():
     """torch.autograd.grad called from a tensor hook DURING a backward pass is a second graph task on the same thread.  It uses the
     same layers; its state must be its own, and the outer pass must go on summing into the tensors it started with."""
     import uno_amd.integral_operators as io
+    import uno_amd._param_grads as pg
     torch.manual_seed(4)
     blk = io.OperatorBlock_2D(8, 8, 20, 20, 4, 4).to(dev())
     params = list(blk.parameters())
@@ -663,7 +666,7 @@ def test_inplace_gradients_with_autograd_grad_inside_a_hook():
 
     res = {}
     for mode in (False, True):
-        io.INPLACE_PARAM_GRADS = mode
+        pg.INPLACE_PARAM_GRADS = mode
         try:
             for p in params:
                 p.grad = None
@@ -672,8 +675,8 @@ def test_inplace_gradients_with_autograd_grad_inside_a_hook():
             loss_fn().backward()
             res[mode] = _grads_of(params) + [x.grad.clone(), seen[0].clone()]
         finally:
-            io.INPLACE_PARAM_GRADS = True
-    assert not io._PASSES
+            pg.INPLACE_PARAM_GRADS = True
+    assert not pg._PASSES
     _assert_same_grads(res[False], res[True])
 
 
@@ -715,11 +718,11 @@ def test_training_step_without_the_private_autograd_entry_points(monkeypatch):
     """with torch._C._current_graph_task_id / the engine's callback queue unavailable (simulated) the whole Darcy
     step - flat gradient buffer, joined skip gradients, a layer used three times - runs on the ordinary gradient path and gives the
     default path's parameters."""
-    import uno_amd.integral_operators as io
+    import uno_amd._param_grads as pg
     from uno_amd.harness import DarcyTrainer, UNO_9, synthetic_darcy_batch
     res = []
     for available in (True, False):
-        monkeypatch.setattr(io, "_PASS_STATE_AVAILABLE", available)
+        monkeypatch.setattr(pg, "_PASS_STATE_AVAILABLE", available)
         torch.manual_seed(0)
         model = UNO_9(3, 8, pad=5).to(dev())
         tr = DarcyTrainer(model, lr=1e-3, weight_decay=1e-3)

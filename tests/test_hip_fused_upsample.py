@@ -95,6 +95,7 @@ def test_operator_block_fused_equals_two_kernel_form(shape):
     """OperatorBlock_2D up-sampling (forward fused) and down-sampling (input gradient fused): outputs and every gradient against the
     two-kernel form (FUSE_UPSAMPLE_ADD = False) on the same inputs."""
     import uno_amd.integral_operators as io
+    import uno_amd.block2d as b2
     B, Ci, Co, S_in, S_out, m = shape
     dev = _dev()
     torch.manual_seed(5)
@@ -103,7 +104,7 @@ def test_operator_block_fused_equals_two_kernel_form(shape):
     gy = torch.randn(B, Co, S_out, S_out, device=dev)
 
     def run(fuse):
-        io.FUSE_UPSAMPLE_ADD = fuse
+        b2.FUSE_UPSAMPLE_ADD = fuse
         try:
             xr = x.clone().requires_grad_(True)
             for p in blk.parameters():
@@ -112,7 +113,7 @@ def test_operator_block_fused_equals_two_kernel_form(shape):
             y.backward(gy)
             return [y.detach(), xr.grad] + [p.grad.clone() for p in blk.parameters()]
         finally:
-            io.FUSE_UPSAMPLE_ADD = True
+            b2.FUSE_UPSAMPLE_ADD = True
     from uno_amd import _native
     _native.profile_begin(1000)
     fused = run(True)
@@ -127,6 +128,7 @@ def test_operator_block_fused_equals_two_kernel_form(shape):
 def test_two_source_block_fused_equals_two_kernel_form():
     """forward_cat (the skip form conv5 of the headline model uses), up-sampling 111 -> 223"""
     import uno_amd.integral_operators as io
+    import uno_amd.block2d as b2
     dev = _dev()
     torch.manual_seed(6)
     B, C1, C2, Co, Si, So, m = 2, 16, 16, 8, 111, 223, 8
@@ -136,7 +138,7 @@ def test_two_source_block_fused_equals_two_kernel_form():
     gy = torch.randn(B, Co, So, So, device=dev)
 
     def run(fuse):
-        io.FUSE_UPSAMPLE_ADD = fuse
+        b2.FUSE_UPSAMPLE_ADD = fuse
         try:
             a, b = x1.clone().requires_grad_(True), x2.clone().requires_grad_(True)
             for p in blk.parameters():
@@ -145,7 +147,7 @@ def test_two_source_block_fused_equals_two_kernel_form():
             y.backward(gy)
             return [y.detach(), a.grad, b.grad] + [p.grad.clone() for p in blk.parameters()]
         finally:
-            io.FUSE_UPSAMPLE_ADD = True
+            b2.FUSE_UPSAMPLE_ADD = True
     fused, two = run(True), run(False)
     for a, b in zip(fused, two):
         assert _rel(a, b) < 5e-6, _rel(a, b)

@@ -111,6 +111,7 @@ def test_window_leaves_the_rest_of_the_planes_alone():
 def test_autograd_function_fused_equals_three_calls(crop):
     """channel_mix_cat_project's backward pass with PROJECT_BACKWARD_FUSED on and off: every gradient agrees (and the fused form ran)"""
     import uno_amd.integral_operators as io
+    import uno_amd.pointwise as pw
     from uno_amd import _native
     torch.manual_seed(3)
     B, C1, C2, Co, H, W = 2, 64, 64, 64, 300, 300
@@ -119,8 +120,8 @@ def test_autograd_function_fused_equals_three_calls(crop):
     gout = torch.randn(B, 1, S1, S2).cuda()
     res, names = [], []
     for fused in (True, False):
-        old = io.PROJECT_BACKWARD_FUSED
-        io.PROJECT_BACKWARD_FUSED = fused
+        old = pw.PROJECT_BACKWARD_FUSED
+        pw.PROJECT_BACKWARD_FUSED = fused
         try:
             t = [v.clone().cuda().requires_grad_(True) for v in base]
             out = io.channel_mix_cat_project(t[:2], t[2], t[3], t[4], t[5], gelu_first=True, crop=crop)[:, :, :S1, :S2]
@@ -130,7 +131,7 @@ def test_autograd_function_fused_equals_three_calls(crop):
             names.append([r[0] for r in _native.profile_end()])
             res.append([v.grad for v in t])
         finally:
-            io.PROJECT_BACKWARD_FUSED = old
+            pw.PROJECT_BACKWARD_FUSED = old
     assert not any("gelu_project_bwd" in n for n in names[0]) and any("gelu_project_bwd" in n for n in names[1])
     for a, b, tol in zip(res[0], res[1], (5e-6, 5e-6, 2e-5, 2e-5, 2e-5, 2e-5)):
         assert rel(a, b) < tol

@@ -4,7 +4,7 @@ out-of-bounds store of any kernel (clamped raw-buffer addressing, ragged tails, 
 fails the test instead of silently corrupting a neighbouring tensor.  The parity tests compare values only.  pytest -m gpu
 
 How: inside the fixture torch.empty / empty_like / zeros / zeros_like (the only allocation calls of uno_amd/_native.py,
-uno_amd/integral_operators.py and uno_amd/harness/*) return views into [64 KiB guard | tensor | 64 KiB guard] blocks filled with 0xA5;
+the layer modules beside it and uno_amd/harness/*) return views into [64 KiB guard | tensor | 64 KiB guard] blocks filled with 0xA5;
 the workloads are the library's own ragged-shape cases (odd grids, prime sizes, overlapping corners, partial tiles, one- and
 two-source blocks, bf16 forms, 3-D volumes and planes, the roll-out's stacked spectra) driven through the public modules, so every C
 entry point that the models reach runs with guarded outputs."""

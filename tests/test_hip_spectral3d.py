@@ -211,7 +211,7 @@ def test_fft_resample3d_matches_the_reference_op_sequence(cfg):
     """The FFT crop / resample of pointwise_op_3D (reference integral_operators.py:448-463) on the pruned-DFT kernels vs the
     reference's own op sequence (rfftn, four corner copies into an input-sized zero spectrum, irfftn(s=size)) in float64 on the
     host: forward and input gradient, including the sizes where the reference misplaces the negative frequencies."""
-    from uno_amd.integral_operators import _FftResample3dFn, _resample3d_plan
+    from uno_amd.spectral3d import _FftResample3dFn, _resample3d_plan
     B, C, din, dout = cfg
     g = torch.Generator().manual_seed(sum(din) * 7 + sum(dout))
     x = torch.randn(B, C, *din, generator=g)
@@ -266,7 +266,8 @@ def test_pointwise_op_3d_outside_the_pruned_dft_range_matches_the_reference_sequ
     `_resample3d_plan` is None: the layer raises, and with STOCK_FFT_RESAMPLE3D = True runs the stock rocFFT sequence with the corner copies as one mask multiplication -
     compared here with the reference's own op sequence (integral_operators.py:439-467) on the host, forward and every gradient
     (these shapes were skipped by the bench-shape test and compared nowhere)."""
-    from uno_amd.integral_operators import _resample3d_plan, pointwise_op_3D
+    from uno_amd.integral_operators import pointwise_op_3D
+    from uno_amd.spectral3d import _resample3d_plan
     din, dout = cfg
     dev = torch.device("cuda:0")
     assert _resample3d_plan(din, dout, dev) is None
@@ -306,7 +307,8 @@ def test_operator_block_3d_one_buffer_equals_branch_sum(geom, normalize, non_lin
     same module's two branches run separately and summed by stock ops (reference integral_operators.py:506-512)."""
     import torch.nn.functional as F
     from uno_amd import _native
-    from uno_amd.integral_operators import OperatorBlock_3D, _resample3d_plan, instance_norm_gelu
+    from uno_amd.integral_operators import OperatorBlock_3D, instance_norm_gelu
+    from uno_amd.spectral3d import _resample3d_plan
     din, dout = geom
     dev = torch.device("cuda:0")
     assert _resample3d_plan(din, dout, dev) is not None

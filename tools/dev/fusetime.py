@@ -1,13 +1,14 @@
 """A/B of the fused `inverse transform + up-sampled addend` kernel (K3-A) in one process on one box:
   (1) kernel level at the two Darcy shapes: K3 alone, K3 + accumulating K7, K3-A
-  (2) the training step with each of the round's switches on / off (alternating groups): integral_operators.FUSE_UPSAMPLE_ADD,
-      PROJECT_BACKWARD_FUSED, PAIR_BACKWARD_GEMMS, REVERSE_SWEEP_RESAMPLE, uno_sweep_alternation
+  (2) the training step with each of the round's switches on / off (alternating groups): block2d.FUSE_UPSAMPLE_ADD,
+      pointwise.PROJECT_BACKWARD_FUSED, uno_sweep_alternation
 python tools/dev/fusetime.py [steps]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
 from uno_amd import _native, resample as rs
-import uno_amd.integral_operators as io
+import uno_amd.block2d as b2
+import uno_amd.pointwise as pw
 from uno_amd.harness import DarcyTrainer, UNO_9, synthetic_darcy_batch
 
 dev = torch.device("cuda:0")
@@ -71,8 +72,6 @@ def ab(label, on_label, off_label, setter):
     print(on_label, min(res[True]), off_label, min(res[False]), flush=True)
 
 
-ab("fuse", "fused", "two-kernel", lambda v: setattr(io, "FUSE_UPSAMPLE_ADD", v))
-ab("project_backward_fused", "fc1 - GELU - fc2 backward without the stored gradient", "three calls", lambda v: setattr(io, "PROJECT_BACKWARD_FUSED", v))
-ab("pair_backward_gemms", "paired", "composite with side stream", lambda v: setattr(io, "PAIR_BACKWARD_GEMMS", v))
-ab("reverse_sweep_resample", "reverse sweep before K1", "after the spectral branch", lambda v: setattr(io, "REVERSE_SWEEP_RESAMPLE", v))
+ab("fuse", "fused", "two-kernel", lambda v: setattr(b2, "FUSE_UPSAMPLE_ADD", v))
+ab("project_backward_fused", "fc1 - GELU - fc2 backward without the stored gradient", "three calls", lambda v: setattr(pw, "PROJECT_BACKWARD_FUSED", v))
 ab("sweep_alternation", "alternating sweeps", "all front to back", _native.sweep_alternation)

@@ -63,7 +63,7 @@ class FlatGradients:
                 assert p.dtype == torch.float32
                 view = seg.view(p.shape)
             p.grad = None
-            p._uno_grad_buffer = view       # where the weight-gradient kernels write this parameter's gradient (integral_operators._grad_target)
+            p._uno_grad_buffer = view       # where the weight-gradient kernels write this parameter's gradient (_param_grads._grad_targets)
             self.views.append(view)
             offsets.append(off)
             off += n

@@ -1,16 +1,18 @@
 """3-D spectral convolution on the HIP path (SpectralConv3d_Uno.forward, reference
 integral_operators.py:385-427): rfftn over (H, W, T) restricted to the four low-frequency corners ->
 per-mode channel mixing with weights1..4 -> zero-padded irfftn, with a custom autograd adjoint that
-saves only the truncated input spectrum."""
+saves only the truncated input spectrum.  Also pointwise_op_3D's FFT resampling on the pruned-DFT kernels
+(plan + Function) and the 3-D operator block in one buffer."""
 from __future__ import annotations
 
 import torch
 from torch.autograd.function import once_differentiable
 
 from . import _native
+from .pointwise import _plain, _wgrad_into
 
 
-def _plain(t):
+def _dense(t):         # (torch's strided copy for every layout; the one-buffer block below goes through pointwise._plain)
     if t.is_complex() and t.is_conj():
         t = t.resolve_conj()
     if t.is_neg():
@@ -21,8 +23,8 @@ def _plain(t):
 class _SpectralConv3dFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w1, w2, w3, w4, d1, d2, d3):
-        x = _plain(x)
-        ws = [_plain(w) for w in (w1, w2, w3, w4)]
+        x = _dense(x)
+        ws = [_dense(w) for w in (w1, w2, w3, w4)]
         y, xt = _native.spectral_conv3d_forward(x, ws, int(d1), int(d2), int(d3))
         ctx.save_for_backward(xt, *ws)
         ctx.in_dims = tuple(x.shape[-3:])
@@ -34,10 +36,121 @@ class _SpectralConv3dFn(torch.autograd.Function):
         xt, *ws = ctx.saved_tensors
         need_gx = ctx.needs_input_grad[0]
         need_gw = any(ctx.needs_input_grad[1:5])
-        gx, gws = _native.spectral_conv3d_backward(_plain(gy), xt, ws, *ctx.in_dims, need_gx=need_gx, need_gw=need_gw)
+        gx, gws = _native.spectral_conv3d_backward(_dense(gy), xt, ws, *ctx.in_dims, need_gx=need_gx, need_gw=need_gw)
         gws = gws or [None] * 4
         return (gx, *gws, None, None, None)
 
 
 def spectral_conv3d(x, weights, dim1, dim2, dim3):
     return _SpectralConv3dFn.apply(x, *weights, dim1, dim2, dim3)
+
+
+def _kept_indices(n_in: int, n_out: int):
+    """Spectrum indices along a complex axis that survive the reference's corner copies into an input-sized zero spectrum
+    (`ft_u[:h] = ft[:h]`, `ft_u[-h:] = ft[-h:]`, h = n_out // 2 - with Python's `-0:` meaning everything) and irfftn's trimming
+    to n_out entries (integral_operators.py:450-463)."""
+    h = n_out // 2
+    idx = set(range(0, min(h, n_in)))
+    idx |= set(range(n_in)) if h == 0 else set(range(max(n_in - h, 0), n_in))
+    return sorted(r for r in idx if r < min(n_in, n_out))
+
+
+_RESAMPLE3D_TABLES = {}
+
+
+def _resample3d_plan(din, dout, device):
+    """(f1, f2, m3) for _native.fft_resample3d, or None when the shape is outside the kernels' range (odd row counts, too many
+    rows or bins, planes too large): the caller then takes the stock FFT path."""
+    key = (tuple(din), tuple(dout), str(device))
+    if key not in _RESAMPLE3D_TABLES:
+        plan = None
+        k1, k2 = _kept_indices(din[0], dout[0]), _kept_indices(din[1], dout[1])
+        m3 = min(dout[2] // 2, din[2] // 2 + 1)
+        ok = (len(k1) >= 2 and len(k1) % 2 == 0 and len(k1) <= 80 and len(k2) >= 2 and len(k2) % 2 == 0 and len(k2) <= 48
+              and 1 <= m3 <= 16 and 16 <= din[1] * din[2] <= 1792 and 16 <= dout[1] * dout[2] <= 1792
+              and din[2] <= 64 and dout[2] <= 64)
+        if ok:
+            t1 = _native.table_to_device(torch.tensor(k1, dtype=torch.int32), device)
+            t2 = _native.table_to_device(torch.tensor(k2, dtype=torch.int32), device)
+            plan = (t1, t2, m3)
+        _RESAMPLE3D_TABLES[key] = plan
+    return _RESAMPLE3D_TABLES[key]
+
+
+class _FftResample3dFn(torch.autograd.Function):
+    """irfftn(corner-copy(rfftn(x)), s=size) of pointwise_op_3D on the pruned-DFT kernels (K1p, K5, K6, K3p with explicit
+    frequency tables); backward is the transpose: the same kernels with sizes swapped and the Hermitian weights on the other side."""
+
+    @staticmethod
+    def forward(ctx, x, size, plan):
+        t1, t2, m3 = plan
+        ctx.plan, ctx.din, ctx.dout = plan, tuple(x.shape[-3:]), tuple(size)
+        scale = 1.0 / (size[0] * size[1] * size[2])
+        return _native.fft_resample3d(_plain(x), size, (t1, t1), (t2, t2), m3, scale, adjoint=False)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        t1, t2, m3 = ctx.plan
+        scale = 1.0 / (ctx.dout[0] * ctx.dout[1] * ctx.dout[2])
+        return _native.fft_resample3d(_plain(gy), ctx.din, (t1, t1), (t2, t2), m3, scale, adjoint=True), None, None
+
+
+class _OperatorBlock3dFn(torch.autograd.Function):
+    """s = SpectralConv3d_Uno(x) + pointwise_op_3D(x) in ONE buffer (reference integral_operators.py:506-512: `x1_out = self.conv(...);
+    x2_out = self.w(...); x_out = x1_out + x2_out`, then F.gelu for blocks without normalisation).
+
+    The spectral branch's inverse transform writes s; the point-wise branch - 1x1x1 convolution (K8), then the reference's FFT crop /
+    resample on the pruned-DFT kernels - ends in a plane-batched inverse transform that ACCUMULATES into s and, for a block whose sum is
+    followed directly by the GELU, writes the activation in the same pass (uno_fft_resample3d_acc).  Backward: the spectral branch
+    writes grad_x, the transposed 1x1x1 convolution accumulates into it.  The element-wise sum (three passes over the output), the
+    GELU (two) and autograd's sum of the two input gradients (three over the input) are gone."""
+
+    @staticmethod
+    def forward(ctx, x, w1, w2, w3, w4, cw, cb, dims, plan, fuse_gelu):
+        ctx.leaves = (cw, cb)
+        x = _plain(x)
+        ws = [_plain(w) for w in (w1, w2, w3, w4)]
+        B, Ci = x.shape[0], x.shape[1]
+        din = tuple(x.shape[2:])
+        Co = cw.shape[0]
+        cwm = _plain(cw).reshape(Co, Ci)
+        cbp = None if cb is None else _plain(cb)
+        s, xt = _native.spectral_conv3d_forward(x, ws, *dims)
+        t = _native.channel_mix(x.view(B, Ci, -1), cwm, cbp).view(B, Co, *din)
+        t1, t2, m3 = plan
+        scale = 1.0 / (dims[0] * dims[1] * dims[2])
+        if fuse_gelu:
+            s, out = _native.fft_resample3d(t, dims, (t1, t1), (t2, t2), m3, scale, adjoint=False, out=s, act=True)
+        else:
+            out = _native.fft_resample3d(t, dims, (t1, t1), (t2, t2), m3, scale, adjoint=False, out=s)
+        ctx.save_for_backward(xt, *ws, cwm, x, s if fuse_gelu else None)
+        ctx.geom = (din, tuple(dims), plan, cb is not None, tuple(cw.shape))
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        xt, w1, w2, w3, w4, cwm, x, pre = ctx.saved_tensors
+        din, dims, plan, has_bias, cw_shape = ctx.geom
+        g = _plain(g)
+        if pre is not None:
+            g = torch.ops.aten.gelu_backward(g, pre)
+        B, Co = g.shape[0], g.shape[1]
+        Ci = cwm.shape[1]
+        need_gx = ctx.needs_input_grad[0]
+        need_gw = any(ctx.needs_input_grad[1:5])
+        need_gc = ctx.needs_input_grad[5] or (has_bias and ctx.needs_input_grad[6])
+        gx, gws = _native.spectral_conv3d_backward(g, xt, [w1, w2, w3, w4], *din, need_gx=need_gx, need_gw=need_gw)
+        gws = gws or [None] * 4
+        gcw = gcb = None
+        if need_gx or need_gc:
+            t1, t2, m3 = plan
+            scale = 1.0 / (dims[0] * dims[1] * dims[2])
+            g_t = _native.fft_resample3d(g, din, (t1, t1), (t2, t2), m3, scale, adjoint=True).view(B, Co, -1)
+            if need_gx:
+                _native.channel_mix(g_t, cwm, None, transpose_w=True, out=gx.view(B, Ci, -1))        # accumulates into the spectral branch's gx
+            if need_gc:
+                gcw, gcb = _wgrad_into(ctx.leaves, g_t, x.view(B, Ci, -1), None, ctx.needs_input_grad[5], has_bias and ctx.needs_input_grad[6])
+                gcw = None if gcw is None else gcw.view(cw_shape)
+        return (gx, *gws, gcw, gcb, None, None, None)
