@@ -1,4 +1,4 @@
-"""K8 / K9 (csrc/channel_mix.hip) against torch in float64: the 1x1 convolution of pointwise_op_2D/3D (reference
+"""K8 / K9 (csrc/channel_mix.hip, csrc/channel_wgrad.hip) against torch in float64: the 1x1 convolution of pointwise_op_2D/3D (reference
 integral_operators.py:219, 439) and the channels-first lift / projection layers - forward, input gradient,
 weight and bias gradient.  f32 accumulation: tolerance 2e-6 (l2-relative) for the channel sums, 2e-5 for the
 pixel-long reductions of the weight / bias gradient."""

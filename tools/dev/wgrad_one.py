@@ -1,5 +1,5 @@
 """rocprofv3 / PMC target: a few weight-gradient calls of one 1x1 layer.  python tools/dev/wgrad_one.py Ci Co S [B] [mix] [lib.so]
-(mix: the forward call instead; lib.so: a library variant, e.g. the cycle-stamped build `tools/dev/mkvariant.py cwsstamps channel_mix.hip -DUNO_CWS_STAMPS`)"""
+(mix: the forward call instead; lib.so: a library variant, e.g. the cycle-stamped build `tools/dev/mkvariant.py cwsstamps channel_wgrad.hip -DUNO_CWS_STAMPS`)"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch

@@ -143,70 +143,68 @@ def _ptr(t: torch.Tensor):
     return C.c_void_p(t.data_ptr())
 
 
+def _opt(t):
+    """pointer of an optional tensor (None: NULL)"""
+    return _ptr(t) if t is not None else C.c_void_p(0)
+
+
+def _count(lead) -> int:
+    """product of the leading dimensions"""
+    n = 1
+    for d in lead:
+        n *= d
+    return n
+
+
 def _stream(t: torch.Tensor):
     return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
-class _any_mode_scratch:
-    """Scratch of the any-mode transforms (mode counts beyond the MFMA kernels' range: the reference's DEFAULT modes).  The library
-    allocates nothing: `needs` = (n_img, H, W, m1, m2) of every transform the call may run; the largest requirement is taken from
-    torch's caching allocator (stream-ordered: the block is reused only by later work on this stream), registered for this thread
-    for the duration of the call and cleared afterwards."""
+class _scratch:
+    """`bytes` of device scratch taken from torch's caching allocator (stream-ordered: the block is reused only by later work on this
+    stream), registered for this thread (uno_scratch_provide) for the duration of the call and cleared afterwards; the library
+    allocates nothing."""
+
+    def __init__(self, device, nbytes):
+        self.bytes, self.device, self.buf = nbytes, device, None
+
+    def __enter__(self):
+        if self.bytes > 0:
+            self.buf = torch.empty(self.bytes, dtype=torch.uint8, device=self.device)
+            _check(lib().uno_scratch_provide(_ptr(self.buf), self.bytes), "uno_scratch_provide")
+        return self
+
+    def __exit__(self, *exc):
+        if self.bytes > 0:
+            lib().uno_scratch_provide(None, 0)
+        return False
+
+
+class _any_mode_scratch(_scratch):
+    """Scratch of the any-mode transforms (mode counts beyond the MFMA kernels' range: the reference's DEFAULT modes):
+    `needs` = (n_img, H, W, m1, m2) of every transform the call may run; the largest requirement is taken."""
 
     def __init__(self, device, *needs):
         L = lib()
-        self.bytes = max((int(L.uno_dft2d_any_ws_bytes(*[int(v) for v in n])) for n in needs), default=0)
-        self.device = device
-        self.buf = None
-
-    def __enter__(self):
-        if self.bytes > 0:
-            self.buf = torch.empty(self.bytes, dtype=torch.uint8, device=self.device)
-            _check(lib().uno_scratch_provide(_ptr(self.buf), self.bytes), "uno_scratch_provide")
-        return self
-
-    def __exit__(self, *exc):
-        if self.bytes > 0:
-            lib().uno_scratch_provide(None, 0)
-        return False
+        _scratch.__init__(self, device, max((int(L.uno_dft2d_any_ws_bytes(*[int(v) for v in n])) for n in needs), default=0))
 
 
-class _mix_scratch:
-    """Scratch of the wide channel-mix layers (uno_channel_mix_ws_bytes: the weights pre-split for the bf16 matrix pipe), taken from
-    torch's caching allocator and registered for this thread for the duration of the call - like _any_mode_scratch."""
+class _mix_scratch(_scratch):
+    """Scratch of the wide channel-mix layers (uno_channel_mix_ws_bytes: the weights pre-split for the bf16 matrix pipe)."""
 
     def __init__(self, device, Ci, Co, P, bf16):
-        self.bytes = int(lib().uno_channel_mix_ws_bytes(int(Ci), int(Co), int(P), 1 if bf16 else 0))
-        self.device = device
-        self.buf = None
-
-    def __enter__(self):
-        if self.bytes > 0:
-            self.buf = torch.empty(self.bytes, dtype=torch.uint8, device=self.device)
-            _check(lib().uno_scratch_provide(_ptr(self.buf), self.bytes), "uno_scratch_provide")
-        return self
-
-    def __exit__(self, *exc):
-        if self.bytes > 0:
-            lib().uno_scratch_provide(None, 0)
-        return False
+        _scratch.__init__(self, device, int(lib().uno_channel_mix_ws_bytes(int(Ci), int(Co), int(P), 1 if bf16 else 0)))
 
 
-def _require(t: torch.Tensor, dtype, name: str):
+def _require(t: torch.Tensor, dtype, name: str, dense: bool = True):
+    """a device tensor of `dtype`; dense=False: of any strides (the transposing copy reads channels-last views)"""
     if not t.is_cuda:
-        raise RuntimeError(f"uno_amd: {name} must live on a HIP device (got {t.device}); the spectral "
-                           "convolution runs only on the MI355X kernels")
+        raise RuntimeError(f"uno_amd: {name} must live on a HIP device (got {t.device})"
+                           + ("; the spectral convolution runs only on the MI355X kernels" if dense else ""))
     if t.dtype != dtype:
         raise RuntimeError(f"uno_amd: {name} must be {dtype} (got {t.dtype})")
-    if not t.is_contiguous():
+    if dense and not t.is_contiguous():
         raise RuntimeError(f"uno_amd: {name} must be contiguous")
-
-
-def _require_dev(t: torch.Tensor, dtype, name: str):
-    if not t.is_cuda:
-        raise RuntimeError(f"uno_amd: {name} must live on a HIP device (got {t.device})")
-    if t.dtype != dtype:
-        raise RuntimeError(f"uno_amd: {name} must be {dtype} (got {t.dtype})")
 
 
 def _act_dtype(t, name):
@@ -229,6 +227,32 @@ def _weights_half(w1, w2, bf16):
     _require(w1, torch.complex64, "weights1")
     _require(w2, torch.complex64, "weights2")
     return False
+
+
+def _complex_grad_buffers(out, shape, n: int, device, accumulate: bool):
+    """n fresh complex64 weight-gradient tensors of `shape`, or the given ones validated -> (list, accumulate: False for fresh ones)"""
+    if out is None:
+        return [torch.empty(shape, dtype=torch.complex64, device=device) for _ in range(n)], False
+    gws = list(out)
+    for t in gws:
+        _require(t, torch.complex64, "weight-gradient buffer")
+        if tuple(t.shape) != tuple(shape):
+            raise RuntimeError("uno_amd: weight-gradient buffer has the wrong shape")
+    return gws, accumulate
+
+
+def _real_grad_buffers(out_w, out_b, Ci: int, Co: int, need_bias: bool, device, accumulate: bool):
+    """fresh float32 gw (Co, Ci) / gb (Co) or None, or out_w / out_b validated -> (gw, gb, accumulate: False for fresh ones)"""
+    if out_w is None:
+        gw = torch.empty((Co, Ci), dtype=torch.float32, device=device)
+        return gw, (torch.empty((Co,), dtype=torch.float32, device=device) if need_bias else None), False
+    gw, gb = out_w, (out_b if need_bias else None)
+    _require(gw, torch.float32, "weight-gradient buffer")
+    if gw.numel() != Co * Ci or (need_bias and (gb is None or gb.numel() != Co)):
+        raise RuntimeError("uno_amd: gradient buffers do not match the layer")
+    if gb is not None:
+        _require(gb, torch.float32, "bias-gradient buffer")
+    return gw, gb, accumulate
 
 
 def spectral_conv2d_forward(x, w1, w2, Ho: int, Wo: int, xt_out=None):
@@ -271,21 +295,12 @@ def spectral_conv2d_backward(gy, xt, w1, w2, H: int, W: int, need_gx=True, need_
     L = lib()
     with torch.cuda.device(gy.device):
         gx = torch.empty((B, Ci, H, W), dtype=gy.dtype, device=gy.device) if need_gx else None
-        if need_gw and gw_out is not None:
-            gw1, gw2 = gw_out
-            for t in gw_out:
-                _require(t, torch.complex64, "weight-gradient buffer")
-                if tuple(t.shape) != (Ci, Co, m1, m2):
-                    raise RuntimeError("uno_amd: weight-gradient buffer has the wrong shape")
-        else:
-            accumulate_gw = False
-            gw1 = torch.empty((Ci, Co, m1, m2), dtype=torch.complex64, device=gy.device) if need_gw else None
-            gw2 = torch.empty((Ci, Co, m1, m2), dtype=torch.complex64, device=gy.device) if need_gw else None
+        gw1, gw2, accumulate_gw = None, None, accumulate_gw and need_gw
+        if need_gw:
+            (gw1, gw2), accumulate_gw = _complex_grad_buffers(gw_out, (Ci, Co, m1, m2), 2, gy.device, accumulate_gw)
         ws = torch.empty(max(1, L.uno_spectral_conv2d_bwd_ws_bytes(B, Ci, Co, m1, m2)), dtype=torch.uint8, device=gy.device)
-        null = C.c_void_p(0)
         with _any_mode_scratch(gy.device, (B * Co, Ho, Wo, m1, m2), (B * Ci, H, W, m1, m2)):
-            rc = L.uno_spectral_conv2d_backward_acc(_ptr(gy), _ptr(xt), _ptr(w1), _ptr(w2), _ptr(gx) if need_gx else null,
-                                                    _ptr(gw1) if need_gw else null, _ptr(gw2) if need_gw else null,
+            rc = L.uno_spectral_conv2d_backward_acc(_ptr(gy), _ptr(xt), _ptr(w1), _ptr(w2), _opt(gx), _opt(gw1), _opt(gw2),
                                                     _ptr(ws), B, Ci, Co, H, W, Ho, Wo, m1, m2, 2 if wh else (1 if bf16 else 0),
                                                     1 if accumulate_gw else 0, _stream(gy))
     _check(rc, "uno_spectral_conv2d_backward")
@@ -300,9 +315,7 @@ def fft_resample3d(x, out_size, f1, f2, m3: int, scale: float, adjoint: bool, ou
     _require(x, torch.float32, "x")
     *lead, D1, D2, D3 = x.shape
     M1, M2, M3 = (int(v) for v in out_size)
-    n = 1
-    for d in lead:
-        n *= d
+    n = _count(lead)
     for t in (*f1, *f2):
         if t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous():
             raise RuntimeError("uno_amd: frequency tables must be contiguous int32 device tensors")
@@ -315,7 +328,7 @@ def fft_resample3d(x, out_size, f1, f2, m3: int, scale: float, adjoint: bool, ou
             if tuple(out.shape) != (*lead, M1, M2, M3) or not out.is_contiguous():
                 raise RuntimeError(f"uno_amd: out must be a contiguous {(*lead, M1, M2, M3)} tensor")
             ya = torch.empty_like(out) if act else None
-            rc = L.uno_fft_resample3d_acc(_ptr(x), _ptr(out), _ptr(ya) if act else C.c_void_p(0), _ptr(ws), n, D1, D2, D3, M1, M2, M3,
+            rc = L.uno_fft_resample3d_acc(_ptr(x), _ptr(out), _opt(ya), _ptr(ws), n, D1, D2, D3, M1, M2, M3,
                                           J1, _ptr(f1[0]), _ptr(f1[1]), J2, _ptr(f2[0]), _ptr(f2[1]), int(m3), float(scale),
                                           int(adjoint), int(not adjoint), _stream(x))
             _check(rc, "uno_fft_resample3d_acc")
@@ -332,9 +345,7 @@ def dft2d_forward(images, m1, m2, scale=1.0, hermitian_cols=False, mask_overlap=
     spectra go to channels [channel_offset, channel_offset + C1) of `out`.  bf16 images: plain form only."""
     bf16 = _act_dtype(images, "images")
     *lead, H, W = images.shape
-    n = 1
-    for d in lead:
-        n *= d
+    n = _count(lead)
     if out is None:
         spec = torch.empty((*lead, 2 * m1, m2), dtype=torch.complex64, device=images.device)
         with torch.cuda.device(images.device):
@@ -385,9 +396,7 @@ def dft2d_inverse(spec, H, W, scale=1.0, hermitian_cols=True, mask_overlap=True,
         _require(t, torch.float32, "addend")
         if channels is not None or dtype != torch.float32 or tuple(t.shape[:-2]) != tuple(lead):
             raise RuntimeError("uno_amd: dft2d_inverse(addend=) takes the plain float32 form with one addend image per spectrum")
-        n = 1
-        for d in lead:
-            n *= d
+        n = _count(lead)
         img = torch.empty((*lead, H, W), dtype=torch.float32, device=spec.device)
         with torch.cuda.device(spec.device):
             rc = lib().uno_dft2d_inverse_add(_ptr(spec), _ptr(img), n, H, W, m1, m2, float(scale), int(hermitian_cols), int(mask_overlap),
@@ -395,9 +404,7 @@ def dft2d_inverse(spec, H, W, scale=1.0, hermitian_cols=True, mask_overlap=True,
         _check(rc, "uno_dft2d_inverse_add")
         return img
     if channels is None:
-        n = 1
-        for d in lead:
-            n *= d
+        n = _count(lead)
         if dtype not in (torch.float32, torch.bfloat16):
             raise RuntimeError("uno_amd: images are float32 or bfloat16")
         img = torch.empty((*lead, H, W), dtype=dtype, device=spec.device)
@@ -451,15 +458,7 @@ def mode_wgrad(xt, go, weight_shape, ncorner: int, out=None, accumulate: bool = 
     _require(go, torch.complex64, "grad spectrum")
     B, Ci = xt.shape[:2]
     Co = go.shape[1]
-    if out is None:
-        accumulate = False
-        gws = [torch.empty(weight_shape, dtype=torch.complex64, device=xt.device) for _ in range(ncorner)]
-    else:
-        gws = list(out)
-        for t in gws:
-            _require(t, torch.complex64, "weight-gradient buffer")
-            if tuple(t.shape) != tuple(weight_shape):
-                raise RuntimeError("uno_amd: weight-gradient buffer has the wrong shape")
+    gws, accumulate = _complex_grad_buffers(out, weight_shape, ncorner, xt.device, accumulate)
     Mc = gws[0][0, 0].numel()
     with torch.cuda.device(xt.device):
         rc = lib().uno_mode_wgrad_acc(_ptr(xt), _ptr(go), _ptr_array(gws), B, Ci, Co, ncorner, Mc, 1 if accumulate else 0, _stream(xt))
@@ -479,15 +478,7 @@ def mode_backward(xt, go, weights, out=None, accumulate: bool = False):
     Co = go.shape[1]
     nc = len(weights)
     Mc = weights[0][0, 0].numel()
-    if out is None:
-        accumulate = False
-        gws = [torch.empty(weights[0].shape, dtype=torch.complex64, device=xt.device) for _ in range(nc)]
-    else:
-        gws = list(out)
-        for t in gws:
-            _require(t, torch.complex64, "weight-gradient buffer")
-            if tuple(t.shape) != tuple(weights[0].shape):
-                raise RuntimeError("uno_amd: weight-gradient buffer has the wrong shape")
+    gws, accumulate = _complex_grad_buffers(out, weights[0].shape, nc, xt.device, accumulate)
     gX = torch.empty((B, Ci, nc * Mc), dtype=torch.complex64, device=xt.device)
     with torch.cuda.device(xt.device):
         rc = lib().uno_mode_backward(_ptr(xt), _ptr(go), _ptr_array(list(weights)), _ptr(gX), _ptr_array(gws), B, Ci, Co, nc, Mc,
@@ -539,7 +530,7 @@ def spectral_conv3d_backward(gy, xt, ws_, H: int, W: int, T: int, need_gx=True, 
         scratch = torch.empty(max(1, L.uno_spectral_conv3d_bwd_ws_bytes(B, Ci, Co, H, Ho, m1, m2, m3)), dtype=torch.uint8,
                               device=gy.device)
         with _any_mode_scratch(gy.device, (B * Co * Ho, Wo, To, m2, m3), (B * Ci * H, W, T, m2, m3)):
-            rc = L.uno_spectral_conv3d_backward(_ptr(gy), _ptr(xt), _ptr_array(ws_), _ptr(gx) if need_gx else C.c_void_p(0),
+            rc = L.uno_spectral_conv3d_backward(_ptr(gy), _ptr(xt), _ptr_array(ws_), _opt(gx),
                                                 _ptr_array(gws) if need_gw else None, _ptr(scratch), B, Ci, Co,
                                                 H, W, T, Ho, Wo, To, m1, m2, m3, _stream(gy))
     _check(rc, "uno_spectral_conv3d_backward")
@@ -552,9 +543,7 @@ def resample2d(x, Ho: int, Wo: int, tabH, tabW, tilesH=None, out=None):
     out: accumulate into this (..., Ho, Wo) tensor instead of allocating the result."""
     bf16 = _act_dtype(x, "x")
     *lead, H, W = x.shape
-    n = 1
-    for d in lead:
-        n *= d
+    n = _count(lead)
     sH, wH = tabH
     sW, wW = tabW
     accumulate = out is not None
@@ -620,10 +609,10 @@ def channel_mix(x, w, bias=None, transpose_w: bool = False, out=None, act_in: bo
             if tuple(dgelu_of.shape) != (B, Co, P):
                 raise RuntimeError(f"uno_amd: dgelu_of has shape {tuple(dgelu_of.shape)}, expected {(B, Co, P)}")
         fn = lib().uno_channel_mix_bf16 if bf16 else lib().uno_channel_mix
-        rc = fn(_ptr(x), _ptr(w), _ptr(bias) if bias is not None else C.c_void_p(0), _ptr(y),
+        rc = fn(_ptr(x), _ptr(w), _opt(bias), _ptr(y),
                                    B, Ci, Co, P, 1 if transpose_w else 0,
                                    (2 if (dgelu_total and dgelu_of is not None) else 1) if accumulate else 0, 1 if act_in else 0,
-                                   _ptr(dgelu_of) if dgelu_of is not None else C.c_void_p(0), _stream(x))
+                                   _opt(dgelu_of), _stream(x))
     _check(rc, "uno_channel_mix")
     return y
 
@@ -659,8 +648,7 @@ def channel_mix_act_padded(x, w, bias, Hp: int, Wp: int, act_in: bool = False, k
     y = torch.empty((B, Co, H, W), dtype=x.dtype, device=x.device) if keep_y else None
     act = torch.empty((B, Co, Hp, Wp), dtype=x.dtype, device=x.device)
     with torch.cuda.device(x.device):
-        rc = lib().uno_channel_mix_act_padded(_ptr(x), _ptr(w), _ptr(bias) if bias is not None else C.c_void_p(0),
-                                              _ptr(y) if keep_y else C.c_void_p(0), _ptr(act),
+        rc = lib().uno_channel_mix_act_padded(_ptr(x), _ptr(w), _opt(bias), _opt(y), _ptr(act),
                                               B, Ci, Co, H, W, int(Hp), int(Wp), 1 if act_in else 0, _stream(x))
     _check(rc, "uno_channel_mix_act_padded")
     return y, act
@@ -682,9 +670,8 @@ def lift_forward(x, w1, b1, w0, b0, Hp: int, Wp: int):
     B, Cin, H, W = x.shape
     Cm, Co = w1.shape[0], w0.shape[0]
     act = torch.empty((B, Co, Hp, Wp), dtype=x.dtype, device=x.device)
-    null = C.c_void_p(0)
     with torch.cuda.device(x.device):
-        rc = lib().uno_lift_forward(_ptr(x), _ptr(w1), _ptr(b1) if b1 is not None else null, _ptr(w0), _ptr(b0) if b0 is not None else null,
+        rc = lib().uno_lift_forward(_ptr(x), _ptr(w1), _opt(b1), _ptr(w0), _opt(b0),
                                     _ptr(act), B, Cin, Cm, Co, H, W, int(Hp), int(Wp), _stream(x))
     _check(rc, "uno_lift_forward")
     return act
@@ -713,12 +700,11 @@ def lift_backward(x, w1, b1, w0, b0, g_act, g_act2=None):
     gw0 = torch.empty((Co, Cm), dtype=torch.float32, device=dev)
     gb1 = torch.empty((Cm,), dtype=torch.float32, device=dev) if b1 is not None else None
     gb0 = torch.empty((Co,), dtype=torch.float32, device=dev) if b0 is not None else None
-    null = C.c_void_p(0)
     with torch.cuda.device(dev):
         ws = torch.empty(max(1, lib().uno_lift_bwd_ws_bytes(B, Cin, Cm, Co, H, W)), dtype=torch.uint8, device=dev)
-        rc = lib().uno_lift_backward2(_ptr(x), _ptr(w1), _ptr(b1) if b1 is not None else null, _ptr(w0), _ptr(b0) if b0 is not None else null,
-                                     _ptr(g_act), _ptr(g_act2) if g_act2 is not None else null, _ptr(gw1), _ptr(gb1) if gb1 is not None else null, _ptr(gw0),
-                                     _ptr(gb0) if gb0 is not None else null, _ptr(ws), B, Cin, Cm, Co, H, W, int(Hp), int(Wp), _stream(x))
+        rc = lib().uno_lift_backward2(_ptr(x), _ptr(w1), _opt(b1), _ptr(w0), _opt(b0),
+                                     _ptr(g_act), _opt(g_act2), _ptr(gw1), _opt(gb1), _ptr(gw0),
+                                     _opt(gb0), _ptr(ws), B, Cin, Cm, Co, H, W, int(Hp), int(Wp), _stream(x))
     _check(rc, "uno_lift_backward")
     return gw1, gb1, gw0, gb0
 
@@ -737,14 +723,14 @@ def channel_mix_dgelu_padded(x, w, bias, g_padded, act_in: bool = False):
     Hp, Wp = g_padded.shape[2:]
     gz = torch.empty((B, Co, H, W), dtype=x.dtype, device=x.device)
     with torch.cuda.device(x.device):
-        rc = lib().uno_channel_mix_dgelu_padded(_ptr(x), _ptr(w), _ptr(bias) if bias is not None else C.c_void_p(0), _ptr(g_padded), _ptr(gz),
+        rc = lib().uno_channel_mix_dgelu_padded(_ptr(x), _ptr(w), _opt(bias), _ptr(g_padded), _ptr(gz),
                                                 B, Ci, Co, H, W, int(Hp), int(Wp), 1 if act_in else 0, _stream(x))
     _check(rc, "uno_channel_mix_dgelu_padded")
     return gz
 
 
 def channel_mix2_ok(C1: int, Co1, Co: int, P: int) -> bool:
-    """shape rules of the fused two-source / two-destination forms (csrc/channel_mix.hip)"""
+    """shape rules of the fused two-source / two-destination forms (csrc/channel_mix.hip, csrc/channel_wgrad.hip)"""
     if C1 is not None and (C1 < 16 or C1 % 16):
         return False
     if Co1 is not None and (Co1 < 64 or Co1 % 64):
@@ -792,7 +778,6 @@ def channel_mix2(x1, x2, w, bias=None, transpose_w: bool = False, out=None, out2
         _require(dgelu_of, x1.dtype, "dgelu_of")
         if tuple(dgelu_of.shape) != (B, Co1, P):
             raise RuntimeError(f"uno_amd: dgelu_of has shape {tuple(dgelu_of.shape)}, expected {(B, Co1, P)}")
-    null = C.c_void_p(0)
     proj = pw = pb = None
     if project is not None:
         pw, pb = project
@@ -810,12 +795,9 @@ def channel_mix2(x1, x2, w, bias=None, transpose_w: bool = False, out=None, out2
             fn, size = lib().uno_channel_mix2_win, (*_window_args(window, P, bf16), P)
         else:
             fn, size = (lib().uno_channel_mix2_bf16 if bf16 else lib().uno_channel_mix2), (P,)
-        rc = fn(_ptr(x1), _ptr(x2) if x2 is not None else null, C1, _ptr(w), _ptr(bias) if bias is not None else null,
-                _ptr(y1), _ptr(y2) if y2 is not None else null, Co1, _ptr(act) if act is not None else null,
+        rc = fn(_ptr(x1), _opt(x2), C1, _ptr(w), _opt(bias), _ptr(y1), _opt(y2), Co1, _opt(act),
                 B, Ci, Co, *size, 1 if transpose_w else 0, acc_flag, 1 if act_in else 0,
-                _ptr(dgelu_of) if dgelu_of is not None else null,
-                _ptr(pw) if pw is not None else null, _ptr(pb) if pb is not None else null, _ptr(proj) if proj is not None else null,
-                _stream(x1))
+                _opt(dgelu_of), _opt(pw), _opt(pb), _opt(proj), _stream(x1))
     _check(rc, "uno_channel_mix2")
     if split_out is not None:
         return y1, y2
@@ -846,7 +828,7 @@ def channel_wgrad_finish(parts, Ci: int, Co: int, need_bias: bool, out_w=None, o
         if gw.numel() != Co * Ci or (need_bias and (gb is None or gb.numel() != Co)):
             raise RuntimeError("uno_amd: gradient buffers do not match the layer")
     with torch.cuda.device(parts.device):
-        rc = lib().uno_channel_wgrad_finish(_ptr(parts), _ptr(gw), _ptr(gb) if gb is not None else C.c_void_p(0), Ci, Co,
+        rc = lib().uno_channel_wgrad_finish(_ptr(parts), _ptr(gw), _opt(gb), Ci, Co,
                                             parts.numel() // blk, 1 if accumulate else 0, _stream(parts))
     _check(rc, "uno_channel_wgrad_finish")
     return gw, gb
@@ -884,28 +866,18 @@ def channel_wgrad2(gy, x1, x2, need_bias: bool = True, act_x: bool = False, out_
             raise RuntimeError("uno_amd: partial-sum buffer has the wrong size")
         with torch.cuda.device(gy.device):
             fn = L.uno_channel_wgrad2_bf16 if bf16 else L.uno_channel_wgrad2
-            rc = fn(_ptr(gy), _ptr(x1), _ptr(x2) if x2 is not None else C.c_void_p(0), C1, C.c_void_p(0), C.c_void_p(0),
+            rc = fn(_ptr(gy), _ptr(x1), _opt(x2), C1, C.c_void_p(0), C.c_void_p(0),
                     _ptr(partials_out), B, Ci, Co, P, 1 if act_x else 0, 3, _stream(gy))
         _check(rc, "uno_channel_wgrad2")
         return None, None
-    if out_w is None:
-        accumulate = False
-        gw = torch.empty((Co, Ci), dtype=torch.float32, device=gy.device)
-        gb = torch.empty((Co,), dtype=torch.float32, device=gy.device) if need_bias else None
-    else:
-        gw, gb = out_w, (out_b if need_bias else None)
-        _require(gw, torch.float32, "weight-gradient buffer")
-        if gw.numel() != Co * Ci or (need_bias and (gb is None or gb.numel() != Co)):
-            raise RuntimeError("uno_amd: gradient buffers do not match the layer")
-        if gb is not None:
-            _require(gb, torch.float32, "bias-gradient buffer")
+    gw, gb, accumulate = _real_grad_buffers(out_w, out_b, Ci, Co, need_bias, gy.device, accumulate)
     with torch.cuda.device(gy.device):
         if window is not None:
             fn, size, Pl = L.uno_channel_wgrad2_win, (*win, P), win[0] * win[1]
         else:
             fn, size, Pl = (L.uno_channel_wgrad2_bf16 if bf16 else L.uno_channel_wgrad2), (P,), P
         ws = torch.empty(max(1, L.uno_channel_wgrad_ws_bytes(B, Ci, Co, Pl)), dtype=torch.uint8, device=gy.device)
-        rc = fn(_ptr(gy), _ptr(x1), _ptr(x2) if x2 is not None else C.c_void_p(0), C1, _ptr(gw), _ptr(gb) if gb is not None else C.c_void_p(0),
+        rc = fn(_ptr(gy), _ptr(x1), _opt(x2), C1, _ptr(gw), _opt(gb),
                 _ptr(ws), B, Ci, Co, *size, 1 if act_x else 0, 1 if accumulate else 0, _stream(gy))
     _check(rc, "uno_channel_wgrad2")
     return gw, gb
@@ -925,7 +897,7 @@ def channel_wgrad(gy, x, need_bias: bool = True, act_x: bool = False):
     with torch.cuda.device(x.device):
         ws = torch.empty(max(1, L.uno_channel_wgrad_ws_bytes(B, Ci, Co, P)), dtype=torch.uint8, device=x.device)
         fn = L.uno_channel_wgrad_bf16 if bf16 else L.uno_channel_wgrad
-        rc = fn(_ptr(gy), _ptr(x), _ptr(gw), _ptr(gb) if need_bias else C.c_void_p(0), _ptr(ws),
+        rc = fn(_ptr(gy), _ptr(x), _ptr(gw), _opt(gb), _ptr(ws),
                                  B, Ci, Co, P, 1 if act_x else 0, _stream(x))
     _check(rc, "uno_channel_wgrad")
     return gw, gb
@@ -957,7 +929,7 @@ def gelu_project_forward(pre, w, bias=None):
         raise RuntimeError(f"uno_amd: weight has {w.numel()} entries for {Cc} channels")
     out = torch.empty((B, P), dtype=pre.dtype, device=pre.device)
     with torch.cuda.device(pre.device):
-        rc = (lib().uno_gelu_project_forward_bf16 if bf16 else lib().uno_gelu_project_forward)(_ptr(pre), _ptr(w), _ptr(bias) if bias is not None else C.c_void_p(0), _ptr(out),
+        rc = (lib().uno_gelu_project_forward_bf16 if bf16 else lib().uno_gelu_project_forward)(_ptr(pre), _ptr(w), _opt(bias), _ptr(out),
                                             B, Cc, P, _stream(pre))
     _check(rc, "uno_gelu_project_forward")
     return out
@@ -982,7 +954,7 @@ def gelu_project_backward(pre, w, gout, need_bias=True, window=None):
         else:
             fn, size, Pl = (L.uno_gelu_project_backward_bf16 if bf16 else L.uno_gelu_project_backward), (P,), P
         ws = torch.empty(max(1, L.uno_gelu_project_bwd_ws_bytes(B, Cc, Pl)), dtype=torch.uint8, device=pre.device)
-        rc = fn(_ptr(pre), _ptr(w), _ptr(gout), _ptr(gpre), _ptr(gw), _ptr(gb) if need_bias else C.c_void_p(0), _ptr(ws), B, Cc, *size,
+        rc = fn(_ptr(pre), _ptr(w), _ptr(gout), _ptr(gpre), _ptr(gw), _opt(gb), _ptr(ws), B, Cc, *size,
                 _stream(pre))
     _check(rc, "uno_gelu_project_backward")
     return gpre, gw, gb
@@ -1053,25 +1025,14 @@ def project_backward(x1, x2, w, pre, w2, gout, act_in: bool = False, need_bias: 
     L = lib()
     g1 = torch.empty_like(x1)
     g2 = torch.empty_like(x2) if x2 is not None else None
-    if out_w is None:
-        accumulate = False
-        gw = torch.empty((Co, Ci), dtype=torch.float32, device=x1.device)
-        gb = torch.empty((Co,), dtype=torch.float32, device=x1.device) if need_bias else None
-    else:
-        gw, gb = out_w, (out_b if need_bias else None)
-        _require(gw, torch.float32, "weight-gradient buffer")
-        if gw.numel() != Co * Ci or (need_bias and (gb is None or gb.numel() != Co)):
-            raise RuntimeError("uno_amd: gradient buffers do not match the layer")
-        if gb is not None:
-            _require(gb, torch.float32, "bias-gradient buffer")
+    gw, gb, accumulate = _real_grad_buffers(out_w, out_b, Ci, Co, need_bias, x1.device, accumulate)
     gw2 = torch.empty((Co,), dtype=torch.float32, device=x1.device)
     gb2 = torch.empty((1,), dtype=torch.float32, device=x1.device) if need_bias2 else None
-    null = C.c_void_p(0)
     with torch.cuda.device(x1.device):
         ws = torch.empty(max(1, L.uno_project_backward_ws_bytes(B, Ci, Co, Pl)), dtype=torch.uint8, device=x1.device)
-        rc = L.uno_project_backward(_ptr(x1), _ptr(x2) if x2 is not None else null, C1, _ptr(w), _ptr(pre), _ptr(w2), _ptr(gout),
-                                    _ptr(g1), _ptr(g2) if g2 is not None else null, _ptr(gw), _ptr(gb) if gb is not None else null,
-                                    _ptr(gw2), _ptr(gb2) if gb2 is not None else null, _ptr(ws), B, Ci, Co, *geo,
+        rc = L.uno_project_backward(_ptr(x1), _opt(x2), C1, _ptr(w), _ptr(pre), _ptr(w2), _ptr(gout),
+                                    _ptr(g1), _opt(g2), _ptr(gw), _opt(gb),
+                                    _ptr(gw2), _opt(gb2), _ptr(ws), B, Ci, Co, *geo,
                                     1 if act_in else 0, 1 if accumulate else 0, _stream(x1))
     _check(rc, "uno_project_backward")
     return g1, g2, gw, gb, gw2, gb2
@@ -1081,9 +1042,7 @@ def gelu_pad(s, Hp: int, Wp: int):
     """s (..., H, W) f32 -> (..., Hp, Wp) = zero-pad(gelu(s)) at the end of both axes."""
     bf16 = _act_dtype(s, "s")
     *lead, H, W = s.shape
-    n = 1
-    for d in lead:
-        n *= d
+    n = _count(lead)
     out = torch.empty((*lead, Hp, Wp), dtype=s.dtype, device=s.device)
     with torch.cuda.device(s.device):
         rc = (lib().uno_gelu_pad_bf16 if bf16 else lib().uno_gelu_pad)(_ptr(s), C.c_void_p(0), _ptr(out), n, H, W, Hp, Wp, 0, _stream(s))
@@ -1097,9 +1056,7 @@ def gelu_pad_backward(s, gy):
     _require(gy, s.dtype, "grad_output")
     *lead, H, W = s.shape
     Hp, Wp = gy.shape[-2:]
-    n = 1
-    for d in lead:
-        n *= d
+    n = _count(lead)
     out = torch.empty_like(s)
     with torch.cuda.device(s.device):
         rc = (lib().uno_gelu_pad_bf16 if bf16 else lib().uno_gelu_pad)(_ptr(s), _ptr(gy), _ptr(out), n, H, W, Hp, Wp, 1, _stream(s))
@@ -1127,12 +1084,10 @@ def channels_last_pitch(t):
 
 def to_channels_first(t):
     """A channels-last f32 activation (see channels_last_pitch) as a contiguous (B, C, *grid) tensor, by the tiled transposing copy."""
-    _require_dev(t, torch.float32, "activation")
+    _require(t, torch.float32, "activation", dense=False)
     ld, sb = channels_last_pitch(t)
     B, Cc = t.shape[:2]
-    P = 1
-    for d in t.shape[2:]:
-        P *= d
+    P = _count(t.shape[2:])
     out = torch.empty(t.shape, dtype=t.dtype, device=t.device)
     with torch.cuda.device(t.device):
         rc = lib().uno_transpose_batched(_ptr(t), _ptr(out), B, P, Cc, ld, sb if B > 1 else 0, P, Cc * P, _stream(t))
@@ -1152,9 +1107,8 @@ def instnorm_forward(x, gamma, beta, eps: float, gelu: bool):
     y = torch.empty_like(x)
     mean = torch.empty(rows, dtype=torch.float32, device=x.device)
     rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
-    null = C.c_void_p(0)
     with torch.cuda.device(x.device):
-        rc = (lib().uno_instnorm_forward_bf16 if bf16 else lib().uno_instnorm_forward)(_ptr(x), _ptr(gamma) if gamma is not None else null, _ptr(beta) if beta is not None else null,
+        rc = (lib().uno_instnorm_forward_bf16 if bf16 else lib().uno_instnorm_forward)(_ptr(x), _opt(gamma), _opt(beta),
                                         _ptr(y), _ptr(mean), _ptr(rstd), rows, Cc, N, float(eps), 1 if gelu else 0, _stream(x))
     _check(rc, "uno_instnorm_forward")
     return y, mean, rstd
@@ -1170,10 +1124,9 @@ def instnorm_backward(x, gy, gamma, beta, mean, rstd, gelu: bool):
     gx = torch.empty_like(x)
     s1 = torch.empty((B, Cc), dtype=torch.float32, device=x.device)
     s2 = torch.empty((B, Cc), dtype=torch.float32, device=x.device)
-    null = C.c_void_p(0)
     with torch.cuda.device(x.device):
-        rc = (lib().uno_instnorm_backward_bf16 if bf16 else lib().uno_instnorm_backward)(_ptr(x), _ptr(gy), _ptr(gamma) if gamma is not None else null,
-                                         _ptr(beta) if beta is not None else null, _ptr(mean), _ptr(rstd), _ptr(gx), _ptr(s1), _ptr(s2),
+        rc = (lib().uno_instnorm_backward_bf16 if bf16 else lib().uno_instnorm_backward)(_ptr(x), _ptr(gy), _opt(gamma),
+                                         _opt(beta), _ptr(mean), _ptr(rstd), _ptr(gx), _ptr(s1), _ptr(s2),
                                          rows, Cc, N, 1 if gelu else 0, _stream(x))
     _check(rc, "uno_instnorm_backward")
     return gx, s1, s2
@@ -1223,7 +1176,7 @@ class AdamPlan:
             raise RuntimeError("uno_amd: Adam device hyper-parameters must be three float64 values on the parameters' device")
         with torch.cuda.device(self.device):
             rc = lib().uno_adam_step_multi_dev(self.n, self.p, self.g, self.m, self.v, self.sizes, self.cplx, lr, beta1, beta2, eps,
-                                               weight_decay, _ptr(counter), _ptr(scalars), _ptr(hyper) if hyper is not None else None,
+                                               weight_decay, _ptr(counter), _ptr(scalars), _opt(hyper),
                                                C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
         _check(rc, "uno_adam_step_multi_dev")
 

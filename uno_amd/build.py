@@ -20,8 +20,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libuno_spectral.so")
 STAMP = os.path.join(LIBDIR, "libuno_spectral.stamp")
-SOURCES = ["capi.hip", "dft2d_fwd.hip", "dft2d_fwd_r4.hip", "dft2d_inv.hip", "dft2d_inv_b.hip", "dft2d_inv_c.hip", "dft2d_inv_add.hip", "dft2d_plane.hip", "dft2d_b16.hip", "mode_gemm.hip", "cdft_axis.hip", "dft3d_volume.hip", "dft_generic.hip", "resample2d.hip", "channel_mix.hip", "adam.hip", "pointwise_fused.hip", "instnorm.hip", "lift_bwd.hip"]
-HEADERS = ["uno_common.h", "dft2d_fwd_kernel.h", "dft2d_fwd_ft_kernel.h", "dft2d_fwd_ht_kernel.h", "dft2d_inv_kernel.h", "dft2d_inv_add_kernel.h", os.path.join("..", "..", "include", "uno_spectral.h")]
+SOURCES = ["capi.hip", "capi_spectral.hip", "capi_pointwise.hip", "dft2d_fwd.hip", "dft2d_fwd_r4.hip", "dft2d_inv.hip", "dft2d_inv_b.hip", "dft2d_inv_c.hip", "dft2d_inv_add.hip", "dft2d_plane.hip", "dft2d_b16.hip", "mode_gemm.hip", "cdft_axis.hip", "dft3d_volume.hip", "dft_generic.hip", "resample2d.hip", "channel_mix.hip", "channel_wgrad.hip", "adam.hip", "pointwise_fused.hip", "instnorm.hip", "lift_bwd.hip"]
+HEADERS = ["uno_common.h", "channel_mix_common.h", "dft2d_fwd_kernel.h", "dft2d_fwd_ft_kernel.h", "dft2d_fwd_ht_kernel.h", "dft2d_inv_kernel.h", "dft2d_inv_add_kernel.h", os.path.join("..", "..", "include", "uno_spectral.h")]
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]
 # per-source flags.  mode_gemm.hip: its 4x4x1 kernel keeps 16 accumulator tiles live across a 4-step unrolled loop; with the
@@ -70,7 +70,9 @@ def build(force: bool = False, verbose: bool = False) -> str:
             print(r.stderr)
         return obj
 
-    with cf.ThreadPoolExecutor(max_workers=min(len(SOURCES), os.cpu_count() or 1)) as ex:
+    # (os.cpu_count() is the whole machine's; a job on a shared host gets fewer: MAX_JOBS, 16 unless set)
+    jobs = min(len(SOURCES), os.cpu_count() or 1, int(os.environ.get("MAX_JOBS", 16)))
+    with cf.ThreadPoolExecutor(max_workers=max(1, jobs)) as ex:
         objs = list(ex.map(compile_one, SOURCES))
     cmd = [hipcc, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-fno-gpu-rdc", *objs, "-o", LIB]
     r = subprocess.run(cmd, capture_output=True, text=True)

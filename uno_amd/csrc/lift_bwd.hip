@@ -5,7 +5,7 @@
 //   gh = gelu'(h) * (w0^T gz),  gw1 = sum_px gh x^T,  gb1 = sum_px gh      (x is data: gh has no other consumer and is not stored)
 //   gw0 = sum_px gz a^T,  gb0 = sum_px gz               -> one (Co, Cm + 1) block of partial sums per workgroup, summed by K9's second stage
 //
-// The four-kernel form (capi.hip, uno_lift_backward) writes gz (64 channels) once and reads it twice: 2.2 GB of the pass's 3.8 GB.
+// The four-kernel form (capi_pointwise.hip, uno_lift_backward) writes gz (64 channels) once and reads it twice: 2.2 GB of the pass's 3.8 GB.
 // Here gz lives in LDS only: a workgroup of 256 threads owns 128 pixels, recomputes a and z, and runs the three small GEMMs
 // (z: 64 x 32 x 128, gh: 32 x 64 x 128, gw0: 64 x 32 over its 128 pixels) on v_mfma_f32_16x16x4_f32 from LDS-resident operands.
 // HBM traffic: x (12 B per pixel), g (256 B) and 9 KB of partial sums per TPW tiles.

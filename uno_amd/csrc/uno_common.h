@@ -266,6 +266,9 @@ inline bool ensure_dynamic_lds(const void* kernel, size_t bytes, int* slot) {
     return true;
 }
 void set_error(const char* fmt, ...);
+// caller-provided scratch of the calling thread (uno_scratch_provide; the one record per thread lives in capi.hip)
+struct Scratch { void* ptr; size_t bytes; };
+const Scratch& thread_scratch();
 // Compute units the launch geometries may count on: the device's, minus those the caller set aside for concurrently running
 // communication kernels (uno_reserve_cus: RCCL's all-reduce of the previous gradient buckets runs beside the backward pass under data
 // parallelism, and a geometry tuned to "one workgroup per CU on all CUs" would run a second round for the CUs RCCL holds)
@@ -352,7 +355,7 @@ int launch_instnorm_bwd(const void* x, const void* gy, const float* gamma, const
 long long channel_wgrad_ws_floats(int B, int Ci, int Co, long long P, int* nsplit_out);
 int launch_channel_wgrad(const void* gy, const void* x, float* gw, float* gb, float* ws, int B, int Ci, int Co, long long P,
                          int act_x, int bf16, hipStream_t s);
-// pb (channel_mix.hip, ChannelWgradParams::pb_*): gy is the layer's pre-activation and stands for w2[o] gelu'(gy) g; the projection's own
+// pb (channel_wgrad.hip, ChannelWgradParams::pb_*): gy is the layer's pre-activation and stands for w2[o] gelu'(gy) g; the projection's own
 // gradients go to gw2 (Co) / gb2 (1, may be null); ws then holds channel_wgrad_pb_ws_floats() floats
 struct WgradProjectedBack { const float* w2 = nullptr; const float* g = nullptr; float* gw2 = nullptr; float* gb2 = nullptr; };
 bool channel_wgrad_pb_applies(int B, int Ci, int Co, int C1, long long P);
@@ -360,7 +363,7 @@ long long channel_wgrad_pb_ws_floats(int B, int Ci, int Co, long long P);
 int launch_channel_wgrad2(const void* gy, const void* x, const void* x2, int C1, float* gw, float* gb, float* ws, int B, int Ci, int Co,
                           long long P, int act_x, int accumulate, int bf16, hipStream_t s, const PixelWindow& win = PixelWindow(),
                           const WgradProjectedBack& pb = WgradProjectedBack());
-// weight gradient with the X operand virtual (see ChannelMixParams: gelu of it is taken when act_x): Ci <= 32 virtual channels
+// weight gradient with the X operand virtual (see ChannelMixParams, channel_mix.hip: gelu of it is taken when act_x): Ci <= 32 virtual channels
 int launch_channel_wgrad_vh(const void* gy, const float* vh_x, const float* vh_w, const float* vh_b, int vh_ci, float* gw, float* gb, float* ws,
                             int B, int Ci, int Co, long long P, int act_x, hipStream_t s, int accumulate = 0);
 // lift_bwd.hip: the lift's backward pass with gz in LDS only (32 middle / 64 output channels)

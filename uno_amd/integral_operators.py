@@ -105,7 +105,7 @@ class SpectralConv2d_Uno(nn.Module):
         return spectral_conv2d(x, self.weights1, self.weights2, self.dim1, self.dim2)
 
     def _bf16_kernels(self):
-        """True when the bf16-image transform kernels cover this layer's mode counts (csrc/capi.hip: modes1 <= 40, modes2 <= 48)."""
+        """True when the bf16-image transform kernels cover this layer's mode counts (csrc/capi_spectral.hip: modes1 <= 40, modes2 <= 48)."""
         return self.modes1 <= 40 and self.modes2 <= 48
 
 

@@ -37,7 +37,7 @@ def _plain(t: torch.Tensor) -> torch.Tensor:
 
 
 class _ChannelMixFn(torch.autograd.Function):
-    """y[b] = W . x[b] + bias on (B, C, pixels) views with the K8 / K9 kernels (csrc/channel_mix.hip)."""
+    """y[b] = W . x[b] + bias on (B, C, pixels) views with the K8 / K9 kernels (csrc/channel_mix.hip, csrc/channel_wgrad.hip)."""
 
     @staticmethod
     def forward(ctx, x, w, bias, leaves=None):
@@ -202,7 +202,7 @@ class GradJoin:
 
 
 # ---- a layer on the channel concatenation of two tensors, never built: one pass over every operand where the kernels' split
-# rules allow (csrc/channel_mix.hip: sources split at a multiple of 16 channels, destinations / weight-gradient tiles at 64),
+# rules allow (csrc/channel_mix.hip, csrc/channel_wgrad.hip: sources split at a multiple of 16 channels, destinations / weight-gradient tiles at 64),
 # two accumulating calls otherwise
 def _mix2_forward(x1, x2, w, bias, act_in=False, out=None, accumulate=False):
     """Wm . cat(x1, x2) + bias -> (B, Co, P); w (Co, C1 + C2).  out + accumulate: out += ..."""
