@@ -258,10 +258,11 @@ def spectral_conv3d_dense_bwd(gy, X, ws, H, W, T):
 # --------------------------------------------------------------------------- #
 def spectral_conv2d_fft(x: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor, Ho: int, Wo: int) -> torch.Tensor:
     """rfft2(norm=forward) -> two corner contractions -> zero-padded irfft2
-    (integral_operators.py:187-206).  Output is float32 (out_ft is cfloat)."""
+    (integral_operators.py:187-206).  out_ft takes the spectrum's dtype: cfloat for the reference's float32 input, complex128 for
+    the float64 runs the parity tests use as their high-precision reference."""
     m1, m2 = w1.shape[2:]
     spec = torch.fft.rfft2(x, norm="forward")
-    out = torch.zeros(x.shape[0], w1.shape[1], Ho, Wo // 2 + 1, dtype=torch.cfloat, device=x.device)
+    out = torch.zeros(x.shape[0], w1.shape[1], Ho, Wo // 2 + 1, dtype=spec.dtype, device=x.device)
     for rows_in, rows_out, w in ((slice(None, m1), slice(None, m1), w1), (slice(-m1, None), slice(-m1, None), w2)):
         out[:, :, rows_out, :m2] = torch.einsum("bixy,ioxy->boxy", spec[:, :, rows_in, :m2], w)
     return torch.fft.irfft2(out, s=(Ho, Wo), norm="forward")
@@ -271,7 +272,7 @@ def spectral_conv3d_fft(x: torch.Tensor, ws, Ho: int, Wo: int, To: int) -> torch
     """integral_operators.py:398-426."""
     m1, m2, m3 = ws[0].shape[2:]
     spec = torch.fft.rfftn(x, dim=[-3, -2, -1], norm="forward")
-    out = torch.zeros(x.shape[0], ws[0].shape[1], Ho, Wo, To // 2 + 1, dtype=torch.cfloat, device=x.device)
+    out = torch.zeros(x.shape[0], ws[0].shape[1], Ho, Wo, To // 2 + 1, dtype=spec.dtype, device=x.device)
     lo1, hi1 = slice(None, m1), slice(-m1, None)
     lo2, hi2 = slice(None, m2), slice(-m2, None)
     for (r, c), w in zip(((lo1, lo2), (hi1, lo2), (lo1, hi2), (hi1, hi2)), ws):
@@ -399,6 +400,17 @@ class OracleOperatorBlock3d(nn.Module):
         if self.normalize:
             y = self.normalize_layer(y)
         return F.gelu(y) if self.non_lin else y
+
+
+def to_float64(model: nn.Module) -> nn.Module:
+    """Deep copy of `model` in double precision.  nn.Module.double() converts the real parameters and buffers only; the complex
+    spectral weights are cast to complex128 here, so that the einsum sees one dtype and nothing drops to single precision."""
+    import copy
+    m = copy.deepcopy(model).double()
+    for p in m.parameters():
+        if p.is_complex():
+            p.data = p.data.to(torch.complex128)
+    return m
 
 
 # --------------------------------------------------------------------------- #

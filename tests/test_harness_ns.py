@@ -76,9 +76,11 @@ def test_ns2d_gpu_product():
 
 @pytest.mark.gpu
 def test_ns3d_gpu_product():
-    # InstanceNorm3d runs on the K13 kernel (it was MIOpen's batch norm, 1e-3 / 2e-2 then); what remains is rocFFT vs
-    # pocketfft inside pointwise_op_3D
-    _ns3d(None, torch.device("cuda:0"), 1e-4, 2e-3)
+    # Every layer of the model runs on the library's own kernels (InstanceNorm3d on K13, pointwise_op_3D's resampling on the pruned-DFT
+    # kernels: no stock FFT is left on this path).  Gradient-norm bound: | ||g_P|| - golden | <= ||g_P - g_R64|| + | ||g_R64|| - golden |
+    # <= 1e-4 ||g|| (the whole-model bound of tests/test_hip_workload_parity.py; 4 x the float32-oracle floor of this case is 1.4e-5)
+    # + 8e-6 ||g|| (the float32 golden's own distance from the float64 oracle, measured on the host), rounded up to 2e-4.  It was 2e-3.
+    _ns3d(None, torch.device("cuda:0"), 1e-4, 2e-4)
 
 
 @pytest.mark.gpu
