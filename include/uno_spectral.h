@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define UNO_SPECTRAL_ABI_VERSION 12
+#define UNO_SPECTRAL_ABI_VERSION 13
 
 /* ABI version of the loaded library (== UNO_SPECTRAL_ABI_VERSION it was built with). */
 int uno_abi_version(void);
@@ -91,6 +91,18 @@ int uno_fft_resample3d(const float* x, float* y, void* ws, int n_vol, int D1, in
  * point-wise branch of OperatorBlock_3D (reference integral_operators.py:506-512: x1_out + x2_out, then F.gelu) lands in the buffer
  * the spectral branch wrote - neither the sum nor the activation is a separate pass. */
 int uno_fft_resample3d_acc(const float* x, float* y, float* y_act, void* ws, int n_vol, int D1, int D2, int D3, int M1, int M2, int M3,
+                           int J1, const int* f1_in, const int* f1_out, int J2, const int* f2_in, const int* f2_out, int m3,
+                           float scale, int herm_in, int herm_out, void* stream);
+
+/* ABI 13.  The same operator as uno_fft_resample3d (same tables, same Hermitian-weight contract, the adjoint again the same call with
+ * sizes and tables swapped) on kernels without its shape limits: any J1, J2 in 1 ... 128 (odd counts included), any
+ * 1 <= m3 <= D3/2 + 1 (and <= M3/2 + 1), every axis length of x and y in 2 ... 128 - planes of up to 128 x 128 elements.  Outside that
+ * range the call returns an error that names the limits; table entries are reduced modulo the axis length.  This is what the last two
+ * layers of the reference's Uno3D_T40 need (navier_stokes_uno3d.py:145-159: (32,32,31) -> (48,48,41) -> (64,64,52) at S = 64, pad 3).
+ * Plain f32 FMA kernels, f32 accumulation, results independent of the launch geometry; no accumulate / GELU form.
+ *   ws: uno_fft_resample3d_any_ws_bytes = 8 n_vol (D1 + M1) J2 m3 bytes. */
+long long uno_fft_resample3d_any_ws_bytes(int n_vol, int D1, int M1, int J1, int J2, int m3);
+int uno_fft_resample3d_any(const float* x, float* y, void* ws, int n_vol, int D1, int D2, int D3, int M1, int M2, int M3,
                            int J1, const int* f1_in, const int* f1_out, int J2, const int* f2_in, const int* f2_out, int m3,
                            float scale, int herm_in, int herm_out, void* stream);
 

@@ -14,7 +14,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libuno_spectral.so")
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 _lib = None
 _lock = threading.Lock()
@@ -35,6 +35,8 @@ _SIGNATURES = {
     "uno_fft_resample3d_ws_bytes": (C.c_longlong, [_i] * 6),
     "uno_fft_resample3d": (C.c_int, [_fp] * 3 + [_i] * 8 + [_fp, _fp, _i, _fp, _fp, _i, C.c_float, _i, _i, _fp]),
     "uno_fft_resample3d_acc": (C.c_int, [_fp] * 4 + [_i] * 8 + [_fp, _fp, _i, _fp, _fp, _i, C.c_float, _i, _i, _fp]),
+    "uno_fft_resample3d_any_ws_bytes": (C.c_longlong, [_i] * 6),
+    "uno_fft_resample3d_any": (C.c_int, [_fp] * 3 + [_i] * 8 + [_fp, _fp, _i, _fp, _fp, _i, C.c_float, _i, _i, _fp]),
     "uno_dft2d_forward": (C.c_int, [_fp, _fp] + [_i] * 5 + [C.c_float, _i, _i, _fp]),
     "uno_dft2d_forward_bf16": (C.c_int, [_fp, _fp] + [_i] * 5 + [C.c_float, _i, _i, _fp]),
     "uno_dft2d_inverse_bf16": (C.c_int, [_fp, _fp] + [_i] * 5 + [C.c_float, _i, _i, _fp]),
@@ -337,6 +339,29 @@ def fft_resample3d(x, out_size, f1, f2, m3: int, scale: float, adjoint: bool, ou
         rc = L.uno_fft_resample3d(_ptr(x), _ptr(y), _ptr(ws), n, D1, D2, D3, M1, M2, M3, J1, _ptr(f1[0]), _ptr(f1[1]), J2,
                                   _ptr(f2[0]), _ptr(f2[1]), int(m3), float(scale), int(adjoint), int(not adjoint), _stream(x))
     _check(rc, "uno_fft_resample3d")
+    return y
+
+
+def fft_resample3d_any(x, out_size, f1, f2, m3: int, scale: float, adjoint: bool):
+    """fft_resample3d on the any-grid kernels (uno_fft_resample3d_any): any number of kept rows, any 1 <= m3 <= n/2 + 1, axis lengths
+    2 ... 128.  Same tables and the same adjoint convention; no accumulate / activation form."""
+    _require(x, torch.float32, "x")
+    *lead, D1, D2, D3 = x.shape
+    M1, M2, M3 = (int(v) for v in out_size)
+    n = _count(lead)
+    for t in (*f1, *f2):
+        if t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous():
+            raise RuntimeError("uno_amd: frequency tables must be contiguous int32 device tensors")
+    J1, J2 = f1[0].numel(), f2[0].numel()
+    if f1[1].numel() != J1 or f2[1].numel() != J2:
+        raise RuntimeError("uno_amd: the forward and inverse frequency tables of an axis must have the same length")
+    L = lib()
+    with torch.cuda.device(x.device):
+        ws = torch.empty(max(1, L.uno_fft_resample3d_any_ws_bytes(n, D1, M1, J1, J2, int(m3))), dtype=torch.uint8, device=x.device)
+        y = torch.empty((*lead, M1, M2, M3), dtype=torch.float32, device=x.device)
+        rc = L.uno_fft_resample3d_any(_ptr(x), _ptr(y), _ptr(ws), n, D1, D2, D3, M1, M2, M3, J1, _ptr(f1[0]), _ptr(f1[1]), J2,
+                                      _ptr(f2[0]), _ptr(f2[1]), int(m3), float(scale), int(adjoint), int(not adjoint), _stream(x))
+    _check(rc, "uno_fft_resample3d_any")
     return y
 
 

@@ -392,6 +392,34 @@ int uno_fft_resample3d_acc(const float* x, float* y, float* y_act, void* ws, int
                                1, y_act, stream);
 }
 
+// ---- the same operator on the any-grid kernels (resample3d_any.hip): any row counts, 1 <= modes3 <= n/2 + 1, axes of 2 ... 128
+long long uno_fft_resample3d_any_ws_bytes(int n_vol, int D1, int M1, int J1, int J2, int m3) {
+    (void)J1;       // the J1 spectrum rows live in LDS only
+    return 8LL * n_vol * ((long long)D1 + M1) * J2 * m3;
+}
+
+int uno_fft_resample3d_any(const float* x, float* y, void* ws, int n_vol, int D1, int D2, int D3, int M1, int M2, int M3,
+                           int J1, const int* f1_in, const int* f1_out, int J2, const int* f2_in, const int* f2_out, int m3,
+                           float scale, int herm_in, int herm_out, void* stream) {
+    const char* who = "uno_fft_resample3d_any";
+    const int dims[6] = {D1, D2, D3, M1, M2, M3};
+    for (int d : dims)
+        if (d < 2 || d > 128) {
+            set_error("%s: grid (%d,%d,%d) -> (%d,%d,%d): every axis length must be in 2 ... 128", who, D1, D2, D3, M1, M2, M3);
+            return -1;
+        }
+    if (J1 < 1 || J1 > 128 || J2 < 1 || J2 > 128) { set_error("%s: kept-row counts J1=%d, J2=%d must be in 1 ... 128", who, J1, J2); return -1; }
+    if (m3 < 1 || m3 > D3 / 2 + 1 || m3 > M3 / 2 + 1) {
+        set_error("%s: need 1 <= modes3=%d <= n/2+1 on the last axis %d -> %d", who, m3, D3, M3);
+        return -1;
+    }
+    if (n_vol < 0 || (long long)n_vol * 128 > 0x7fffffffLL) { set_error("%s: bad volume count %d (0 ... 2^24 - 1)", who, n_vol); return -1; }
+    if (n_vol == 0) return 0;
+    if (!x || !y || !ws || !f1_in || !f1_out || !f2_in || !f2_out) { set_error("%s: null pointer", who); return -1; }
+    return launch_resample3d_any(x, y, ws, n_vol, D1, D2, D3, M1, M2, M3, J1, f1_in, f1_out, J2, f2_in, f2_out, m3, scale, herm_in, herm_out,
+                                 (hipStream_t)stream);
+}
+
 static int check_modes3d(const char* who, int H, int W, int T, int Ho, int Wo, int To, int m1, int m2, int m3) {
     if (H < 1 || W < 1 || T < 1 || Ho < 1 || Wo < 1 || To < 1) { set_error("%s: empty grid", who); return -1; }
     if (m1 < 1 || m1 > H || m1 > Ho) { set_error("%s: modes1=%d incompatible with axis %d -> %d", who, m1, H, Ho); return -1; }

@@ -16,7 +16,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..integral_operators import (GradJoin, OperatorBlock_2D, OperatorBlock_3D, channel_mix, channel_mix_cat, channel_mix_cat_project,
-                                  gelu_channel_mix, gelu_channel_mix_pad, gelu_pad2d, gelu_project, lift_gelu_pad)
+                                  enable_native_resample3d_any, gelu_channel_mix, gelu_channel_mix_pad, gelu_pad2d, gelu_project, lift_gelu_pad)
 
 
 class UNO_9(nn.Module):
@@ -236,5 +236,53 @@ class Uno3D_T20(nn.Module):
         c8 = torch.cat([c8, self._resize(lifted, c8)], dim=1)
         if self.padding != 0:
             c8 = c8[..., 2 * self.padding:-2 * self.padding] if self.pad_both else c8[..., :-2 * self.padding]
+        out = gelu_project(channel_mix(c8.contiguous(), self.fc1.weight, self.fc1.bias), self.fc2.weight, self.fc2.bias)
+        return out.permute(0, 2, 3, 4, 1).contiguous()
+
+
+class Uno3D_T40(Uno3D_T20):
+    """Navier-Stokes 3-D U-NO mapping 10 input steps to 40 output steps - own counterpart of the reference's `Uno3D_T40`
+    (navier_stokes_uno3d.py:22-237): the T20 network with a narrower lift (width // 2), a deeper bottom level (conv3 at an eighth of
+    the grid), a time axis stretched 1.6 / 2.4 / 3.2 / 4 times and a `4 * padding` crop.  Input (B, S, S, T, 1) -> output
+    (B, S, S, 4T, 1).  Its last two layers resample grids outside the pruned-DFT kernels' range ((32,32,31) -> (48,48,41) ->
+    (64,64,52) at S = 64, pad 3): on product blocks the model opts its point-wise layers into the any-grid kernels."""
+
+    def __init__(self, in_width, width, pad=2, factor=1, pad_both=False, block_cls=OperatorBlock_3D):
+        nn.Module.__init__(self)
+        self.in_width, self.width, self.pad, self.pad_both = in_width, width, pad, pad_both
+        w, f = width, factor
+        self.fc = nn.Linear(in_width, w // 2)
+        self.fc0 = nn.Linear(w // 2, w)
+        self.conv0 = block_cls(w, 2 * f * w, 48, 48, 10, 20, 20, 4, Normalize=True)
+        self.conv1 = block_cls(2 * f * w, 4 * f * w, 32, 32, 10, 14, 14, 4)
+        self.conv2 = block_cls(4 * f * w, 8 * f * w, 16, 16, 16, 6, 6, 4)
+        self.conv3 = block_cls(8 * f * w, 16 * f * w, 16, 16, 16, 6, 6, 7, Normalize=True)
+        self.conv6 = block_cls(16 * f * w, 4 * f * w, 32, 32, 24, 6, 6, 7)
+        self.conv7 = block_cls(8 * f * w, 2 * f * w, 48, 48, 32, 14, 14, 10, Normalize=True)
+        self.conv8 = block_cls(4 * f * w, 2 * w, 64, 64, 40, 20, 20, 14)
+        self.fc1 = nn.Linear(3 * w, 4 * w)
+        self.fc2 = nn.Linear(4 * w, 1)
+        self._grid_cache = {}
+        if issubclass(block_cls, OperatorBlock_3D):
+            enable_native_resample3d_any(self)
+
+    def forward(self, x):
+        x = torch.cat((x, self.get_grid(x.shape, x.device)), dim=-1).permute(0, 4, 1, 2, 3).contiguous()
+        lifted = F.gelu(gelu_channel_mix(channel_mix(x, self.fc.weight, self.fc.bias), self.fc0.weight, self.fc0.bias))
+        self.padding = int(self.pad * 0.1 * lifted.shape[-1])
+        lifted = F.pad(lifted, [self.padding, self.padding, 0, 0, 0, 0] if self.pad_both else [0, self.padding, 0, 0, 0, 0])
+        d1, d2, d3 = lifted.shape[-3:]
+        c0 = self.conv0(lifted, int(3 * d1 / 4), int(3 * d2 / 4), d3)
+        c1 = self.conv1(c0, d1 // 2, d2 // 2, d3)
+        c2 = self.conv2(c1, d1 // 4, d2 // 4, int(d3 * 1.6))
+        c3 = self.conv3(c2, d1 // 8, d2 // 8, int(d3 * 1.6))
+        c6 = self.conv6(c3, d1 // 2, d2 // 2, int(d3 * 2.4))
+        c6 = torch.cat([c6, self._resize(c1, c6)], dim=1)
+        c7 = self.conv7(c6, int(3 * d1 / 4), int(3 * d2 / 4), int(3.2 * d3))
+        c7 = torch.cat([c7, self._resize(c0, c7)], dim=1)
+        c8 = self.conv8(c7, d1, d2, 4 * d3)
+        c8 = torch.cat([c8, self._resize(lifted, c8)], dim=1)
+        if self.padding != 0:
+            c8 = c8[..., 4 * self.padding:-4 * self.padding] if self.pad_both else c8[..., :-4 * self.padding]
         out = gelu_project(channel_mix(c8.contiguous(), self.fc1.weight, self.fc1.bias), self.fc2.weight, self.fc2.bias)
         return out.permute(0, 2, 3, 4, 1).contiguous()

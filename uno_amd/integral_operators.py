@@ -32,10 +32,11 @@ from .block2d import _OperatorBlock2dCatFn, _OperatorBlock2dFn, _SpectralConv2dF
 from .pointwise import (GradJoin, _dev_act, channel_mix, channel_mix_cat, channel_mix_cat_project, gelu_channel_mix, gelu_channel_mix_pad,
                         gelu_pad2d, gelu_project, instance_norm_gelu, lift_gelu_pad)
 from .resample import resample2d_bicubic_aa
-from .spectral3d import _FftResample3dFn, _OperatorBlock3dFn, _resample3d_plan, spectral_conv3d
+from .spectral3d import (_FftResample3dAnyFn, _FftResample3dFn, _OperatorBlock3dFn, _resample3d_plan, _resample3d_plan_any, resample3d_any_applies,
+                         spectral_conv3d)
 
 __all__ = [
-    "enable_mixed_precision", "GradJoin", "channel_mix_cat_project", "release_pass_state",
+    "enable_mixed_precision", "enable_native_resample3d_any", "GradJoin", "channel_mix_cat_project", "release_pass_state",
     "SpectralConv1d_Uno", "pointwise_op_1D", "OperatorBlock_1D",
     "SpectralConv2d_Uno", "pointwise_op_2D", "OperatorBlock_2D",
     "SpectralConv3d_Uno", "pointwise_op_3D", "OperatorBlock_3D",
@@ -246,6 +247,20 @@ class SpectralConv3d_Uno(nn.Module):
 # pointwise_op_3D on a grid its pruned-DFT resampling kernels do not take (_resample3d_plan is None): False (default) - raise, naming the
 # limits; True - run the reference's op sequence on torch.fft (rocFFT on the device: a stock-library dispatch the caller asked for)
 STOCK_FFT_RESAMPLE3D = False
+# ... and on such a grid with every axis length in 2 ... 128 (resample3d_any_applies): True - run the any-grid HIP kernels
+# (uno_fft_resample3d_any: plain-FMA pruned transforms without the row-count / plane-size limits).  Opt-in: the default (False) leaves
+# every module as it was; a single module opts in through its `native_any_grid` attribute (enable_native_resample3d_any).  A zero-edit
+# user of the reference's navier_stokes_uno3d.py sets this switch once: Uno3D_T40's last two layers are outside the pruned-DFT range.
+NATIVE_RESAMPLE3D_ANY = False
+
+
+def enable_native_resample3d_any(module: nn.Module, enabled: bool = True) -> nn.Module:
+    """Let every pointwise_op_3D under `module` run grids outside the pruned-DFT kernels' range on the any-grid HIP kernels
+    (sets `native_any_grid`); grids inside the range keep their kernels."""
+    for m in module.modules():
+        if isinstance(m, pointwise_op_3D):
+            m.native_any_grid = bool(enabled)
+    return module
 
 
 class pointwise_op_3D(nn.Module):
@@ -254,7 +269,8 @@ class pointwise_op_3D(nn.Module):
     trims/zero-pads at the END of each axis, identity trilinear resize) - reference
     integral_operators.py:430-468.  The convolution runs on the channel-mix kernels (K8 / K9) for float32 device
     tensors - MIOpen executes a 1x1x1 Conv3d with its naive direct kernels, 0.9 s of a 2.2 s first NS-3D step - the
-    FFT resampling runs on the pruned-DFT kernels (_FftResample3dFn; outside their shape range the layer raises unless STOCK_FFT_RESAMPLE3D allows torch.fft); the trilinear resize to the size the tensor already has is an exact
+    FFT resampling runs on the pruned-DFT kernels (_FftResample3dFn; outside their shape range the layer runs the any-grid kernels where
+    `native_any_grid` / NATIVE_RESAMPLE3D_ANY opts in, else raises unless STOCK_FFT_RESAMPLE3D allows torch.fft); the trilinear resize to the size the tensor already has is an exact
     identity under align_corners=True and is skipped on the device."""
 
     def __init__(self, in_codim, out_codim, dim1, dim2, dim3):
@@ -283,13 +299,16 @@ class pointwise_op_3D(nn.Module):
             plan = _resample3d_plan(out.shape[-3:], (dim1, dim2, dim3), out.device)
             if plan is not None:
                 return _FftResample3dFn.apply(out, (dim1, dim2, dim3), plan)
+            if (getattr(self, "native_any_grid", False) or NATIVE_RESAMPLE3D_ANY) and resample3d_any_applies(out.shape[-3:], (dim1, dim2, dim3)):
+                return _FftResample3dAnyFn.apply(out, (dim1, dim2, dim3), _resample3d_plan_any(out.shape[-3:], (dim1, dim2, dim3), out.device))
         if on_device and not STOCK_FFT_RESAMPLE3D:
             # no silent dispatch to a stock library from a product component: the pruned-DFT resampling kernels do not cover this grid
             raise RuntimeError(
                 f"pointwise_op_3D: the FFT crop / resample {tuple(out.shape[-3:])} -> {(dim1, dim2, dim3)} is outside the range of the "
                 "pruned-DFT kernels (they take an even number of kept rows per complex axis - at most 80 / 48 - and (W, T) planes of at most "
                 "1792 elements with T <= 64); set uno_amd.integral_operators.STOCK_FFT_RESAMPLE3D = True to run this layer's resampling "
-                "through torch.fft (rocFFT) instead")
+                "through torch.fft (rocFFT) instead, or - for axis lengths of 2 ... 128 - uno_amd.integral_operators.NATIVE_RESAMPLE3D_ANY = True "
+                "(enable_native_resample3d_any(model) for one model) to run it on the any-grid HIP kernels")
         spec = torch.fft.rfftn(out, dim=[-3, -2, -1])
         h1, h2, h3 = dim1 // 2, dim2 // 2, dim3 // 2
         if on_device:

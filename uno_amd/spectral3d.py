@@ -96,6 +96,57 @@ class _FftResample3dFn(torch.autograd.Function):
         return _native.fft_resample3d(_plain(gy), ctx.din, (t1, t1), (t2, t2), m3, scale, adjoint=True), None, None
 
 
+RESAMPLE3D_ANY_MAX_AXIS = 128       # the any-grid kernels keep whole (W, T) planes in LDS: every axis length in 2 ... 128
+
+
+def _any_modes3(din, dout):
+    return min(dout[2] // 2, din[2] // 2 + 1)
+
+
+def resample3d_any_applies(din, dout) -> bool:
+    """True when the any-grid kernels (uno_fft_resample3d_any) take the FFT crop / resample din -> dout: every axis length in 2 ... 128
+    (then every kept-row count is in 1 ... 128 and 1 <= modes3 <= n/2 + 1).  A host predicate: no device, no library call."""
+    din, dout = tuple(int(v) for v in din), tuple(int(v) for v in dout)
+    if len(din) != 3 or len(dout) != 3 or not all(2 <= v <= RESAMPLE3D_ANY_MAX_AXIS for v in (*din, *dout)):
+        return False
+    k1, k2 = _kept_indices(din[0], dout[0]), _kept_indices(din[1], dout[1])
+    return len(k1) >= 1 and len(k2) >= 1 and 1 <= _any_modes3(din, dout) <= din[2] // 2 + 1
+
+
+_RESAMPLE3D_ANY_TABLES = {}
+
+
+def _resample3d_plan_any(din, dout, device):
+    """(f1, f2, m3) for _native.fft_resample3d_any, or None when resample3d_any_applies says no; tables cached per (grids, device)."""
+    key = (tuple(din), tuple(dout), str(device))
+    if key not in _RESAMPLE3D_ANY_TABLES:
+        plan = None
+        if resample3d_any_applies(din, dout):
+            t1 = _native.table_to_device(torch.tensor(_kept_indices(din[0], dout[0]), dtype=torch.int32), device)
+            t2 = _native.table_to_device(torch.tensor(_kept_indices(din[1], dout[1]), dtype=torch.int32), device)
+            plan = (t1, t2, _any_modes3(din, dout))
+        _RESAMPLE3D_ANY_TABLES[key] = plan
+    return _RESAMPLE3D_ANY_TABLES[key]
+
+
+class _FftResample3dAnyFn(torch.autograd.Function):
+    """_FftResample3dFn on the any-grid kernels (K1a, K5a, K3a: any kept-row counts, axes of 2 ... 128); backward is the adjoint call."""
+
+    @staticmethod
+    def forward(ctx, x, size, plan):
+        t1, t2, m3 = plan
+        ctx.plan, ctx.din, ctx.dout = plan, tuple(x.shape[-3:]), tuple(size)
+        scale = 1.0 / (size[0] * size[1] * size[2])
+        return _native.fft_resample3d_any(_plain(x), size, (t1, t1), (t2, t2), m3, scale, adjoint=False)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        t1, t2, m3 = ctx.plan
+        scale = 1.0 / (ctx.dout[0] * ctx.dout[1] * ctx.dout[2])
+        return _native.fft_resample3d_any(_plain(gy), ctx.din, (t1, t1), (t2, t2), m3, scale, adjoint=True), None, None
+
+
 class _OperatorBlock3dFn(torch.autograd.Function):
     """s = SpectralConv3d_Uno(x) + pointwise_op_3D(x) in ONE buffer (reference integral_operators.py:506-512: `x1_out = self.conv(...);
     x2_out = self.w(...); x_out = x1_out + x2_out`, then F.gelu for blocks without normalisation).
