@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define UNO_SPECTRAL_ABI_VERSION 13
+#define UNO_SPECTRAL_ABI_VERSION 14
 
 /* ABI version of the loaded library (== UNO_SPECTRAL_ABI_VERSION it was built with). */
 int uno_abi_version(void);
@@ -99,12 +99,22 @@ int uno_fft_resample3d_acc(const float* x, float* y, float* y_act, void* ws, int
  * 1 <= m3 <= D3/2 + 1 (and <= M3/2 + 1), every axis length of x and y in 2 ... 128 - planes of up to 128 x 128 elements.  Outside that
  * range the call returns an error that names the limits; table entries are reduced modulo the axis length.  This is what the last two
  * layers of the reference's Uno3D_T40 need (navier_stokes_uno3d.py:145-159: (32,32,31) -> (48,48,41) -> (64,64,52) at S = 64, pad 3).
- * Plain f32 FMA kernels, f32 accumulation, results independent of the launch geometry; no accumulate / GELU form.
+ * Plain f32 FMA kernels, f32 accumulation, results independent of the launch geometry.
  *   ws: uno_fft_resample3d_any_ws_bytes = 8 n_vol (D1 + M1) J2 m3 bytes. */
 long long uno_fft_resample3d_any_ws_bytes(int n_vol, int D1, int M1, int J1, int J2, int m3);
 int uno_fft_resample3d_any(const float* x, float* y, void* ws, int n_vol, int D1, int D2, int D3, int M1, int M2, int M3,
                            int J1, const int* f1_in, const int* f1_out, int J2, const int* f2_in, const int* f2_out, int m3,
                            float scale, int herm_in, int herm_out, void* stream);
+
+/* ABI 14.  uno_fft_resample3d_any ACCUMULATING into y (y += resampled x) and, with y_act != NULL, writing y_act = gelu(y) in the same
+ * pass: what uno_fft_resample3d_acc is to uno_fft_resample3d, for the point-wise branch of an OperatorBlock_3D (reference
+ * integral_operators.py:506-512: x1_out + x2_out, then F.gelu) on a grid outside the pruned-DFT range.  Same validation, limits and
+ * workspace (uno_fft_resample3d_any_ws_bytes) as uno_fft_resample3d_any; the transform's summation order is that of the plain call, so
+ * y holds exactly (old y) + (the plain call's result) in one float32 addition.  y_act == NULL: accumulate only.  y_act == y, x == y and
+ * x == y_act are refused (negative code, the message names the argument). */
+int uno_fft_resample3d_any_acc(const float* x, float* y, float* y_act, void* ws, int n_vol, int D1, int D2, int D3, int M1, int M2, int M3,
+                               int J1, const int* f1_in, const int* f1_out, int J2, const int* f2_in, const int* f2_out, int m3,
+                               float scale, int herm_in, int herm_out, void* stream);
 
 /* SpectralConv3d_Uno.forward - reference integral_operators.py:385-427
  *   x (B, Ci, H, W, T) f32;  w[0..3] = weights1..4 (Ci, Co, m1, m2, m3) c64 in the reference's corner

@@ -14,7 +14,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libuno_spectral.so")
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 _lib = None
 _lock = threading.Lock()
@@ -37,6 +37,7 @@ _SIGNATURES = {
     "uno_fft_resample3d_acc": (C.c_int, [_fp] * 4 + [_i] * 8 + [_fp, _fp, _i, _fp, _fp, _i, C.c_float, _i, _i, _fp]),
     "uno_fft_resample3d_any_ws_bytes": (C.c_longlong, [_i] * 6),
     "uno_fft_resample3d_any": (C.c_int, [_fp] * 3 + [_i] * 8 + [_fp, _fp, _i, _fp, _fp, _i, C.c_float, _i, _i, _fp]),
+    "uno_fft_resample3d_any_acc": (C.c_int, [_fp] * 4 + [_i] * 8 + [_fp, _fp, _i, _fp, _fp, _i, C.c_float, _i, _i, _fp]),
     "uno_dft2d_forward": (C.c_int, [_fp, _fp] + [_i] * 5 + [C.c_float, _i, _i, _fp]),
     "uno_dft2d_forward_bf16": (C.c_int, [_fp, _fp] + [_i] * 5 + [C.c_float, _i, _i, _fp]),
     "uno_dft2d_inverse_bf16": (C.c_int, [_fp, _fp] + [_i] * 5 + [C.c_float, _i, _i, _fp]),
@@ -342,9 +343,10 @@ def fft_resample3d(x, out_size, f1, f2, m3: int, scale: float, adjoint: bool, ou
     return y
 
 
-def fft_resample3d_any(x, out_size, f1, f2, m3: int, scale: float, adjoint: bool):
-    """fft_resample3d on the any-grid kernels (uno_fft_resample3d_any): any number of kept rows, any 1 <= m3 <= n/2 + 1, axis lengths
-    2 ... 128.  Same tables and the same adjoint convention; no accumulate / activation form."""
+def fft_resample3d_any(x, out_size, f1, f2, m3: int, scale: float, adjoint: bool, out=None, act=False):
+    """fft_resample3d on the any-grid kernels (uno_fft_resample3d_any / _acc): any number of kept rows, any 1 <= m3 <= n/2 + 1, axis
+    lengths 2 ... 128.  Same tables, the same adjoint convention and the same `out` / `act`: ACCUMULATE into `out` (returned); act: also
+    return gelu(out) written in the same pass -> (out, act)."""
     _require(x, torch.float32, "x")
     *lead, D1, D2, D3 = x.shape
     M1, M2, M3 = (int(v) for v in out_size)
@@ -358,6 +360,16 @@ def fft_resample3d_any(x, out_size, f1, f2, m3: int, scale: float, adjoint: bool
     L = lib()
     with torch.cuda.device(x.device):
         ws = torch.empty(max(1, L.uno_fft_resample3d_any_ws_bytes(n, D1, M1, J1, J2, int(m3))), dtype=torch.uint8, device=x.device)
+        if out is not None:
+            _require(out, torch.float32, "out")
+            if tuple(out.shape) != (*lead, M1, M2, M3) or not out.is_contiguous():
+                raise RuntimeError(f"uno_amd: out must be a contiguous {(*lead, M1, M2, M3)} tensor")
+            ya = torch.empty_like(out) if act else None
+            rc = L.uno_fft_resample3d_any_acc(_ptr(x), _ptr(out), _opt(ya), _ptr(ws), n, D1, D2, D3, M1, M2, M3,
+                                              J1, _ptr(f1[0]), _ptr(f1[1]), J2, _ptr(f2[0]), _ptr(f2[1]), int(m3), float(scale),
+                                              int(adjoint), int(not adjoint), _stream(x))
+            _check(rc, "uno_fft_resample3d_any_acc")
+            return (out, ya) if act else out
         y = torch.empty((*lead, M1, M2, M3), dtype=torch.float32, device=x.device)
         rc = L.uno_fft_resample3d_any(_ptr(x), _ptr(y), _ptr(ws), n, D1, D2, D3, M1, M2, M3, J1, _ptr(f1[0]), _ptr(f1[1]), J2,
                                       _ptr(f2[0]), _ptr(f2[1]), int(m3), float(scale), int(adjoint), int(not adjoint), _stream(x))

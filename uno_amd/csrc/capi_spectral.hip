@@ -398,10 +398,9 @@ long long uno_fft_resample3d_any_ws_bytes(int n_vol, int D1, int M1, int J1, int
     return 8LL * n_vol * ((long long)D1 + M1) * J2 * m3;
 }
 
-int uno_fft_resample3d_any(const float* x, float* y, void* ws, int n_vol, int D1, int D2, int D3, int M1, int M2, int M3,
-                           int J1, const int* f1_in, const int* f1_out, int J2, const int* f2_in, const int* f2_out, int m3,
-                           float scale, int herm_in, int herm_out, void* stream) {
-    const char* who = "uno_fft_resample3d_any";
+static int fft_resample3d_any_impl(const char* who, const float* x, float* y, float* y_act, int accumulate, void* ws, int n_vol, int D1,
+                                   int D2, int D3, int M1, int M2, int M3, int J1, const int* f1_in, const int* f1_out, int J2,
+                                   const int* f2_in, const int* f2_out, int m3, float scale, int herm_in, int herm_out, void* stream) {
     const int dims[6] = {D1, D2, D3, M1, M2, M3};
     for (int d : dims)
         if (d < 2 || d > 128) {
@@ -414,10 +413,29 @@ int uno_fft_resample3d_any(const float* x, float* y, void* ws, int n_vol, int D1
         return -1;
     }
     if (n_vol < 0 || (long long)n_vol * 128 > 0x7fffffffLL) { set_error("%s: bad volume count %d (0 ... 2^24 - 1)", who, n_vol); return -1; }
+    if (accumulate) {       // the kernels read x while they write y, and read y back before they write y_act
+        if (y_act && y_act == y) { set_error("%s: y_act must not alias y", who); return -1; }
+        if (x && x == y) { set_error("%s: x must not alias y", who); return -1; }
+        if (x && x == y_act) { set_error("%s: x must not alias y_act", who); return -1; }
+    }
     if (n_vol == 0) return 0;
     if (!x || !y || !ws || !f1_in || !f1_out || !f2_in || !f2_out) { set_error("%s: null pointer", who); return -1; }
-    return launch_resample3d_any(x, y, ws, n_vol, D1, D2, D3, M1, M2, M3, J1, f1_in, f1_out, J2, f2_in, f2_out, m3, scale, herm_in, herm_out,
-                                 (hipStream_t)stream);
+    return launch_resample3d_any(x, y, y_act, accumulate, ws, n_vol, D1, D2, D3, M1, M2, M3, J1, f1_in, f1_out, J2, f2_in, f2_out, m3, scale,
+                                 herm_in, herm_out, (hipStream_t)stream);
+}
+
+int uno_fft_resample3d_any(const float* x, float* y, void* ws, int n_vol, int D1, int D2, int D3, int M1, int M2, int M3,
+                           int J1, const int* f1_in, const int* f1_out, int J2, const int* f2_in, const int* f2_out, int m3,
+                           float scale, int herm_in, int herm_out, void* stream) {
+    return fft_resample3d_any_impl("uno_fft_resample3d_any", x, y, nullptr, 0, ws, n_vol, D1, D2, D3, M1, M2, M3, J1, f1_in, f1_out, J2, f2_in,
+                                   f2_out, m3, scale, herm_in, herm_out, stream);
+}
+
+int uno_fft_resample3d_any_acc(const float* x, float* y, float* y_act, void* ws, int n_vol, int D1, int D2, int D3, int M1, int M2, int M3,
+                               int J1, const int* f1_in, const int* f1_out, int J2, const int* f2_in, const int* f2_out, int m3,
+                               float scale, int herm_in, int herm_out, void* stream) {
+    return fft_resample3d_any_impl("uno_fft_resample3d_any_acc", x, y, y_act, 1, ws, n_vol, D1, D2, D3, M1, M2, M3, J1, f1_in, f1_out, J2,
+                                   f2_in, f2_out, m3, scale, herm_in, herm_out, stream);
 }
 
 static int check_modes3d(const char* who, int H, int W, int T, int Ho, int Wo, int To, int m1, int m2, int m3) {

@@ -1,4 +1,4 @@
-// Any-grid form of pointwise_op_3D's FFT crop / resample (K1a / K5a / K3a; C ABI: uno_fft_resample3d_any).
+// Any-grid form of pointwise_op_3D's FFT crop / resample (K1a / K5a / K3a; C ABI: uno_fft_resample3d_any, uno_fft_resample3d_any_acc).
 //
 // uno_fft_resample3d runs on the MFMA plane-batched kernels (dft2d_plane.hip) and the tiled leading-axis kernels (cdft_axis.hip): even
 // kept-row counts (<= 80 / 48), modes3 <= 16, (W, T) planes of <= 1792 elements, T <= 64.  The reference's first 3-D model
@@ -17,6 +17,9 @@
 // Workgroups are persistent (the CU count x what the LDS admits) and load their tables once.  The complex stages give every thread
 // four neighbouring columns (two ds_read_b128 + one twiddle per 16 FMA); the real stages give it four rows a quarter plane apart
 // (odd row pitch: consecutive lanes hit consecutive banks).  Fixed summation order: two runs are bit-identical.
+// K3a also has an accumulate form (y += result) and an accumulate + activation form (y_act = gelu(y) in the same pass): the point-wise
+// branch of a one-buffer OperatorBlock_3D (reference integral_operators.py:506-512) on these grids.  Separate instantiations: the plain
+// form's code is what it was.
 #include "uno_common.h"
 #include <algorithm>
 
@@ -25,6 +28,7 @@ namespace uno {
 struct Resample3dAnyParams {
     const float* x;             // (n_vol, D1, D2, D3) f32
     float* y;                   // (n_vol, M1, M2, M3) f32
+    float* y_act;               // accumulate form only: (n_vol, M1, M2, M3) f32 = gelu(y) after the accumulation, or nullptr
     float2* Z1;                 // (n_vol, D1, J2, m3) c64
     float2* Z2;                 // (n_vol, M1, J2, m3) c64
     const float2 *tw1i, *tw2i, *tw3i, *tw1o, *tw2o, *tw3o;     // (cos, sin)(2 pi n / N) of D1, D2, D3, M1, M2, M3
@@ -32,6 +36,7 @@ struct Resample3dAnyParams {
     int n_vol, D1, D2, D3, M1, M2, M3, J1, J2, m3;
     float scale;
     int herm_in, herm_out;
+    int accumulate;             // K3a: y += result instead of y = result
 };
 
 constexpr int RA_THREADS = 256;
@@ -189,6 +194,8 @@ __host__ __device__ __forceinline__ size_t ra_inv_lds(int M2, int M3, int J2, in
     return (size_t)(J2 + M2) * ra_up4(m3) * 8 + (size_t)(M2 + M3) * 8 + (size_t)J2 * 4;
 }
 
+// EPI 0: y = result; 1: y += result; 2: y += result and y_act = gelu(y)
+template <int EPI>
 __global__ __launch_bounds__(RA_THREADS) void resample3d_any_inv_plane_kernel(Resample3dAnyParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int M2 = p.M2, M3 = p.M3, J2 = p.J2, m3 = p.m3, Lp = ra_up4(m3);
@@ -226,6 +233,11 @@ __global__ __launch_bounds__(RA_THREADS) void resample3d_any_inv_plane_kernel(Re
             const float2* row[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) row[r] = sU + (size_t)min(wq + r * WQ, M2 - 1) * Lp;
+            float old[4] = {0.f, 0.f, 0.f, 0.f};
+            if (EPI) {          // the old values are asked for here and first used after the FMA loop, which hides their latency
+#pragma unroll
+                for (int r = 0; r < 4; ++r) old[r] = dst[(size_t)min(wq + r * WQ, M2 - 1) * M3 + t];
+            }
             float acc[4] = {0.f, 0.f, 0.f, 0.f};
             int idx = 0;
             for (int l = 0; l < m3; ++l) {
@@ -240,7 +252,14 @@ __global__ __launch_bounds__(RA_THREADS) void resample3d_any_inv_plane_kernel(Re
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int w = wq + r * WQ;
-                if (w < M2) dst[(size_t)w * M3 + t] = acc[r];
+                if (w >= M2) continue;
+                if (EPI == 0) {
+                    dst[(size_t)w * M3 + t] = acc[r];
+                } else {
+                    const float v = old[r] + acc[r];
+                    dst[(size_t)w * M3 + t] = v;
+                    if (EPI == 2) p.y_act[(size_t)plane * M2 * M3 + (size_t)w * M3 + t] = uno_gelu(v);
+                }
             }
         }
     }
@@ -269,11 +288,11 @@ static int ra_check(const char* who) {
     return 0;
 }
 
-int launch_resample3d_any(const float* x, float* y, void* ws, int n_vol, int D1, int D2, int D3, int M1, int M2, int M3, int J1,
+int launch_resample3d_any(const float* x, float* y, float* y_act, int accumulate, void* ws, int n_vol, int D1, int D2, int D3, int M1, int M2, int M3, int J1,
                           const int* f1_in, const int* f1_out, int J2, const int* f2_in, const int* f2_out, int m3, float scale,
                           int herm_in, int herm_out, hipStream_t s) {
     Resample3dAnyParams p;
-    p.x = x; p.y = y;
+    p.x = x; p.y = y; p.y_act = accumulate ? y_act : nullptr; p.accumulate = accumulate ? 1 : 0;
     p.Z1 = static_cast<float2*>(ws);
     p.Z2 = p.Z1 + (size_t)n_vol * D1 * J2 * m3;
     p.f1_in = f1_in; p.f1_out = f1_out; p.f2_in = f2_in; p.f2_out = f2_out;
@@ -283,10 +302,14 @@ int launch_resample3d_any(const float* x, float* y, void* ws, int n_vol, int D1,
     p.tw1o = twiddle_table(M1); p.tw2o = twiddle_table(M2); p.tw3o = twiddle_table(M3);
     if (!p.tw1i || !p.tw2i || !p.tw3i || !p.tw1o || !p.tw2o || !p.tw3o) return -6;
     const size_t lds_f = ra_fwd_lds(D2, D3, J2, m3), lds_a = ra_axis_lds(D1, M1, J1), lds_i = ra_inv_lds(M2, M3, J2, m3);
-    static int slot_f[64], slot_a[64], slot_i[64];
+    static int slot_f[64], slot_a[64], slot_i[3][64];
+    const int epi = !p.accumulate ? 0 : (p.y_act ? 2 : 1);
+    const void* inv_kernel = epi == 0   ? reinterpret_cast<const void*>(resample3d_any_inv_plane_kernel<0>)
+                             : epi == 1 ? reinterpret_cast<const void*>(resample3d_any_inv_plane_kernel<1>)
+                                        : reinterpret_cast<const void*>(resample3d_any_inv_plane_kernel<2>);
     if (!ensure_dynamic_lds(reinterpret_cast<const void*>(resample3d_any_fwd_plane_kernel), lds_f, slot_f) ||
         !ensure_dynamic_lds(reinterpret_cast<const void*>(resample3d_any_axis_kernel), lds_a, slot_a) ||
-        !ensure_dynamic_lds(reinterpret_cast<const void*>(resample3d_any_inv_plane_kernel), lds_i, slot_i)) {
+        !ensure_dynamic_lds(inv_kernel, lds_i, slot_i[epi])) {
         set_error("uno_fft_resample3d_any: cannot raise the dynamic LDS limit (%zu / %zu / %zu bytes)", lds_f, lds_a, lds_i);
         return -3;
     }
@@ -302,11 +325,17 @@ int launch_resample3d_any(const float* x, float* y, void* ws, int n_vol, int D1,
         hipLaunchKernelGGL(resample3d_any_axis_kernel, dim3(ra_grid(n_vol * tiles, lds_a)), dim3(RA_THREADS), lds_a, s, p);
     }
     if (int rc = ra_check("resample3d_any_axis")) return rc;
-    {
-        ProfScope prof("uno::resample3d_any_inv_plane_kernel", 4.0 * n_vol * (double)M1 * M2 * M3 + spec * M1, s);
-        hipLaunchKernelGGL(resample3d_any_inv_plane_kernel, dim3(ra_grid((long long)n_vol * M1, lds_i)), dim3(RA_THREADS), lds_i, s, p);
+    const double out_bytes = 4.0 * n_vol * (double)M1 * M2 * M3;
+    const dim3 grid_i(ra_grid((long long)n_vol * M1, lds_i));
+    if (epi == 0) {
+        ProfScope prof("uno::resample3d_any_inv_plane_kernel", out_bytes + spec * M1, s);
+        hipLaunchKernelGGL(resample3d_any_inv_plane_kernel<0>, grid_i, dim3(RA_THREADS), lds_i, s, p);
+    } else {        // + the read of the old y and, with the activation, the second store
+        ProfScope prof("uno::resample3d_any_inv_plane_acc_kernel", out_bytes * (epi == 2 ? 3.0 : 2.0) + spec * M1, s);
+        if (epi == 1) hipLaunchKernelGGL(resample3d_any_inv_plane_kernel<1>, grid_i, dim3(RA_THREADS), lds_i, s, p);
+        else hipLaunchKernelGGL(resample3d_any_inv_plane_kernel<2>, grid_i, dim3(RA_THREADS), lds_i, s, p);
     }
-    return ra_check("resample3d_any_inv_plane");
+    return ra_check(epi ? "resample3d_any_inv_plane_acc" : "resample3d_any_inv_plane");
 }
 
 }  // namespace uno

@@ -311,8 +311,9 @@ int launch_mode_gemm_pair(const ModeGemmParams& input_grad, const ModeGemmParams
 int launch_cdft(const CdftParams& p, bool inverse, hipStream_t s);
 int launch_dft2d_generic(const Dft2dParams& p, bool inverse, void* ws, size_t ws_bytes, hipStream_t s);      // dft_generic.hip: any mode count; ws: 8 n_img H m2 bytes
 int launch_cdft_generic(const CdftParams& p, bool inverse, hipStream_t s);
-// resample3d_any.hip: the FFT crop / resample of pointwise_op_3D for any row counts and axis lengths 2 ... 128 (arguments validated by the caller)
-int launch_resample3d_any(const float* x, float* y, void* ws, int n_vol, int D1, int D2, int D3, int M1, int M2, int M3, int J1,
+// resample3d_any.hip: the FFT crop / resample of pointwise_op_3D for any row counts and axis lengths 2 ... 128 (arguments validated by the caller);
+// accumulate != 0: y += result and, with y_act != nullptr, y_act = gelu(y)
+int launch_resample3d_any(const float* x, float* y, float* y_act, int accumulate, void* ws, int n_vol, int D1, int D2, int D3, int M1, int M2, int M3, int J1,
                           const int* f1_in, const int* f1_out, int J2, const int* f2_in, const int* f2_out, int m3, float scale,
                           int herm_in, int herm_out, hipStream_t s);
 int launch_resample2d(const void* in, void* out, float* tmp, int n_img, int H, int W, int Ho, int Wo, const int* startH,

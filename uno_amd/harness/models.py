@@ -16,7 +16,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..integral_operators import (GradJoin, OperatorBlock_2D, OperatorBlock_3D, channel_mix, channel_mix_cat, channel_mix_cat_project,
-                                  enable_native_resample3d_any, gelu_channel_mix, gelu_channel_mix_pad, gelu_pad2d, gelu_project, lift_gelu_pad)
+                                  enable_native_resample3d_any, enable_one_buffer_any_grid, gelu_channel_mix, gelu_channel_mix_pad, gelu_pad2d, gelu_project, lift_gelu_pad)
 
 
 class UNO_9(nn.Module):
@@ -245,9 +245,10 @@ class Uno3D_T40(Uno3D_T20):
     (navier_stokes_uno3d.py:22-237): the T20 network with a narrower lift (width // 2), a deeper bottom level (conv3 at an eighth of
     the grid), a time axis stretched 1.6 / 2.4 / 3.2 / 4 times and a `4 * padding` crop.  Input (B, S, S, T, 1) -> output
     (B, S, S, 4T, 1).  Its last two layers resample grids outside the pruned-DFT kernels' range ((32,32,31) -> (48,48,41) ->
-    (64,64,52) at S = 64, pad 3): on product blocks the model opts its point-wise layers into the any-grid kernels."""
+    (64,64,52) at S = 64, pad 3): on product blocks the model opts its point-wise layers into the any-grid kernels, and with
+    `one_buffer_any=True` its blocks into the one-buffer form on those grids (enable_one_buffer_any_grid)."""
 
-    def __init__(self, in_width, width, pad=2, factor=1, pad_both=False, block_cls=OperatorBlock_3D):
+    def __init__(self, in_width, width, pad=2, factor=1, pad_both=False, block_cls=OperatorBlock_3D, one_buffer_any=False):
         nn.Module.__init__(self)
         self.in_width, self.width, self.pad, self.pad_both = in_width, width, pad, pad_both
         w, f = width, factor
@@ -265,6 +266,8 @@ class Uno3D_T40(Uno3D_T20):
         self._grid_cache = {}
         if issubclass(block_cls, OperatorBlock_3D):
             enable_native_resample3d_any(self)
+            if one_buffer_any:
+                enable_one_buffer_any_grid(self)
 
     def forward(self, x):
         x = torch.cat((x, self.get_grid(x.shape, x.device)), dim=-1).permute(0, 4, 1, 2, 3).contiguous()

@@ -36,7 +36,7 @@ from .spectral3d import (_FftResample3dAnyFn, _FftResample3dFn, _OperatorBlock3d
                          spectral_conv3d)
 
 __all__ = [
-    "enable_mixed_precision", "enable_native_resample3d_any", "GradJoin", "channel_mix_cat_project", "release_pass_state",
+    "enable_mixed_precision", "enable_native_resample3d_any", "enable_one_buffer_any_grid", "GradJoin", "channel_mix_cat_project", "release_pass_state",
     "SpectralConv1d_Uno", "pointwise_op_1D", "OperatorBlock_1D",
     "SpectralConv2d_Uno", "pointwise_op_2D", "OperatorBlock_2D",
     "SpectralConv3d_Uno", "pointwise_op_3D", "OperatorBlock_3D",
@@ -327,6 +327,22 @@ class pointwise_op_3D(nn.Module):
 
 
 ONE_BUFFER_3D = True        # OperatorBlock_3D in one buffer (_OperatorBlock3dFn); False: the two branches and stock sum / GELU (A/B switch)
+# ... and on a grid outside the pruned-DFT range whose point-wise layer runs the any-grid kernels: True - the same one-buffer form with
+# uno_fft_resample3d_any_acc as its last transform.  Opt-in like NATIVE_RESAMPLE3D_ANY: the default (False) leaves every block on the two
+# branches there; a single block opts in through its `one_buffer_any_grid` attribute (enable_one_buffer_any_grid).
+ONE_BUFFER_3D_ANY = False
+
+
+def enable_one_buffer_any_grid(module: nn.Module, enabled: bool = True) -> nn.Module:
+    """Let every OperatorBlock_3D under `module` take the one-buffer form on grids outside the pruned-DFT kernels' range (sets
+    `one_buffer_any_grid`; enabling also sets `native_any_grid` on the block's point-wise layer, which the form runs on).  Disabling
+    clears the block attribute only.  Grids inside the range keep their kernels."""
+    for m in module.modules():
+        if isinstance(m, OperatorBlock_3D):
+            m.one_buffer_any_grid = bool(enabled)
+            if enabled:
+                m.w.native_any_grid = True
+    return module
 
 
 class OperatorBlock_3D(nn.Module):
@@ -357,7 +373,9 @@ class OperatorBlock_3D(nn.Module):
 
     def _fused(self, x, dim1, dim2, dim3):
         """(conv(x) + w(x) [activated], whether the GELU has been applied) through the one-buffer form, or None when the layer has to take
-        the two branches separately (CPU tensors, other dtypes, grids outside the pruned-DFT resampling kernels' range, mismatched grids)."""
+        the two branches separately (CPU tensors, other dtypes, mismatched grids, grids outside the pruned-DFT resampling kernels' range
+        unless the block is opted into the one-buffer form on the any-grid kernels - `one_buffer_any_grid` / ONE_BUFFER_3D_ANY with the
+        point-wise layer's `native_any_grid` / NATIVE_RESAMPLE3D_ANY - and resample3d_any_applies holds)."""
         conv, w = self.conv, self.w
         if not (ONE_BUFFER_3D and x.is_cuda and x.dtype == torch.float32 and x.dim() == 5 and x.shape[1] == conv.in_channels
                 and w.conv.weight.dtype == torch.float32):
@@ -368,14 +386,19 @@ class OperatorBlock_3D(nn.Module):
             dims = (int(w.dim1), int(w.dim2), int(w.dim3))
             if (conv.dim1, conv.dim2, conv.dim3) != dims:
                 return None
-        plan = _resample3d_plan(tuple(x.shape[-3:]), dims, x.device)
-        if plan is None:
-            return None
+        din = tuple(x.shape[-3:])
+        plan = _resample3d_plan(din, dims, x.device)
+        any_grid = plan is None
+        if any_grid:
+            if not ((getattr(self, "one_buffer_any_grid", False) or ONE_BUFFER_3D_ANY)
+                    and (getattr(w, "native_any_grid", False) or NATIVE_RESAMPLE3D_ANY) and resample3d_any_applies(din, dims)):
+                return None
+            plan = _resample3d_plan_any(din, dims, x.device)
         if dim1 is not None:
             conv.dim1, conv.dim2, conv.dim3 = dim1, dim2, dim3
         gelu = self.non_lin and not self.normalize
         out = _OperatorBlock3dFn.apply(x, conv.weights1, conv.weights2, conv.weights3, conv.weights4, w.conv.weight, w.conv.bias,
-                                       dims, plan, gelu)
+                                       dims, plan, gelu, any_grid)
         return out, gelu
 
 

@@ -1,8 +1,8 @@
 """3-D spectral convolution on the HIP path (SpectralConv3d_Uno.forward, reference
 integral_operators.py:385-427): rfftn over (H, W, T) restricted to the four low-frequency corners ->
 per-mode channel mixing with weights1..4 -> zero-padded irfftn, with a custom autograd adjoint that
-saves only the truncated input spectrum.  Also pointwise_op_3D's FFT resampling on the pruned-DFT kernels
-(plan + Function) and the 3-D operator block in one buffer."""
+saves only the truncated input spectrum.  Also pointwise_op_3D's FFT resampling on the pruned-DFT and the any-grid kernels
+(plans + Functions) and the 3-D operator block in one buffer."""
 from __future__ import annotations
 
 import torch
@@ -60,7 +60,7 @@ _RESAMPLE3D_TABLES = {}
 
 def _resample3d_plan(din, dout, device):
     """(f1, f2, m3) for _native.fft_resample3d, or None when the shape is outside the kernels' range (odd row counts, too many
-    rows or bins, planes too large): the caller then takes the stock FFT path."""
+    rows or bins, planes too large): the caller then takes the any-grid kernels (_resample3d_plan_any) where it is opted in."""
     key = (tuple(din), tuple(dout), str(device))
     if key not in _RESAMPLE3D_TABLES:
         plan = None
@@ -153,13 +153,15 @@ class _OperatorBlock3dFn(torch.autograd.Function):
 
     The spectral branch's inverse transform writes s; the point-wise branch - 1x1x1 convolution (K8), then the reference's FFT crop /
     resample on the pruned-DFT kernels - ends in a plane-batched inverse transform that ACCUMULATES into s and, for a block whose sum is
-    followed directly by the GELU, writes the activation in the same pass (uno_fft_resample3d_acc).  Backward: the spectral branch
+    followed directly by the GELU, writes the activation in the same pass (uno_fft_resample3d_acc; with `any_grid`, a plan of
+    _resample3d_plan_any: the any-grid kernels and uno_fft_resample3d_any_acc).  Backward: the spectral branch
     writes grad_x, the transposed 1x1x1 convolution accumulates into it.  The element-wise sum (three passes over the output), the
     GELU (two) and autograd's sum of the two input gradients (three over the input) are gone."""
 
     @staticmethod
-    def forward(ctx, x, w1, w2, w3, w4, cw, cb, dims, plan, fuse_gelu):
+    def forward(ctx, x, w1, w2, w3, w4, cw, cb, dims, plan, fuse_gelu, any_grid):
         ctx.leaves = (cw, cb)
+        resample = _native.fft_resample3d_any if any_grid else _native.fft_resample3d
         x = _plain(x)
         ws = [_plain(w) for w in (w1, w2, w3, w4)]
         B, Ci = x.shape[0], x.shape[1]
@@ -172,18 +174,18 @@ class _OperatorBlock3dFn(torch.autograd.Function):
         t1, t2, m3 = plan
         scale = 1.0 / (dims[0] * dims[1] * dims[2])
         if fuse_gelu:
-            s, out = _native.fft_resample3d(t, dims, (t1, t1), (t2, t2), m3, scale, adjoint=False, out=s, act=True)
+            s, out = resample(t, dims, (t1, t1), (t2, t2), m3, scale, adjoint=False, out=s, act=True)
         else:
-            out = _native.fft_resample3d(t, dims, (t1, t1), (t2, t2), m3, scale, adjoint=False, out=s)
+            out = resample(t, dims, (t1, t1), (t2, t2), m3, scale, adjoint=False, out=s)
         ctx.save_for_backward(xt, *ws, cwm, x, s if fuse_gelu else None)
-        ctx.geom = (din, tuple(dims), plan, cb is not None, tuple(cw.shape))
+        ctx.geom = (din, tuple(dims), plan, cb is not None, tuple(cw.shape), resample)
         return out
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
         xt, w1, w2, w3, w4, cwm, x, pre = ctx.saved_tensors
-        din, dims, plan, has_bias, cw_shape = ctx.geom
+        din, dims, plan, has_bias, cw_shape, resample = ctx.geom
         g = _plain(g)
         if pre is not None:
             g = torch.ops.aten.gelu_backward(g, pre)
@@ -198,10 +200,10 @@ class _OperatorBlock3dFn(torch.autograd.Function):
         if need_gx or need_gc:
             t1, t2, m3 = plan
             scale = 1.0 / (dims[0] * dims[1] * dims[2])
-            g_t = _native.fft_resample3d(g, din, (t1, t1), (t2, t2), m3, scale, adjoint=True).view(B, Co, -1)
+            g_t = resample(g, din, (t1, t1), (t2, t2), m3, scale, adjoint=True).view(B, Co, -1)
             if need_gx:
                 _native.channel_mix(g_t, cwm, None, transpose_w=True, out=gx.view(B, Ci, -1))        # accumulates into the spectral branch's gx
             if need_gc:
                 gcw, gcb = _wgrad_into(ctx.leaves, g_t, x.view(B, Ci, -1), None, ctx.needs_input_grad[5], has_bias and ctx.needs_input_grad[6])
                 gcw = None if gcw is None else gcw.view(cw_shape)
-        return (gx, *gws, gcw, gcb, None, None, None)
+        return (gx, *gws, gcw, gcb, None, None, None, None)
