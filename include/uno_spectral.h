@@ -157,7 +157,11 @@ int uno_reserve_cus(int n);
 /* ABI 11.  (no reference counterpart) Alternating sweep direction: consecutive launches of the streaming kernels walk their work items
  * (images, batch entries, pixel tiles) in opposite directions, so that a kernel starts with the part of a > 256 MB tensor its predecessor
  * touched last - the part the Infinity Cache still holds.  Results do not depend on it.  enable = 0 turns it off (every launch front to
- * back); returns the previous setting (default 1). */
+ * back); returns the previous setting (default 255 = every family; 1 is stored as 255).  Other values 0 .. 255 are a mask of kernel families
+ * (development).  A value with bit 8 set (256 | mask) PINS the direction: every launch of a masked family runs reversed and the per-thread
+ * launch counter is neither read nor advanced (the masked-off families run front to back); for tests, which can then run one launch both
+ * ways - backward launches included, whose counter belongs to another thread.  The value returned then is that 256 | mask.  A negative
+ * value never pins: its low eight bits are the mask, as before. */
 int uno_sweep_alternation(int enable);
 
 /* ABI 11.  Pruned inverse DFT PLUS the up-sampled point-wise branch in one pass over the output:

@@ -414,6 +414,19 @@ def sweep_alternation(enable: bool) -> bool:
     return bool(lib().uno_sweep_alternation(1 if enable else 0))
 
 
+def sweep_direction(mode: str, mask: int = 255) -> int:
+    """Direction of the sweep-taking launches of the families in `mask` (the SWEEP_* bits of csrc/uno_common.h; the others run front to
+    back): "alternate" (the default: every other launch of a thread reversed), "forward" (every launch front to back) or "reversed"
+    (every launch reversed, the per-thread counter untouched).  Returns the previous raw setting of uno_sweep_alternation, which
+    lib().uno_sweep_alternation(value) restores."""
+    if mode not in ("alternate", "forward", "reversed") or not 0 <= int(mask) <= 255:
+        raise ValueError(f"uno_amd: sweep_direction({mode!r}, {mask!r}): mode is alternate | forward | reversed, mask 0 .. 255")
+    value = {"alternate": int(mask), "forward": 0, "reversed": 256 | int(mask)}[mode]
+    if value == 1:
+        raise ValueError("uno_amd: sweep_direction('alternate', 1): the C entry point reads 1 as 'every family' (255)")
+    return int(lib().uno_sweep_alternation(value))
+
+
 def dft2d_inverse_add_applies(n_img, H, W, m1, m2, Hs, Ws) -> bool:
     """True where dft2d_inverse(..., addend=) runs the fused kernel (K3 + up-sampled addend, csrc/dft2d_inv_add_kernel.h)."""
     return bool(lib().uno_dft2d_inverse_add_applies(int(n_img), int(H), int(W), int(m1), int(m2), int(Hs), int(Ws)))

@@ -116,8 +116,15 @@ int reserved_cus() { return __atomic_load_n(&g_reserved_cus, __ATOMIC_RELAXED); 
 static int g_sweep_alternation = 255;
 static thread_local unsigned t_sweep_count = 0;
 // family bits of the setting: 1 K1, 2 K3, 4 K7, 8 K8, 16 K9, 32 InstanceNorm, 64 GELU-projection backward, 128 lift kernels; a launch of a
-// family that is switched off runs front to back and does not advance the counter
-int next_sweep_reversed(int family) { return (__atomic_load_n(&g_sweep_alternation, __ATOMIC_RELAXED) & family) ? (int)(t_sweep_count++ & 1u) : 0; }
+// family that is switched off runs front to back and does not advance the counter.  Bit 8 (256 | mask) pins the direction: every launch of a
+// masked family runs reversed and the counter is neither read nor advanced (the tests' handle on the direction: a caller cannot see or set
+// the counter of another thread, autograd's among them)
+int next_sweep_reversed(int family) {
+    const int a = __atomic_load_n(&g_sweep_alternation, __ATOMIC_RELAXED);
+    if (!(a & family)) return 0;
+    if (a & 256) return 1;
+    return (int)(t_sweep_count++ & 1u);
+}
 
 }  // namespace uno
 
@@ -135,7 +142,7 @@ void* uno_upload_table(const void* host, long long bytes) {
 }
 
 int uno_sweep_alternation(int enable) {
-    return __atomic_exchange_n(&uno::g_sweep_alternation, enable == 1 ? 255 : (enable & 255), __ATOMIC_RELAXED);      // (1: all families; other values: a mask, development)
+    return __atomic_exchange_n(&uno::g_sweep_alternation, enable == 1 ? 255 : (enable & (enable < 0 ? 255 : 511)), __ATOMIC_RELAXED);      // (1: all families; other values: a mask, development; 256 | mask: pinned reversed; negative values keep their low eight bits, as before)
 }
 
 int uno_reserve_cus(int n) {

@@ -278,7 +278,8 @@ int reserved_cus();
 // tail before reaching it.  So consecutive launches of the streaming kernels walk their work items (images, batch entries, pixel tiles)
 // in opposite directions: every launcher takes the next direction from a per-thread counter.  Only the ORDER changes - workgroup k
 // computes work item G - 1 - k, writes that item's outputs and partial-sum slots - never the result.  uno_sweep_alternation(0) turns
-// it off (every launch front to back).
+// it off (every launch front to back); uno_sweep_alternation(256 | mask) pins the masked families to the reversed direction on every launch
+// and leaves the counter alone (tests/test_hip_launch_state.py holds every family to "only the order changes" with it).
 int next_sweep_reversed(int family);       // family: SWEEP_* bit (uno_sweep_alternation takes a mask of them; 1 = all)
 enum { SWEEP_K1 = 1, SWEEP_K3 = 2, SWEEP_K7 = 4, SWEEP_K8 = 8, SWEEP_K9 = 16, SWEEP_NORM = 32, SWEEP_PROJ = 64, SWEEP_LIFT = 128 };
 inline int usable_cus(int device_cus) { const int r = reserved_cus(); return device_cus - r >= 8 ? device_cus - r : (device_cus < 8 ? device_cus : 8); }
