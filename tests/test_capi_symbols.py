@@ -88,3 +88,49 @@ def test_argument_errors_of_the_block_level_entry_points(libpath):
     assert lib.uno_gelu_pad(nul, nul, nul, 0, 4, 4, 5, 5, 0, None) == 0
     assert lib.uno_instnorm_forward(nul, nul, nul, nul, nul, nul, 0, 2, 7, 1e-5, 1, None) == 0
     assert lib.uno_channel_wgrad_ws_bytes(2, 64, 64, 1000) > 0 and lib.uno_gelu_project_bwd_ws_bytes(2, 64, 5000) % (4 * 65) == 0 and lib.uno_gelu_project_bwd_ws_bytes(2, 64, 5000) > 0
+
+
+def _prototypes():
+    """{entry point: (return type, [argument kind])} of include/uno_spectral.h; kinds: int, long long, float, double, pointer"""
+    hdr = open(os.path.join(ROOT, "include", "uno_spectral.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    hdr = re.sub(r"//[^\n]*", "", hdr)
+    out = {}
+    for ret, name, args in re.findall(r"\b(int|long long|void\s*\*|const char\s*\*)\s*(uno_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", hdr):
+        kinds = []
+        for arg in (a.strip() for a in args.split(",")):
+            if arg == "void" and "," not in args:
+                continue
+            if "*" in arg:
+                kinds.append("pointer")
+            else:
+                kind = " ".join(arg.split()[:-1])            # the type: everything before the parameter's name
+                assert kind in ("int", "long long", "float", "double"), f"{name}: argument {arg!r} of a kind the binding does not know"
+                kinds.append(kind)
+        assert name not in out, f"{name} declared twice"
+        out[name] = (re.sub(r"\s+", "", ret).replace("constchar", "const char").replace("longlong", "long long"), kinds)
+    return out
+
+
+def test_binding_signatures_match_the_header_prototypes():
+    """Argument count, the kind of every argument and the return type of every entry point as _native._SIGNATURES declares them
+    equal the header's prototypes (a c_int where the header says long long would truncate a pixel count silently)."""
+    from uno_amd import _native
+    protos = _prototypes()
+    assert sorted(protos) == _declared()
+
+    def kind(ct):
+        scalar = {ctypes.c_int: "int", ctypes.c_longlong: "long long", ctypes.c_float: "float", ctypes.c_double: "double"}
+        if ct in scalar:
+            return scalar[ct]
+        assert ct in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(ct, ctypes._Pointer), ct
+        return "pointer"
+
+    returns = {ctypes.c_int: "int", ctypes.c_longlong: "long long", ctypes.c_void_p: "void*", ctypes.c_char_p: "const char*"}
+    assert sorted(_native._SIGNATURES) == sorted(protos)
+    for name, (res, args) in _native._SIGNATURES.items():
+        ret, kinds = protos[name]
+        assert returns[res] == ret, f"{name}: returns {ret} in the header, {res.__name__} in the binding"
+        assert len(args) == len(kinds), f"{name}: {len(kinds)} arguments in the header, {len(args)} in the binding"
+        for i, (a, k) in enumerate(zip(args, kinds)):
+            assert kind(a) == k, f"{name}: argument {i} is {k} in the header, {a.__name__} in the binding"

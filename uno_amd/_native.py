@@ -210,6 +210,11 @@ def _require(t: torch.Tensor, dtype, name: str, dense: bool = True):
         raise RuntimeError(f"uno_amd: {name} must be contiguous")
 
 
+def _entry(name: str, bf16: bool):
+    """the float32 entry point `name`, or its bfloat16 twin `name`_bf16"""
+    return getattr(lib(), name + "_bf16" if bf16 else name)
+
+
 def _act_dtype(t, name):
     """f32, or bf16 for the mixed-precision entry points (activations bf16, everything else f32 / c64)."""
     bf16 = t.dtype == torch.bfloat16
@@ -278,7 +283,7 @@ def spectral_conv2d_forward(x, w1, w2, Ho: int, Wo: int, xt_out=None):
             if tuple(xt.shape) != (B, Ci, 2 * m1, m2):
                 raise RuntimeError("uno_amd: xtrunc buffer has the wrong shape")
         ws = torch.empty(max(1, L.uno_spectral_conv2d_fwd_ws_bytes(B, Ci, Co, m1, m2)), dtype=torch.uint8, device=x.device)
-        fn = L.uno_spectral_conv2d_forward_mixed if wh else (L.uno_spectral_conv2d_forward_bf16 if bf16 else L.uno_spectral_conv2d_forward)
+        fn = L.uno_spectral_conv2d_forward_mixed if wh else _entry("uno_spectral_conv2d_forward", bf16)
         with _any_mode_scratch(x.device, (B * Ci, H, W, m1, m2), (B * Co, Ho, Wo, m1, m2)):
             rc = fn(_ptr(x), _ptr(w1), _ptr(w2), _ptr(y), _ptr(xt), _ptr(ws), B, Ci, Co, H, W, Ho, Wo, m1, m2, _stream(x))
     _check(rc, "uno_spectral_conv2d_forward")
@@ -310,71 +315,50 @@ def spectral_conv2d_backward(gy, xt, w1, w2, H: int, W: int, need_gx=True, need_
     return gx, gw1, gw2
 
 
+def _fft_resample3d(any_grid: bool, x, out_size, f1, f2, m3, scale, adjoint, out, act):
+    """fft_resample3d / fft_resample3d_any: the two kernel families take the same arguments"""
+    name = "uno_fft_resample3d_any" if any_grid else "uno_fft_resample3d"
+    _require(x, torch.float32, "x")
+    *lead, D1, D2, D3 = x.shape
+    M1, M2, M3 = (int(v) for v in out_size)
+    n = _count(lead)
+    for t in (*f1, *f2):
+        if t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous():
+            raise RuntimeError("uno_amd: frequency tables must be contiguous int32 device tensors")
+    J1, J2 = f1[0].numel(), f2[0].numel()
+    if any_grid and (f1[1].numel() != J1 or f2[1].numel() != J2):
+        raise RuntimeError("uno_amd: the forward and inverse frequency tables of an axis must have the same length")
+    L = lib()
+    with torch.cuda.device(x.device):
+        ws = torch.empty(max(1, getattr(L, name + "_ws_bytes")(n, D1, M1, J1, J2, int(m3))), dtype=torch.uint8, device=x.device)
+        if out is not None:
+            _require(out, torch.float32, "out")
+            if tuple(out.shape) != (*lead, M1, M2, M3) or not out.is_contiguous():
+                raise RuntimeError(f"uno_amd: out must be a contiguous {(*lead, M1, M2, M3)} tensor")
+            ya = torch.empty_like(out) if act else None
+            fn, dst, res = getattr(L, name + "_acc"), (_ptr(out), _opt(ya)), ((out, ya) if act else out)
+        else:
+            res = torch.empty((*lead, M1, M2, M3), dtype=torch.float32, device=x.device)
+            fn, dst = getattr(L, name), (_ptr(res),)
+        rc = fn(_ptr(x), *dst, _ptr(ws), n, D1, D2, D3, M1, M2, M3, J1, _ptr(f1[0]), _ptr(f1[1]), J2, _ptr(f2[0]), _ptr(f2[1]),
+                int(m3), float(scale), int(adjoint), int(not adjoint), _stream(x))
+    _check(rc, name + ("_acc" if out is not None else ""))
+    return res
+
+
 def fft_resample3d(x, out_size, f1, f2, m3: int, scale: float, adjoint: bool, out=None, act=False):
     """x (..., D1, D2, D3) f32 -> (..., M1, M2, M3): pruned DFT with row frequencies f1[0] / f2[0] (int32 device tensors) along
     axes 1 / 2 and m3 half-spectrum bins, pruned inverse DFT with f1[1] / f2[1]; adjoint=True: Hermitian weights on the
     forward side instead of the inverse side (the transpose of the operator with sizes and tables swapped).
     out: ACCUMULATE into this (..., M1, M2, M3) tensor (returned); act: also return gelu(out) written in the same pass -> (out, act)."""
-    _require(x, torch.float32, "x")
-    *lead, D1, D2, D3 = x.shape
-    M1, M2, M3 = (int(v) for v in out_size)
-    n = _count(lead)
-    for t in (*f1, *f2):
-        if t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous():
-            raise RuntimeError("uno_amd: frequency tables must be contiguous int32 device tensors")
-    J1, J2 = f1[0].numel(), f2[0].numel()
-    L = lib()
-    with torch.cuda.device(x.device):
-        ws = torch.empty(max(1, L.uno_fft_resample3d_ws_bytes(n, D1, M1, J1, J2, int(m3))), dtype=torch.uint8, device=x.device)
-        if out is not None:
-            _require(out, torch.float32, "out")
-            if tuple(out.shape) != (*lead, M1, M2, M3) or not out.is_contiguous():
-                raise RuntimeError(f"uno_amd: out must be a contiguous {(*lead, M1, M2, M3)} tensor")
-            ya = torch.empty_like(out) if act else None
-            rc = L.uno_fft_resample3d_acc(_ptr(x), _ptr(out), _opt(ya), _ptr(ws), n, D1, D2, D3, M1, M2, M3,
-                                          J1, _ptr(f1[0]), _ptr(f1[1]), J2, _ptr(f2[0]), _ptr(f2[1]), int(m3), float(scale),
-                                          int(adjoint), int(not adjoint), _stream(x))
-            _check(rc, "uno_fft_resample3d_acc")
-            return (out, ya) if act else out
-        y = torch.empty((*lead, M1, M2, M3), dtype=torch.float32, device=x.device)
-        rc = L.uno_fft_resample3d(_ptr(x), _ptr(y), _ptr(ws), n, D1, D2, D3, M1, M2, M3, J1, _ptr(f1[0]), _ptr(f1[1]), J2,
-                                  _ptr(f2[0]), _ptr(f2[1]), int(m3), float(scale), int(adjoint), int(not adjoint), _stream(x))
-    _check(rc, "uno_fft_resample3d")
-    return y
+    return _fft_resample3d(False, x, out_size, f1, f2, m3, scale, adjoint, out, act)
 
 
 def fft_resample3d_any(x, out_size, f1, f2, m3: int, scale: float, adjoint: bool, out=None, act=False):
     """fft_resample3d on the any-grid kernels (uno_fft_resample3d_any / _acc): any number of kept rows, any 1 <= m3 <= n/2 + 1, axis
-    lengths 2 ... 128.  Same tables, the same adjoint convention and the same `out` / `act`: ACCUMULATE into `out` (returned); act: also
-    return gelu(out) written in the same pass -> (out, act)."""
-    _require(x, torch.float32, "x")
-    *lead, D1, D2, D3 = x.shape
-    M1, M2, M3 = (int(v) for v in out_size)
-    n = _count(lead)
-    for t in (*f1, *f2):
-        if t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous():
-            raise RuntimeError("uno_amd: frequency tables must be contiguous int32 device tensors")
-    J1, J2 = f1[0].numel(), f2[0].numel()
-    if f1[1].numel() != J1 or f2[1].numel() != J2:
-        raise RuntimeError("uno_amd: the forward and inverse frequency tables of an axis must have the same length")
-    L = lib()
-    with torch.cuda.device(x.device):
-        ws = torch.empty(max(1, L.uno_fft_resample3d_any_ws_bytes(n, D1, M1, J1, J2, int(m3))), dtype=torch.uint8, device=x.device)
-        if out is not None:
-            _require(out, torch.float32, "out")
-            if tuple(out.shape) != (*lead, M1, M2, M3) or not out.is_contiguous():
-                raise RuntimeError(f"uno_amd: out must be a contiguous {(*lead, M1, M2, M3)} tensor")
-            ya = torch.empty_like(out) if act else None
-            rc = L.uno_fft_resample3d_any_acc(_ptr(x), _ptr(out), _opt(ya), _ptr(ws), n, D1, D2, D3, M1, M2, M3,
-                                              J1, _ptr(f1[0]), _ptr(f1[1]), J2, _ptr(f2[0]), _ptr(f2[1]), int(m3), float(scale),
-                                              int(adjoint), int(not adjoint), _stream(x))
-            _check(rc, "uno_fft_resample3d_any_acc")
-            return (out, ya) if act else out
-        y = torch.empty((*lead, M1, M2, M3), dtype=torch.float32, device=x.device)
-        rc = L.uno_fft_resample3d_any(_ptr(x), _ptr(y), _ptr(ws), n, D1, D2, D3, M1, M2, M3, J1, _ptr(f1[0]), _ptr(f1[1]), J2,
-                                      _ptr(f2[0]), _ptr(f2[1]), int(m3), float(scale), int(adjoint), int(not adjoint), _stream(x))
-    _check(rc, "uno_fft_resample3d_any")
-    return y
+    lengths 2 ... 128.  Same tables, the same adjoint convention and the same `out` / `act`; the forward and inverse tables of an axis
+    must have the same length."""
+    return _fft_resample3d(True, x, out_size, f1, f2, m3, scale, adjoint, out, act)
 
 
 def dft2d_forward(images, m1, m2, scale=1.0, hermitian_cols=False, mask_overlap=False, out=None, channel_offset=0):
@@ -386,7 +370,7 @@ def dft2d_forward(images, m1, m2, scale=1.0, hermitian_cols=False, mask_overlap=
     if out is None:
         spec = torch.empty((*lead, 2 * m1, m2), dtype=torch.complex64, device=images.device)
         with torch.cuda.device(images.device):
-            fn = lib().uno_dft2d_forward_bf16 if bf16 else lib().uno_dft2d_forward
+            fn = _entry("uno_dft2d_forward", bf16)
             with _any_mode_scratch(images.device, (n, H, W, m1, m2)):
                 rc = fn(_ptr(images), _ptr(spec), n, H, W, m1, m2, float(scale), int(hermitian_cols), int(mask_overlap), _stream(images))
         _check(rc, "uno_dft2d_forward")
@@ -396,7 +380,7 @@ def dft2d_forward(images, m1, m2, scale=1.0, hermitian_cols=False, mask_overlap=
             or channel_offset < 0 or channel_offset + images.shape[1] > out.shape[1]:
         raise RuntimeError("uno_amd: out must be (B, Ctot, 2*m1, m2) with room for the image channels at channel_offset")
     with torch.cuda.device(images.device):
-        fn = lib().uno_dft2d_forward_grouped_bf16 if bf16 else lib().uno_dft2d_forward_grouped
+        fn = _entry("uno_dft2d_forward_grouped", bf16)
         with _any_mode_scratch(images.device, (n, H, W, m1, m2)):
             rc = fn(_ptr(images), _ptr(out), n, H, W, m1, m2, float(scale), int(hermitian_cols),
                     int(mask_overlap), images.shape[1], out.shape[1], int(channel_offset), _stream(images))
@@ -459,7 +443,7 @@ def dft2d_inverse(spec, H, W, scale=1.0, hermitian_cols=True, mask_overlap=True,
             raise RuntimeError("uno_amd: images are float32 or bfloat16")
         img = torch.empty((*lead, H, W), dtype=dtype, device=spec.device)
         with torch.cuda.device(spec.device):
-            fn = lib().uno_dft2d_inverse_bf16 if dtype == torch.bfloat16 else lib().uno_dft2d_inverse
+            fn = _entry("uno_dft2d_inverse", dtype == torch.bfloat16)
             with _any_mode_scratch(spec.device, (n, H, W, m1, m2)):
                 rc = fn(_ptr(spec), _ptr(img), n, H, W, m1, m2, float(scale), int(hermitian_cols), int(mask_overlap), _stream(spec))
         _check(rc, "uno_dft2d_inverse")
@@ -471,7 +455,7 @@ def dft2d_inverse(spec, H, W, scale=1.0, hermitian_cols=True, mask_overlap=True,
     B = spec.shape[0]
     img = torch.empty((B, channels, H, W), dtype=dtype, device=spec.device)
     with torch.cuda.device(spec.device):
-        fn = lib().uno_dft2d_inverse_grouped_bf16 if dtype == torch.bfloat16 else lib().uno_dft2d_inverse_grouped
+        fn = _entry("uno_dft2d_inverse_grouped", dtype == torch.bfloat16)
         with _any_mode_scratch(spec.device, (B * channels, H, W, m1, m2)):
             rc = fn(_ptr(spec), _ptr(img), B * channels, H, W, m1, m2, float(scale), int(hermitian_cols),
                     int(mask_overlap), int(channels), spec.shape[1], int(channel_offset), _stream(spec))
@@ -610,19 +594,24 @@ def resample2d(x, Ho: int, Wo: int, tabH, tabW, tilesH=None, out=None):
             targs = (_ptr(tp0), _ptr(tw), tw.shape[1])
         else:
             targs = (C.c_void_p(0), C.c_void_p(0), 0)
-        fn = lib().uno_resample2d_bf16 if bf16 else lib().uno_resample2d
+        fn = _entry("uno_resample2d", bf16)
         rc = fn(_ptr(x), _ptr(out), _ptr(tmp), n, H, W, Ho, Wo, _ptr(sH), _ptr(wH), wH.shape[1],
                 _ptr(sW), _ptr(wW), wW.shape[1], *targs, 1 if accumulate else 0, _stream(x))
     _check(rc, "uno_resample2d")
     return out
 
 
+def _window_fits(rows: int, cols: int, pitch: int, plane: int) -> bool:
+    """the window rule of the _win entry points (uno_spectral.h, ABI 10)"""
+    return not (rows < 1 or cols % 4 or cols < 260 or pitch < cols or (rows - 1) * pitch + cols > plane or rows * cols >= 1 << 24)
+
+
 def _window_args(window, plane: int, bf16: bool):
-    """(rows, cols, pitch) of a windowed call (uno_spectral.h, ABI 10): the tensors' last axis is a whole plane of `plane` elements."""
+    """(rows, cols, pitch) of a windowed call: the tensors' last axis is a whole plane of `plane` elements."""
     rows, cols, pitch = (int(v) for v in window)
     if bf16:
         raise RuntimeError("uno_amd: pixel windows are float32 only")
-    if rows < 1 or cols % 4 or cols < 260 or pitch < cols or (rows - 1) * pitch + cols > plane or rows * cols >= 1 << 24:
+    if not _window_fits(rows, cols, pitch, plane):
         raise RuntimeError(f"uno_amd: window rows={rows} cols={cols} pitch={pitch} does not fit a plane of {plane} elements "
                            "(cols: a multiple of 4, 260 <= cols <= pitch; rows * cols < 2^24)")
     return rows, cols, pitch
@@ -658,11 +647,9 @@ def channel_mix(x, w, bias=None, transpose_w: bool = False, out=None, act_in: bo
             _require(dgelu_of, x.dtype, "dgelu_of")
             if tuple(dgelu_of.shape) != (B, Co, P):
                 raise RuntimeError(f"uno_amd: dgelu_of has shape {tuple(dgelu_of.shape)}, expected {(B, Co, P)}")
-        fn = lib().uno_channel_mix_bf16 if bf16 else lib().uno_channel_mix
-        rc = fn(_ptr(x), _ptr(w), _opt(bias), _ptr(y),
-                                   B, Ci, Co, P, 1 if transpose_w else 0,
-                                   (2 if (dgelu_total and dgelu_of is not None) else 1) if accumulate else 0, 1 if act_in else 0,
-                                   _opt(dgelu_of), _stream(x))
+        rc = _entry("uno_channel_mix", bf16)(_ptr(x), _ptr(w), _opt(bias), _ptr(y), B, Ci, Co, P, 1 if transpose_w else 0,
+                                             (2 if (dgelu_total and dgelu_of is not None) else 1) if accumulate else 0,
+                                             1 if act_in else 0, _opt(dgelu_of), _stream(x))
     _check(rc, "uno_channel_mix")
     return y
 
@@ -844,7 +831,7 @@ def channel_mix2(x1, x2, w, bias=None, transpose_w: bool = False, out=None, out2
         if window is not None:
             fn, size = lib().uno_channel_mix2_win, (*_window_args(window, P, bf16), P)
         else:
-            fn, size = (lib().uno_channel_mix2_bf16 if bf16 else lib().uno_channel_mix2), (P,)
+            fn, size = _entry("uno_channel_mix2", bf16), (P,)
         rc = fn(_ptr(x1), _opt(x2), C1, _ptr(w), _opt(bias), _ptr(y1), _opt(y2), Co1, _opt(act),
                 B, Ci, Co, *size, 1 if transpose_w else 0, acc_flag, 1 if act_in else 0,
                 _opt(dgelu_of), _opt(pw), _opt(pb), _opt(proj), _stream(x1))
@@ -868,15 +855,7 @@ def channel_wgrad_finish(parts, Ci: int, Co: int, need_bias: bool, out_w=None, o
     blk = Co * (Ci + 1)
     if parts.numel() == 0 or parts.numel() % blk:
         raise RuntimeError("uno_amd: the partial sums are not a whole number of (Co, Ci + 1) blocks")
-    if out_w is None:
-        accumulate = False
-        gw = torch.empty((Co, Ci), dtype=torch.float32, device=parts.device)
-        gb = torch.empty((Co,), dtype=torch.float32, device=parts.device) if need_bias else None
-    else:
-        gw, gb = out_w, (out_b if need_bias else None)
-        _require(gw, torch.float32, "weight-gradient buffer")
-        if gw.numel() != Co * Ci or (need_bias and (gb is None or gb.numel() != Co)):
-            raise RuntimeError("uno_amd: gradient buffers do not match the layer")
+    gw, gb, accumulate = _real_grad_buffers(out_w, out_b, Ci, Co, need_bias, parts.device, accumulate)
     with torch.cuda.device(parts.device):
         rc = lib().uno_channel_wgrad_finish(_ptr(parts), _ptr(gw), _opt(gb), Ci, Co,
                                             parts.numel() // blk, 1 if accumulate else 0, _stream(parts))
@@ -915,9 +894,8 @@ def channel_wgrad2(gy, x1, x2, need_bias: bool = True, act_x: bool = False, out_
         if partials_out.numel() != channel_wgrad_partial_floats(B, Ci, Co, P):
             raise RuntimeError("uno_amd: partial-sum buffer has the wrong size")
         with torch.cuda.device(gy.device):
-            fn = L.uno_channel_wgrad2_bf16 if bf16 else L.uno_channel_wgrad2
-            rc = fn(_ptr(gy), _ptr(x1), _opt(x2), C1, C.c_void_p(0), C.c_void_p(0),
-                    _ptr(partials_out), B, Ci, Co, P, 1 if act_x else 0, 3, _stream(gy))
+            rc = _entry("uno_channel_wgrad2", bf16)(_ptr(gy), _ptr(x1), _opt(x2), C1, C.c_void_p(0), C.c_void_p(0),
+                                                    _ptr(partials_out), B, Ci, Co, P, 1 if act_x else 0, 3, _stream(gy))
         _check(rc, "uno_channel_wgrad2")
         return None, None
     gw, gb, accumulate = _real_grad_buffers(out_w, out_b, Ci, Co, need_bias, gy.device, accumulate)
@@ -925,7 +903,7 @@ def channel_wgrad2(gy, x1, x2, need_bias: bool = True, act_x: bool = False, out_
         if window is not None:
             fn, size, Pl = L.uno_channel_wgrad2_win, (*win, P), win[0] * win[1]
         else:
-            fn, size, Pl = (L.uno_channel_wgrad2_bf16 if bf16 else L.uno_channel_wgrad2), (P,), P
+            fn, size, Pl = _entry("uno_channel_wgrad2", bf16), (P,), P
         ws = torch.empty(max(1, L.uno_channel_wgrad_ws_bytes(B, Ci, Co, Pl)), dtype=torch.uint8, device=gy.device)
         rc = fn(_ptr(gy), _ptr(x1), _opt(x2), C1, _ptr(gw), _opt(gb),
                 _ptr(ws), B, Ci, Co, *size, 1 if act_x else 0, 1 if accumulate else 0, _stream(gy))
@@ -946,9 +924,7 @@ def channel_wgrad(gy, x, need_bias: bool = True, act_x: bool = False):
     gb = torch.empty((Co,), dtype=torch.float32, device=x.device) if need_bias else None
     with torch.cuda.device(x.device):
         ws = torch.empty(max(1, L.uno_channel_wgrad_ws_bytes(B, Ci, Co, P)), dtype=torch.uint8, device=x.device)
-        fn = L.uno_channel_wgrad_bf16 if bf16 else L.uno_channel_wgrad
-        rc = fn(_ptr(gy), _ptr(x), _ptr(gw), _opt(gb), _ptr(ws),
-                                 B, Ci, Co, P, 1 if act_x else 0, _stream(x))
+        rc = _entry("uno_channel_wgrad", bf16)(_ptr(gy), _ptr(x), _ptr(gw), _opt(gb), _ptr(ws), B, Ci, Co, P, 1 if act_x else 0, _stream(x))
     _check(rc, "uno_channel_wgrad")
     return gw, gb
 
@@ -979,8 +955,7 @@ def gelu_project_forward(pre, w, bias=None):
         raise RuntimeError(f"uno_amd: weight has {w.numel()} entries for {Cc} channels")
     out = torch.empty((B, P), dtype=pre.dtype, device=pre.device)
     with torch.cuda.device(pre.device):
-        rc = (lib().uno_gelu_project_forward_bf16 if bf16 else lib().uno_gelu_project_forward)(_ptr(pre), _ptr(w), _opt(bias), _ptr(out),
-                                            B, Cc, P, _stream(pre))
+        rc = _entry("uno_gelu_project_forward", bf16)(_ptr(pre), _ptr(w), _opt(bias), _ptr(out), B, Cc, P, _stream(pre))
     _check(rc, "uno_gelu_project_forward")
     return out
 
@@ -1002,7 +977,7 @@ def gelu_project_backward(pre, w, gout, need_bias=True, window=None):
             win = _window_args(window, P, bf16)
             fn, size, Pl = L.uno_gelu_project_backward_win, (*win, P), win[0] * win[1]
         else:
-            fn, size, Pl = (L.uno_gelu_project_backward_bf16 if bf16 else L.uno_gelu_project_backward), (P,), P
+            fn, size, Pl = _entry("uno_gelu_project_backward", bf16), (P,), P
         ws = torch.empty(max(1, L.uno_gelu_project_bwd_ws_bytes(B, Cc, Pl)), dtype=torch.uint8, device=pre.device)
         rc = fn(_ptr(pre), _ptr(w), _ptr(gout), _ptr(gpre), _ptr(gw), _opt(gb), _ptr(ws), B, Cc, *size,
                 _stream(pre))
@@ -1043,13 +1018,11 @@ def _project_geometry(window, P: int):
 
 def project_backward_applies(B: int, C1: int, Ci: int, Co: int, P: int, window=None) -> bool:
     """Does uno_project_backward take fc1 (Ci -> Co, sources split at C1; C1 = Ci: one source) on planes of P elements [on that window]?"""
+    geo = (0, 0, 0, P)
     if window is not None:
-        rows, cols, pitch = (int(v) for v in window)
-        if rows < 1 or cols % 4 or cols < 260 or pitch < cols or (rows - 1) * pitch + cols > P or rows * cols >= 1 << 24:
+        geo = (*(int(v) for v in window), P)
+        if not _window_fits(*geo):
             return False
-        geo = (rows, cols, pitch, P)
-    else:
-        geo = (0, 0, 0, P)
     return bool(lib().uno_project_backward_applies(B, C1, Ci, Co, *geo))
 
 
@@ -1088,30 +1061,27 @@ def project_backward(x1, x2, w, pre, w2, gout, act_in: bool = False, need_bias: 
     return g1, g2, gw, gb, gw2, gb2
 
 
-def gelu_pad(s, Hp: int, Wp: int):
-    """s (..., H, W) f32 -> (..., Hp, Wp) = zero-pad(gelu(s)) at the end of both axes."""
-    bf16 = _act_dtype(s, "s")
+def _gelu_pad(s, gy, out, Hp: int, Wp: int):
+    """uno_gelu_pad: out = zero-pad(gelu(s)) to (Hp, Wp), or with gy (..., Hp, Wp) the backward form gelu'(s) * gy[..., :H, :W]"""
     *lead, H, W = s.shape
-    n = _count(lead)
-    out = torch.empty((*lead, Hp, Wp), dtype=s.dtype, device=s.device)
     with torch.cuda.device(s.device):
-        rc = (lib().uno_gelu_pad_bf16 if bf16 else lib().uno_gelu_pad)(_ptr(s), C.c_void_p(0), _ptr(out), n, H, W, Hp, Wp, 0, _stream(s))
+        rc = _entry("uno_gelu_pad", s.dtype == torch.bfloat16)(_ptr(s), _opt(gy), _ptr(out), _count(lead), H, W, Hp, Wp,
+                                                               0 if gy is None else 1, _stream(s))
     _check(rc, "uno_gelu_pad")
     return out
+
+
+def gelu_pad(s, Hp: int, Wp: int):
+    """s (..., H, W) f32 -> (..., Hp, Wp) = zero-pad(gelu(s)) at the end of both axes."""
+    _act_dtype(s, "s")
+    return _gelu_pad(s, None, torch.empty((*s.shape[:-2], Hp, Wp), dtype=s.dtype, device=s.device), Hp, Wp)
 
 
 def gelu_pad_backward(s, gy):
     """gs (..., H, W) = gelu'(s) * gy[..., :H, :W]."""
-    bf16 = _act_dtype(s, "s")
+    _act_dtype(s, "s")
     _require(gy, s.dtype, "grad_output")
-    *lead, H, W = s.shape
-    Hp, Wp = gy.shape[-2:]
-    n = _count(lead)
-    out = torch.empty_like(s)
-    with torch.cuda.device(s.device):
-        rc = (lib().uno_gelu_pad_bf16 if bf16 else lib().uno_gelu_pad)(_ptr(s), _ptr(gy), _ptr(out), n, H, W, Hp, Wp, 1, _stream(s))
-    _check(rc, "uno_gelu_pad")
-    return out
+    return _gelu_pad(s, gy, torch.empty_like(s), *gy.shape[-2:])
 
 
 def channels_last_pitch(t):
@@ -1158,8 +1128,8 @@ def instnorm_forward(x, gamma, beta, eps: float, gelu: bool):
     mean = torch.empty(rows, dtype=torch.float32, device=x.device)
     rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
-        rc = (lib().uno_instnorm_forward_bf16 if bf16 else lib().uno_instnorm_forward)(_ptr(x), _opt(gamma), _opt(beta),
-                                        _ptr(y), _ptr(mean), _ptr(rstd), rows, Cc, N, float(eps), 1 if gelu else 0, _stream(x))
+        rc = _entry("uno_instnorm_forward", bf16)(_ptr(x), _opt(gamma), _opt(beta), _ptr(y), _ptr(mean), _ptr(rstd), rows, Cc, N,
+                                                  float(eps), 1 if gelu else 0, _stream(x))
     _check(rc, "uno_instnorm_forward")
     return y, mean, rstd
 
@@ -1175,9 +1145,8 @@ def instnorm_backward(x, gy, gamma, beta, mean, rstd, gelu: bool):
     s1 = torch.empty((B, Cc), dtype=torch.float32, device=x.device)
     s2 = torch.empty((B, Cc), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
-        rc = (lib().uno_instnorm_backward_bf16 if bf16 else lib().uno_instnorm_backward)(_ptr(x), _ptr(gy), _opt(gamma),
-                                         _opt(beta), _ptr(mean), _ptr(rstd), _ptr(gx), _ptr(s1), _ptr(s2),
-                                         rows, Cc, N, 1 if gelu else 0, _stream(x))
+        rc = _entry("uno_instnorm_backward", bf16)(_ptr(x), _ptr(gy), _opt(gamma), _opt(beta), _ptr(mean), _ptr(rstd), _ptr(gx), _ptr(s1),
+                                                   _ptr(s2), rows, Cc, N, 1 if gelu else 0, _stream(x))
     _check(rc, "uno_instnorm_backward")
     return gx, s1, s2
 

@@ -33,6 +33,59 @@ def _half_weights(w1, w2):
     return out[0], out[1]
 
 
+def _xt_slot(stack):
+    """where a forward pass leaves its truncated input spectrum: the slot of the layer's stack, or None (a fresh tensor)"""
+    return None if stack is None else stack[0].X[stack[1]]
+
+
+def _xt_dest(stack, B, Ci, m1, m2, device):
+    slot = _xt_slot(stack)
+    return torch.empty((B, Ci, 2 * m1, m2), dtype=torch.complex64, device=device) if slot is None else slot
+
+
+def _block_prologue(ctx, iw, x, Ci, w1, w2, cw, cb, Ho, Wo, half_weights):
+    """Common start of the block Functions' forward (x: the plain first source, Ci: all input channels, iw: position of w1 among the
+    inputs): takes the layer's stack slot (ctx.stack) -> (w1, w2 plain [as half-precision copies], cwm (Co, Ci), cb, same, mix_last)."""
+    B, _, H, W = x.shape
+    ctx.stack = _stack_take(w1, (B, Ci, 2 * w1.shape[2], w1.shape[3]), x.device, _stack_wanted(ctx, iw, x, half_weights))
+    w1, w2 = _plain(w1), _plain(w2)
+    if half_weights:                    # complex64 master weights, read through float16 (re, im) copies
+        w1, w2 = _half_weights(w1, w2)
+    cwm = _plain(cw).reshape(cw.shape[0], Ci)
+    cb = None if cb is None else _plain(cb)
+    same = (H, W) == (Ho, Wo)
+    return w1, w2, cwm, cb, same, same or Ho * Wo < H * W          # the 1x1 convolution runs on whichever side has fewer pixels
+
+
+def _pointwise_input_grads(g_src, w, C1, gx1, gx2, geom, dgelu_of=None, dgelu_total=False, g_act=None):
+    """The point-wise branch's part of the input gradient(s), ACCUMULATED into gx1 (B, C1, H, W) - the columns [:C1] of w (Co, Ci) -
+    and gx2 (the other columns); None: not wanted.  g_src (B, Co, P) is the gradient at the 1x1 convolution's output;
+    geom = (H, W, Ho, Wo, same, mix_last).  The transposed channel mix accumulates into the destinations - both from one launch
+    where _mix2_input_grads' split rule allows - except in a block that resampled BEFORE the mix (mix_last and not same): there
+    it writes fresh tensors on the output grid, whose adjoint resampling accumulates (g_act: gx1's, where the caller has mixed it
+    already).  dgelu_of / dgelu_total: channel_mix's, on gx1 (accumulating mix only)."""
+    H, W, Ho, Wo, same, mix_last = geom
+    B = g_src.shape[0]
+    direct = same or not mix_last
+
+    def dest(gx):
+        return gx.view(B, gx.shape[1], -1) if direct else None
+
+    g1, g2 = g_act, None
+    if gx1 is not None and gx2 is not None:
+        g1, g2 = _mix2_input_grads(g_src, w, C1, out1=dest(gx1), out2=dest(gx2))
+    else:
+        if gx1 is not None and g1 is None:
+            g1 = _native.channel_mix(g_src, w if C1 == w.shape[1] else w[:, :C1].contiguous(), None, transpose_w=True, out=dest(gx1),
+                                     dgelu_of=dgelu_of, dgelu_total=dgelu_total)
+        if gx2 is not None:
+            g2 = _native.channel_mix(g_src, w[:, C1:].contiguous(), None, transpose_w=True, out=dest(gx2))
+    if not direct:
+        for g, gx in ((g1, gx1), (g2, gx2)):
+            if gx is not None:
+                resample_adjoint(g.view(B, gx.shape[1], Ho, Wo), H, W, out=gx)
+
+
 class _SpectralConv2dFn(torch.autograd.Function):
     """y = irfft2(corner-mix(rfft2(x)));  saves only the truncated input spectrum."""
 
@@ -44,7 +97,7 @@ class _SpectralConv2dFn(torch.autograd.Function):
         w1, w2 = _plain(w1), _plain(w2)
         if half_weights:                    # complex64 master weights, read through float16 (re, im) copies
             w1, w2 = _half_weights(w1, w2)
-        y, xt = _native.spectral_conv2d_forward(x, w1, w2, int(Ho), int(Wo), xt_out=None if ctx.stack is None else ctx.stack[0].X[ctx.stack[1]])
+        y, xt = _native.spectral_conv2d_forward(x, w1, w2, int(Ho), int(Wo), xt_out=_xt_slot(ctx.stack))
         ctx.save_for_backward(xt, w1, w2)
         ctx.in_hw = (x.shape[-2], x.shape[-1])
         return y
@@ -160,15 +213,8 @@ class _OperatorBlock2dFn(torch.autograd.Function):
                 ctx.join = join
         x = _plain(x)
         B, Ci, H, W = x.shape
-        ctx.stack = _stack_take(w1, (B, Ci, 2 * w1.shape[2], w1.shape[3]), x.device, _stack_wanted(ctx, 1, x, half_weights))
-        w1, w2 = _plain(w1), _plain(w2)
-        if half_weights:
-            w1, w2 = _half_weights(w1, w2)
         Co = cw.shape[0]
-        cwm = _plain(cw).reshape(Co, Ci)
-        cb = None if cb is None else _plain(cb)
-        same = (H, W) == (Ho, Wo)
-        mix_last = same or Ho * Wo < H * W          # the 1x1 convolution runs on whichever side has fewer pixels
+        w1, w2, cwm, cb, same, mix_last = _block_prologue(ctx, 1, x, Ci, w1, w2, cw, cb, Ho, Wo, half_weights)
         t = fused = None
         if not mix_last and not half_weights and x.dtype == torch.float32:
             # up-sampling block: the 1x1 convolution first, its result joins the inverse transform's (one pass over the output)
@@ -176,7 +222,7 @@ class _OperatorBlock2dFn(torch.autograd.Function):
             fused = _fused_addend(t, Ho, Wo, w1.shape[2], w1.shape[3], False)
         if fused is not None:
             m1, m2 = w1.shape[2], w1.shape[3]
-            xt = torch.empty((B, Ci, 2 * m1, m2), dtype=torch.complex64, device=x.device) if ctx.stack is None else ctx.stack[0].X[ctx.stack[1]]
+            xt = _xt_dest(ctx.stack, B, Ci, m1, m2, x.device)
             _native.dft2d_forward(x, m1, m2, 1.0 / (H * W), out=xt, channel_offset=0)
             O = _native.mode_mix(xt.view(B, Ci, 2, m1 * m2), [w1, w2], 0)
             s = _native.dft2d_inverse(O.view(B, Co, 2 * m1, m2), Ho, Wo, 1.0, True, True, addend=fused)
@@ -186,7 +232,7 @@ class _OperatorBlock2dFn(torch.autograd.Function):
                 # the resampling kernel (K7) runs right BEFORE the forward transform (K1) that reads the same tensor: the two walk the
                 # images in opposite order (launch alternation), so what K7 read last is still cached when K1 starts
                 pre_act = resample_forward(x, Ho, Wo)
-            s, xt = _native.spectral_conv2d_forward(x, w1, w2, Ho, Wo, xt_out=None if ctx.stack is None else ctx.stack[0].X[ctx.stack[1]])
+            s, xt = _native.spectral_conv2d_forward(x, w1, w2, Ho, Wo, xt_out=_xt_slot(ctx.stack))
         out = s
         if fused is not None:
             act = x
@@ -253,31 +299,18 @@ class _OperatorBlock2dFn(torch.autograd.Function):
         xpre = join.pre if (join is not None and need_gx) else None
         own_last = xpre is not None and not join.pending
         dg_view = xpre.view(B, Ci, -1) if own_last else None
-        dg_done = False
-        if mix_last:
-            # forward: act = R x;  s += Wm act + b
-            if need_gx:
-                if same:
-                    _native.channel_mix(gs.view(B, Co, -1), cwm, None, transpose_w=True, out=gx.view(B, Ci, -1), dgelu_of=dg_view,
-                                        dgelu_total=own_last)
-                    dg_done = own_last
-                elif addend is None:
-                    if g_act is None:
-                        g_act = _native.channel_mix(gs.view(B, Co, -1), cwm, None, transpose_w=True).view(B, Ci, Ho, Wo)
-                    resample_adjoint(g_act, H, W, out=gx)
-            if need_gc:
-                gcw, gcb = _wgrad_into((lcw, lcb), gs.view(B, Co, -1), act.view(B, Ci, -1), None, ctx.needs_input_grad[3],
-                                       has_bias and ctx.needs_input_grad[4], stack=pstack)
-        else:
-            # forward: t = Wm x + b;  s += R t
-            if need_gx:
-                _native.channel_mix(g_t, cwm, None, transpose_w=True, out=gx.view(B, Ci, -1), dgelu_of=dg_view, dgelu_total=own_last)
-                dg_done = own_last
-            if need_gc:
-                gcw, gcb = _wgrad_into((lcw, lcb), g_t, act.view(B, Ci, -1), None, ctx.needs_input_grad[3],
-                                       has_bias and ctx.needs_input_grad[4], stack=pstack)
-        if gcw is not None:
-            gcw = gcw.view(cw_shape)
+        # forward: act = R x; s += Wm act + b (mix_last), or t = Wm x + b; s += R t.  Only the mix that accumulates into gx itself
+        # (no resampling after it) can apply gelu'
+        direct = same or not mix_last
+        g_src = gs.view(B, Co, -1) if mix_last else g_t
+        if need_gx and (direct or addend is None):
+            _pointwise_input_grads(g_src, cwm, Ci, gx, None, (H, W, Ho, Wo, same, mix_last), dgelu_of=dg_view if direct else None,
+                                   dgelu_total=own_last and direct, g_act=g_act)
+        dg_done = own_last and direct
+        if need_gc:
+            gcw, gcb = _wgrad_into((lcw, lcb), g_src, act.view(B, Ci, -1), None, ctx.needs_input_grad[3],
+                                   has_bias and ctx.needs_input_grad[4], stack=pstack)
+            gcw = None if gcw is None else gcw.view(cw_shape)
         if join is not None:
             if need_gx:
                 # the point-wise contributions of x's other consumer accumulate into this buffer (the last one applies gelu'(pre))
@@ -305,19 +338,12 @@ class _OperatorBlock2dCatFn(torch.autograd.Function):
         B, C1, H, W = x1.shape
         C2 = x2.shape[1]
         Ci, Co, m1, m2 = w1.shape
-        ctx.stack = _stack_take(w1, (B, Ci, 2 * m1, m2), x1.device, _stack_wanted(ctx, 2, x1, half_weights))
-        w1, w2 = _plain(w1), _plain(w2)
-        if half_weights:
-            w1, w2 = _half_weights(w1, w2)
-        cwm = _plain(cw).reshape(Co, Ci)
-        cb = None if cb is None else _plain(cb)
+        w1, w2, cwm, cb, same, mix_last = _block_prologue(ctx, 2, x1, Ci, w1, w2, cw, cb, Ho, Wo, half_weights)
         # spectral branch, stage by stage (the composite entry point takes a single source)
-        xt = torch.empty((B, Ci, 2 * m1, m2), dtype=torch.complex64, device=x1.device) if ctx.stack is None else ctx.stack[0].X[ctx.stack[1]]
+        xt = _xt_dest(ctx.stack, B, Ci, m1, m2, x1.device)
         _native.dft2d_forward(x1, m1, m2, 1.0 / (H * W), out=xt, channel_offset=0)
         _native.dft2d_forward(x2, m1, m2, 1.0 / (H * W), out=xt, channel_offset=C1)
         O = _native.mode_mix(xt.view(B, Ci, 2, m1 * m2), [w1, w2], 0)
-        same = (H, W) == (Ho, Wo)
-        mix_last = same or Ho * Wo < H * W
         t = fused = None
         if not mix_last and not half_weights and x1.dtype == torch.float32:
             # up-sampling block: the 1x1 convolution first, its result joins the inverse transform's (one pass over the output)
@@ -371,48 +397,19 @@ class _OperatorBlock2dCatFn(torch.autograd.Function):
             elif need2:
                 gx2 = _native.dft2d_inverse(gX, H, W, 1.0 / (H * W), False, False, channels=C2, channel_offset=C1, dtype=gs.dtype)
         gcw = gcb = None
-        both = gx1 is not None and gx2 is not None
+        geom = (H, W, Ho, Wo, same, mix_last)
         if defer is not None:
-            # point-wise part of x2's gradient: accumulated into the joined buffer later; x1's part now
+            # point-wise part of x2's gradient: accumulated into the joined buffer later (where its mix accumulates itself it can
+            # apply the owner's gelu'); x1's part now
             cw2 = cwm[:, C1:].contiguous()
-            def mix_into(out, dg=None):
-                _native.channel_mix(g_src, cw2, None, transpose_w=True, out=out.view(B, C2, -1),
-                                    dgelu_of=None if dg is None else dg.view(B, C2, -1), dgelu_total=dg is not None)
-            if mix_last and not same:
-                defer.pending.append((lambda out: resample_adjoint(
-                    _native.channel_mix(g_src, cw2, None, transpose_w=True).view(B, C2, Ho, Wo), H, W, out=out), False))
-            else:
-                defer.pending.append((mix_into, True))
-            if gx1 is not None:
-                cw1 = cwm[:, :C1].contiguous()
-                if mix_last and not same:
-                    resample_adjoint(_native.channel_mix(g_src, cw1, None, transpose_w=True).view(B, C1, Ho, Wo), H, W, out=gx1)
-                else:
-                    _native.channel_mix(g_src, cw1, None, transpose_w=True, out=gx1.view(B, C1, -1))
-        elif mix_last:
-            if both and same:
-                _mix2_input_grads(g_src, cwm, C1, out1=gx1.view(B, C1, -1), out2=gx2.view(B, C2, -1))
-            elif both:
-                g_a1, g_a2 = _mix2_input_grads(g_src, cwm, C1)
-                resample_adjoint(g_a1.view(B, C1, Ho, Wo), H, W, out=gx1)
-                resample_adjoint(g_a2.view(B, C2, Ho, Wo), H, W, out=gx2)
-            else:
-                for gx, cwx, Cx in ((gx1, cwm[:, :C1], C1), (gx2, cwm[:, C1:], C2)):
-                    if gx is None:
-                        continue
-                    if same:
-                        _native.channel_mix(g_src, cwx.contiguous(), None, transpose_w=True, out=gx.view(B, Cx, -1))
-                    else:
-                        g_act = _native.channel_mix(g_src, cwx.contiguous(), None, transpose_w=True)
-                        resample_adjoint(g_act.view(B, Cx, Ho, Wo), H, W, out=gx)
+
+            def x2_part(out, dg=None):
+                _pointwise_input_grads(g_src, cw2, C2, out, None, geom, dgelu_of=None if dg is None else dg.view(B, C2, -1),
+                                       dgelu_total=dg is not None)
+            defer.pending.append((x2_part, same or not mix_last))
+            _pointwise_input_grads(g_src, cwm, C1, gx1, None, geom)
         else:
-            if both:
-                _mix2_input_grads(g_src, cwm, C1, out1=gx1.view(B, C1, -1), out2=gx2.view(B, C2, -1))
-            else:
-                if gx1 is not None:
-                    _native.channel_mix(g_src, cwm[:, :C1].contiguous(), None, transpose_w=True, out=gx1.view(B, C1, -1))
-                if gx2 is not None:
-                    _native.channel_mix(g_src, cwm[:, C1:].contiguous(), None, transpose_w=True, out=gx2.view(B, C2, -1))
+            _pointwise_input_grads(g_src, cwm, C1, gx1, gx2, geom)
         if need_gc:
             gcw, gcb = _wgrad_into((lcw, lcb), g_src, a1.view(B, C1, -1), a2.view(B, C2, -1), ctx.needs_input_grad[4],
                                    has_bias and ctx.needs_input_grad[5])

@@ -31,7 +31,7 @@ static int dft2d(bool inverse, const float* in, float* out, int n_img, int H, in
     if (n_img == 0) return 0;
     Dft2dParams p;
     p.in = in; p.out = out; p.n_img = n_img; p.H = H; p.W = W; p.m1 = m1; p.m2 = m2;
-    p.scale = scale; p.herm = herm ? 1 : 0; p.mask = mask ? 1 : 0; p.bf16 = bf16 ? 1 : 0; p.rowfreq = nullptr; p.nw = 1; p.exp = 0; p.accumulate = 0; p.act_out = nullptr;
+    p.scale = scale; p.herm = herm ? 1 : 0; p.mask = mask ? 1 : 0; p.bf16 = bf16 ? 1 : 0;
     if (sp_group <= 0) { sp_group = n_img; sp_stride = 0; sp_offset = 0; }          // plain layout: spectrum i of image i
     if (sp_offset < 0 || sp_stride < sp_offset + sp_group || n_img % sp_group) {
         if (!(sp_stride == 0 && sp_offset == 0 && sp_group == n_img)) {
@@ -183,9 +183,8 @@ int uno_dft2d_inverse(const float* spec, float* images, int n_img, int H, int W,
 int uno_dft2d_inverse_add_applies(int n_img, int H, int W, int m1, int m2, int Hs, int Ws) {
     if (n_img < 1 || H < 1 || W < 1 || m1 < 1 || m2 < 1 || Hs < 1 || Ws < 1 || m1 > H || m2 > W / 2 + 1 || m1 > 40 || m2 > 48) return 0;
     Dft2dParams p;
-    p.in = nullptr; p.out = nullptr; p.n_img = n_img; p.H = H; p.W = W; p.m1 = m1; p.m2 = m2; p.scale = 1.f; p.herm = 1; p.mask = 1;
-    p.bf16 = 0; p.rowfreq = nullptr; p.nw = 1; p.exp = 0; p.accumulate = 0; p.act_out = nullptr;
-    p.sp_group = n_img; p.sp_stride = 0; p.sp_offset = 0; p.twH = nullptr; p.twW = nullptr;
+    p.n_img = n_img; p.H = H; p.W = W; p.m1 = m1; p.m2 = m2; p.herm = 1; p.mask = 1;
+    p.sp_group = n_img; p.sp_stride = 0;
     p.add_Hs = Hs; p.add_Ws = Ws;
     if (dft2d_inv_plane_applies(p)) return 0;           // (many small images take the plane-batched kernels)
     return dft2d_inv_add_applies(p) ? 1 : 0;
@@ -206,9 +205,8 @@ int uno_dft2d_inverse_add(const float* spec, float* images, int n_img, int H, in
     }
     Dft2dParams p;
     p.in = spec; p.out = images; p.n_img = n_img; p.H = H; p.W = W; p.m1 = m1; p.m2 = m2;
-    p.scale = scale; p.herm = hermitian_cols ? 1 : 0; p.mask = mask_overlap ? 1 : 0; p.bf16 = 0; p.rowfreq = nullptr; p.nw = 1; p.exp = 0;
-    p.accumulate = 0; p.act_out = nullptr;
-    p.sp_group = n_img; p.sp_stride = 0; p.sp_offset = 0;
+    p.scale = scale; p.herm = hermitian_cols ? 1 : 0; p.mask = mask_overlap ? 1 : 0;
+    p.sp_group = n_img; p.sp_stride = 0;
     p.twH = twiddle_table(H);
     p.twW = twiddle_table(W);
     if (!p.twH || !p.twW) return -6;
@@ -319,7 +317,7 @@ int uno_cdft_axis(const float* in, float* out, int inverse, int n_img, int H, in
     if (!in || !out) { set_error("uno_cdft_axis: null pointer"); return -1; }
     CdftParams p;
     p.in = in; p.out = out; p.n_img = n_img; p.H = H; p.C = 2 * m2 * m3; p.m1 = m1; p.m2 = m2; p.m3 = m3;
-    p.scale = scale; p.mask = mask_overlap ? 1 : 0; p.rowfreq = nullptr;
+    p.scale = scale; p.mask = mask_overlap ? 1 : 0;
     p.tw = twiddle_table(H);
     if (!p.tw) return -6;
     if (m1 > 40) return launch_cdft_generic(p, inverse != 0, (hipStream_t)stream);
@@ -353,15 +351,15 @@ static int fft_resample3d_impl(const float* x, float* y, void* ws, int n_vol, in
     float* Z2 = Z1 + 2LL * n_vol * D1 * C;                        // (n_vol * M1, J2, m3) c64
     float* S = Z2 + 2LL * n_vol * M1 * C;                         // (n_vol, 4, J1/2, J2/2, m3) c64
     Dft2dParams p;
-    p.n_img = n_vol * D1; p.H = D2; p.W = D3; p.m1 = J2 / 2; p.m2 = m3; p.scale = 1.0f; p.herm = herm_in ? 1 : 0; p.mask = 0; p.bf16 = 0; p.nw = 1; p.exp = 0; p.accumulate = 0; p.act_out = nullptr;
-    p.sp_group = p.n_img; p.sp_stride = 0; p.sp_offset = 0;
+    p.n_img = n_vol * D1; p.H = D2; p.W = D3; p.m1 = J2 / 2; p.m2 = m3; p.herm = herm_in ? 1 : 0;
+    p.sp_group = p.n_img; p.sp_stride = 0;
     p.in = x; p.out = Z1; p.rowfreq = f2_in;
     p.twH = twiddle_table(D2); p.twW = twiddle_table(D3);
     if (!p.twH || !p.twW) return -6;
     if (!dft2d_fwd_plane_applies(p)) { set_error("%s: input planes %d x %d (%d of them) are outside the plane-batched kernels' range", who, D2, D3, p.n_img); return -2; }
     if (int rc = launch_dft2d_fwd_plane(p, s)) return rc;
     CdftParams c;
-    c.n_img = n_vol; c.C = (int)C; c.m1 = J1 / 2; c.m2 = J2 / 2; c.m3 = m3; c.mask = 0; c.scale = 1.0f;
+    c.n_img = n_vol; c.C = (int)C; c.m1 = J1 / 2; c.m2 = J2 / 2; c.m3 = m3;
     c.in = Z1; c.out = S; c.H = D1; c.rowfreq = f1_in; c.tw = twiddle_table(D1);
     if (!c.tw) return -6;
     if (int rc = launch_cdft(c, false, s)) return rc;

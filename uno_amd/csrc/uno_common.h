@@ -170,23 +170,23 @@ __device__ __forceinline__ int sweep_x(int rev) { return rev ? (int)(gridDim.x -
 __device__ __forceinline__ int sweep_y(int rev) { return rev ? (int)(gridDim.y - 1 - blockIdx.y) : (int)blockIdx.y; }
 
 struct Dft2dParams {
-    const float* in;        // forward: images (n_img, H, W) f32; inverse: spectra (n_img, 2*m1, m2) c64
-    float* out;             // forward: spectra; inverse: images
-    const float2* twH;      // (cos, sin)(2 pi n / H), n in [0, H)
-    const float2* twW;
-    int n_img, H, W, m1, m2;
-    float scale;            // applied to every spectrum entry
-    int herm;               // 1: multiply column l by the Hermitian weight c_l of W
-    int mask;               // 1: zero lo-corner rows overwritten by the hi corner (later-wins)
+    const float* in = nullptr;        // forward: images (n_img, H, W) f32; inverse: spectra (n_img, 2*m1, m2) c64
+    float* out = nullptr;             // forward: spectra; inverse: images
+    const float2* twH = nullptr;      // (cos, sin)(2 pi n / H), n in [0, H)
+    const float2* twW = nullptr;
+    int n_img = 0, H = 0, W = 0, m1 = 0, m2 = 0;
+    float scale = 1.f;      // applied to every spectrum entry
+    int herm = 0;           // 1: multiply column l by the Hermitian weight c_l of W
+    int mask = 0;           // 1: zero lo-corner rows overwritten by the hi corner (later-wins)
     // spectrum of image i lives at index (i / sp_group) * sp_stride + sp_offset + i % sp_group: a (B, C1) batch of
     // images can face channels [sp_offset, sp_offset + C1) of a (B, sp_stride) spectrum tensor (two-source blocks)
-    int sp_group, sp_stride, sp_offset;
-    int bf16;               // 1: the images (forward input / inverse output) are bfloat16; spectra stay complex64
-    const int* rowfreq;     // optional (plane-batched kernels only): frequency of spectrum row j, j < 2*m1, instead of the corner rule
-    int nw;                 // set by the K1 / K3 launchers: waves per image (a workgroup holds blockDim / (64 nw) images)
-    int exp;                // development: knock-out switches of the bf16-MFMA kernels (dft2d_b16.hip), 0 in production
-    int accumulate;         // plane-batched inverse only: out += result (the point-wise branch of OperatorBlock_3D lands in the spectral branch's buffer)
-    float* act_out;         // ... and, if set, act_out = gelu(out) is written in the same pass (blocks without normalisation)
+    int sp_group = 1, sp_stride = 1, sp_offset = 0;      // (the defaults: spectrum i at index i)
+    int bf16 = 0;           // 1: the images (forward input / inverse output) are bfloat16; spectra stay complex64
+    const int* rowfreq = nullptr;     // optional (plane-batched kernels only): frequency of spectrum row j, j < 2*m1, instead of the corner rule
+    int nw = 1;             // set by the K1 / K3 launchers: waves per image (a workgroup holds blockDim / (64 nw) images)
+    int exp = 0;            // development: knock-out switches of the bf16-MFMA kernels (dft2d_b16.hip), 0 in production
+    int accumulate = 0;     // plane-batched inverse only: out += result (the point-wise branch of OperatorBlock_3D lands in the spectral branch's buffer)
+    float* act_out = nullptr;         // ... and, if set, act_out = gelu(out) is written in the same pass (blocks without normalisation)
     // K3-A (dft2d_inv_add_kernel.h): out = transform + separable banded up-sampling of add_src (n_img, add_Hs, add_Ws); host-built operand
     // tables (uno_amd/resample.py): first source row of each 16-row tile, row operator [tile][3][64], first source column of each
     // (column tile, side), column operator [column tile][2][3][64]
@@ -222,26 +222,26 @@ struct ModeGemmParams {
 
 // Pruned complex DFT along the leading axis of (n_img, H, C) <-> corner-major (n_img, 4, m1, m2, m3).
 struct CdftParams {
-    const float* in;
-    float* out;
-    const float2* tw;       // twiddles of length H
-    int n_img, H, C, m1, m2, m3;
-    float scale;
-    int mask;               // zero lo-corner rows overwritten by the hi corner (on the spectrum side)
-    const int* rowfreq;     // optional: frequency of spectrum row j, j < 2*m1, instead of the corner rule
+    const float* in = nullptr;
+    float* out = nullptr;
+    const float2* tw = nullptr;       // twiddles of length H
+    int n_img = 0, H = 0, C = 0, m1 = 0, m2 = 0, m3 = 0;
+    float scale = 1.f;
+    int mask = 0;           // zero lo-corner rows overwritten by the hi corner (on the spectrum side)
+    const int* rowfreq = nullptr;     // optional: frequency of spectrum row j, j < 2*m1, instead of the corner rule
 };
 
 // One workgroup per (sample, channel) volume: all three pruned transforms of the 3-D layer (dft3d_volume.hip).
 struct Vol3dParams {
-    const float* in;        // forward: volumes (n_vol, D1, D2, D3) f32; inverse: corner-major spectra (n_vol, 4, m1, m2, m3) c64
-    float* out;
-    const float2* tw1;      // (cos, sin)(2 pi n / (2 D1)), n in [0, 2 D1): half-shifted frequencies and the e^{i pi h / D1} twist
-    const float2* tw2;      // ... of 2 D2
-    const float2* tw3;      // (cos, sin)(2 pi n / D3)
-    int n_vol, D1, D2, D3, m1, m2, m3;
-    float scale;
-    int herm;               // 1: multiply T-mode l by the Hermitian weight c_l of D3
-    const float* ctab;      // host-built operand table of the kernel (filled in by the launcher)
+    const float* in = nullptr;        // forward: volumes (n_vol, D1, D2, D3) f32; inverse: corner-major spectra (n_vol, 4, m1, m2, m3) c64
+    float* out = nullptr;
+    const float2* tw1 = nullptr;      // (cos, sin)(2 pi n / (2 D1)), n in [0, 2 D1): half-shifted frequencies and the e^{i pi h / D1} twist
+    const float2* tw2 = nullptr;      // ... of 2 D2
+    const float2* tw3 = nullptr;      // (cos, sin)(2 pi n / D3)
+    int n_vol = 0, D1 = 0, D2 = 0, D3 = 0, m1 = 0, m2 = 0, m3 = 0;
+    float scale = 1.f;
+    int herm = 0;           // 1: multiply T-mode l by the Hermitian weight c_l of D3
+    const float* ctab = nullptr;      // host-built operand table of the kernel (filled in by the launcher)
 };
 
 const float2* twiddle_table(int N);      // device-resident, cached per (device, N); nullptr on failure

@@ -32,8 +32,7 @@ from .block2d import _OperatorBlock2dCatFn, _OperatorBlock2dFn, _SpectralConv2dF
 from .pointwise import (GradJoin, _dev_act, channel_mix, channel_mix_cat, channel_mix_cat_project, gelu_channel_mix, gelu_channel_mix_pad,
                         gelu_pad2d, gelu_project, instance_norm_gelu, lift_gelu_pad)
 from .resample import resample2d_bicubic_aa
-from .spectral3d import (_FftResample3dAnyFn, _FftResample3dFn, _OperatorBlock3dFn, _resample3d_plan, _resample3d_plan_any, resample3d_any_applies,
-                         spectral_conv3d)
+from .spectral3d import (_FftResample3dAnyFn, _FftResample3dFn, _OperatorBlock3dFn, _resample3d_plan, _resample3d_plan_any, spectral_conv3d)
 
 __all__ = [
     "enable_mixed_precision", "enable_native_resample3d_any", "enable_one_buffer_any_grid", "GradJoin", "channel_mix_cat_project", "release_pass_state",
@@ -263,6 +262,17 @@ def enable_native_resample3d_any(module: nn.Module, enabled: bool = True) -> nn.
     return module
 
 
+def _resample3d_kernels(w, din, dout, device):
+    """Which resample kernels the point-wise layer `w` takes for din -> dout: (plan, any_grid) - the pruned-DFT plan (any_grid False),
+    inside its range; outside it the any-grid plan (True) where the layer is opted in and resample3d_any_applies holds; else
+    (None, False)."""
+    plan = _resample3d_plan(din, dout, device)
+    if plan is None and (getattr(w, "native_any_grid", False) or NATIVE_RESAMPLE3D_ANY):
+        plan = _resample3d_plan_any(din, dout, device)
+        return plan, plan is not None
+    return plan, False
+
+
 class pointwise_op_3D(nn.Module):
     """1x1x1 convolution + the reference's FFT crop/resample (quirks kept bug-for-bug: unnormalised
     forward transform, corners copied into an INPUT-sized zero spectrum, irfftn(s=output dims) that
@@ -296,11 +306,9 @@ class pointwise_op_3D(nn.Module):
         on_device = x.is_cuda and x.dtype == torch.float32 and x.dim() == 5
         out = channel_mix(x.contiguous(), self.conv.weight, self.conv.bias) if on_device else self.conv(x)
         if on_device:
-            plan = _resample3d_plan(out.shape[-3:], (dim1, dim2, dim3), out.device)
+            plan, any_grid = _resample3d_kernels(self, out.shape[-3:], (dim1, dim2, dim3), out.device)
             if plan is not None:
-                return _FftResample3dFn.apply(out, (dim1, dim2, dim3), plan)
-            if (getattr(self, "native_any_grid", False) or NATIVE_RESAMPLE3D_ANY) and resample3d_any_applies(out.shape[-3:], (dim1, dim2, dim3)):
-                return _FftResample3dAnyFn.apply(out, (dim1, dim2, dim3), _resample3d_plan_any(out.shape[-3:], (dim1, dim2, dim3), out.device))
+                return (_FftResample3dAnyFn if any_grid else _FftResample3dFn).apply(out, (dim1, dim2, dim3), plan)
         if on_device and not STOCK_FFT_RESAMPLE3D:
             # no silent dispatch to a stock library from a product component: the pruned-DFT resampling kernels do not cover this grid
             raise RuntimeError(
@@ -314,15 +322,12 @@ class pointwise_op_3D(nn.Module):
         if on_device:
             # the four corner copies into a zero spectrum == one multiplication by a 0 / 1 mask (same values bit for bit;
             # one pass forward and backward instead of zeros_like + 4 slice copies and their CopySlices backward chain)
-            out = torch.fft.irfftn(spec * self._corner_mask(spec, h1, h2, h3), s=(dim1, dim2, dim3))
-            return out
+            return torch.fft.irfftn(spec * self._corner_mask(spec, h1, h2, h3), s=(dim1, dim2, dim3))
         kept = torch.zeros_like(spec)
         for rows in (slice(None, h1), slice(-h1, None)):
             for cols in (slice(None, h2), slice(-h2, None)):
                 kept[:, :, rows, cols, :h3] = spec[:, :, rows, cols, :h3]
         out = torch.fft.irfftn(kept, s=(dim1, dim2, dim3))
-        if on_device:
-            return out
         return F.interpolate(out, size=(dim1, dim2, dim3), mode="trilinear", align_corners=True)
 
 
@@ -387,13 +392,9 @@ class OperatorBlock_3D(nn.Module):
             if (conv.dim1, conv.dim2, conv.dim3) != dims:
                 return None
         din = tuple(x.shape[-3:])
-        plan = _resample3d_plan(din, dims, x.device)
-        any_grid = plan is None
-        if any_grid:
-            if not ((getattr(self, "one_buffer_any_grid", False) or ONE_BUFFER_3D_ANY)
-                    and (getattr(w, "native_any_grid", False) or NATIVE_RESAMPLE3D_ANY) and resample3d_any_applies(din, dims)):
-                return None
-            plan = _resample3d_plan_any(din, dims, x.device)
+        plan, any_grid = _resample3d_kernels(w, din, dims, x.device)
+        if plan is None or (any_grid and not (getattr(self, "one_buffer_any_grid", False) or ONE_BUFFER_3D_ANY)):
+            return None
         if dim1 is not None:
             conv.dim1, conv.dim2, conv.dim3 = dim1, dim2, dim3
         gelu = self.non_lin and not self.normalize

@@ -55,52 +55,20 @@ def _kept_indices(n_in: int, n_out: int):
     return sorted(r for r in idx if r < min(n_in, n_out))
 
 
-_RESAMPLE3D_TABLES = {}
-
-
-def _resample3d_plan(din, dout, device):
-    """(f1, f2, m3) for _native.fft_resample3d, or None when the shape is outside the kernels' range (odd row counts, too many
-    rows or bins, planes too large): the caller then takes the any-grid kernels (_resample3d_plan_any) where it is opted in."""
-    key = (tuple(din), tuple(dout), str(device))
-    if key not in _RESAMPLE3D_TABLES:
-        plan = None
-        k1, k2 = _kept_indices(din[0], dout[0]), _kept_indices(din[1], dout[1])
-        m3 = min(dout[2] // 2, din[2] // 2 + 1)
-        ok = (len(k1) >= 2 and len(k1) % 2 == 0 and len(k1) <= 80 and len(k2) >= 2 and len(k2) % 2 == 0 and len(k2) <= 48
-              and 1 <= m3 <= 16 and 16 <= din[1] * din[2] <= 1792 and 16 <= dout[1] * dout[2] <= 1792
-              and din[2] <= 64 and dout[2] <= 64)
-        if ok:
-            t1 = _native.table_to_device(torch.tensor(k1, dtype=torch.int32), device)
-            t2 = _native.table_to_device(torch.tensor(k2, dtype=torch.int32), device)
-            plan = (t1, t2, m3)
-        _RESAMPLE3D_TABLES[key] = plan
-    return _RESAMPLE3D_TABLES[key]
-
-
-class _FftResample3dFn(torch.autograd.Function):
-    """irfftn(corner-copy(rfftn(x)), s=size) of pointwise_op_3D on the pruned-DFT kernels (K1p, K5, K6, K3p with explicit
-    frequency tables); backward is the transpose: the same kernels with sizes swapped and the Hermitian weights on the other side."""
-
-    @staticmethod
-    def forward(ctx, x, size, plan):
-        t1, t2, m3 = plan
-        ctx.plan, ctx.din, ctx.dout = plan, tuple(x.shape[-3:]), tuple(size)
-        scale = 1.0 / (size[0] * size[1] * size[2])
-        return _native.fft_resample3d(_plain(x), size, (t1, t1), (t2, t2), m3, scale, adjoint=False)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gy):
-        t1, t2, m3 = ctx.plan
-        scale = 1.0 / (ctx.dout[0] * ctx.dout[1] * ctx.dout[2])
-        return _native.fft_resample3d(_plain(gy), ctx.din, (t1, t1), (t2, t2), m3, scale, adjoint=True), None, None
-
-
 RESAMPLE3D_ANY_MAX_AXIS = 128       # the any-grid kernels keep whole (W, T) planes in LDS: every axis length in 2 ... 128
 
 
-def _any_modes3(din, dout):
+def _modes3(din, dout):
     return min(dout[2] // 2, din[2] // 2 + 1)
+
+
+def _resample3d_pruned_applies(din, dout) -> bool:
+    """True inside the pruned-DFT kernels' range: an even number of kept rows per complex axis (at most 80 / 48), at most 16 bins,
+    (W, T) planes of 16 ... 1792 elements with T <= 64."""
+    k1, k2 = _kept_indices(din[0], dout[0]), _kept_indices(din[1], dout[1])
+    return (len(k1) >= 2 and len(k1) % 2 == 0 and len(k1) <= 80 and len(k2) >= 2 and len(k2) % 2 == 0 and len(k2) <= 48
+            and 1 <= _modes3(din, dout) <= 16 and 16 <= din[1] * din[2] <= 1792 and 16 <= dout[1] * dout[2] <= 1792
+            and din[2] <= 64 and dout[2] <= 64)
 
 
 def resample3d_any_applies(din, dout) -> bool:
@@ -110,41 +78,60 @@ def resample3d_any_applies(din, dout) -> bool:
     if len(din) != 3 or len(dout) != 3 or not all(2 <= v <= RESAMPLE3D_ANY_MAX_AXIS for v in (*din, *dout)):
         return False
     k1, k2 = _kept_indices(din[0], dout[0]), _kept_indices(din[1], dout[1])
-    return len(k1) >= 1 and len(k2) >= 1 and 1 <= _any_modes3(din, dout) <= din[2] // 2 + 1
+    return len(k1) >= 1 and len(k2) >= 1 and 1 <= _modes3(din, dout) <= din[2] // 2 + 1
 
 
-_RESAMPLE3D_ANY_TABLES = {}
+_RESAMPLE3D_PLANS = {}
+
+
+def _cached_plan(any_grid: bool, din, dout, device):
+    """(f1, f2, m3) of the kernel family for din -> dout, or None outside its range (no device is touched then); the tables are cached
+    per (family, grids, device)."""
+    key = (any_grid, tuple(din), tuple(dout), str(device))
+    if key not in _RESAMPLE3D_PLANS:
+        plan = None
+        if (resample3d_any_applies if any_grid else _resample3d_pruned_applies)(din, dout):
+            t1 = _native.table_to_device(torch.tensor(_kept_indices(din[0], dout[0]), dtype=torch.int32), device)
+            t2 = _native.table_to_device(torch.tensor(_kept_indices(din[1], dout[1]), dtype=torch.int32), device)
+            plan = (t1, t2, _modes3(din, dout))
+        _RESAMPLE3D_PLANS[key] = plan
+    return _RESAMPLE3D_PLANS[key]
+
+
+def _resample3d_plan(din, dout, device):
+    """(f1, f2, m3) for _native.fft_resample3d, or None when the shape is outside the kernels' range (odd row counts, too many
+    rows or bins, planes too large): the caller then takes the any-grid kernels (_resample3d_plan_any) where it is opted in."""
+    return _cached_plan(False, din, dout, device)
 
 
 def _resample3d_plan_any(din, dout, device):
-    """(f1, f2, m3) for _native.fft_resample3d_any, or None when resample3d_any_applies says no; tables cached per (grids, device)."""
-    key = (tuple(din), tuple(dout), str(device))
-    if key not in _RESAMPLE3D_ANY_TABLES:
-        plan = None
-        if resample3d_any_applies(din, dout):
-            t1 = _native.table_to_device(torch.tensor(_kept_indices(din[0], dout[0]), dtype=torch.int32), device)
-            t2 = _native.table_to_device(torch.tensor(_kept_indices(din[1], dout[1]), dtype=torch.int32), device)
-            plan = (t1, t2, _any_modes3(din, dout))
-        _RESAMPLE3D_ANY_TABLES[key] = plan
-    return _RESAMPLE3D_ANY_TABLES[key]
+    """(f1, f2, m3) for _native.fft_resample3d_any, or None when resample3d_any_applies says no."""
+    return _cached_plan(True, din, dout, device)
 
 
-class _FftResample3dAnyFn(torch.autograd.Function):
-    """_FftResample3dFn on the any-grid kernels (K1a, K5a, K3a: any kept-row counts, axes of 2 ... 128); backward is the adjoint call."""
+class _FftResample3dFn(torch.autograd.Function):
+    """irfftn(corner-copy(rfftn(x)), s=size) of pointwise_op_3D on the pruned-DFT kernels (K1p, K5, K6, K3p with explicit
+    frequency tables); backward is the transpose: the same kernels with sizes swapped and the Hermitian weights on the other side."""
+    resample = staticmethod(_native.fft_resample3d)
 
     @staticmethod
     def forward(ctx, x, size, plan):
         t1, t2, m3 = plan
         ctx.plan, ctx.din, ctx.dout = plan, tuple(x.shape[-3:]), tuple(size)
         scale = 1.0 / (size[0] * size[1] * size[2])
-        return _native.fft_resample3d_any(_plain(x), size, (t1, t1), (t2, t2), m3, scale, adjoint=False)
+        return ctx._forward_cls.resample(_plain(x), size, (t1, t1), (t2, t2), m3, scale, adjoint=False)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gy):
         t1, t2, m3 = ctx.plan
         scale = 1.0 / (ctx.dout[0] * ctx.dout[1] * ctx.dout[2])
-        return _native.fft_resample3d_any(_plain(gy), ctx.din, (t1, t1), (t2, t2), m3, scale, adjoint=True), None, None
+        return ctx._forward_cls.resample(_plain(gy), ctx.din, (t1, t1), (t2, t2), m3, scale, adjoint=True), None, None
+
+
+class _FftResample3dAnyFn(_FftResample3dFn):
+    """_FftResample3dFn on the any-grid kernels (K1a, K5a, K3a: any kept-row counts, axes of 2 ... 128); backward is the adjoint call."""
+    resample = staticmethod(_native.fft_resample3d_any)
 
 
 class _OperatorBlock3dFn(torch.autograd.Function):
