@@ -250,7 +250,7 @@ def test_aborted_backward_leaves_gradient_buckets_and_pass_state_clean():
             def backward(ctx, g):
                 raise RuntimeError("boom")
         x = torch.ones(3, 6)
-        pg._PASSES[424242] = {"id": 424242, "acc": {}, "stacks": {}, "uses": {}, "born": 0.0}      # what a failed pass leaves behind
+        pg._PASSES[424242] = pg._Pass(424242, born=0.0)      # what a failed pass leaves behind
         with pytest.raises(RuntimeError, match="boom"):
             tr.step_with(lambda: lin2(Boom.apply(lin1(x))).sum())          # lin2's buckets are issued, then the pass dies
         g = tr.grads

@@ -74,8 +74,8 @@ def test_stale_backward_pass_entries_are_swept(monkeypatch):
     """a backward pass that raises never runs its final callback; its _PASSES entry must not live for ever."""
     import time
     pg._PASSES.clear()
-    pg._PASSES[123456] = {"id": 123456, "acc": {}, "stacks": {}, "uses": {}, "born": time.monotonic() - 2 * pg._STALE_PASS_SECONDS}
-    pg._PASSES[123457] = {"id": 123457, "acc": {}, "stacks": {}, "uses": {}, "born": time.monotonic()}
+    pg._PASSES[123456] = pg._Pass(123456, born=time.monotonic() - 2 * pg._STALE_PASS_SECONDS)
+    pg._PASSES[123457] = pg._Pass(123457, born=time.monotonic())
     assert pg._pass_state() is None            # outside a pass: sweeps
     assert 123456 not in pg._PASSES and 123457 in pg._PASSES
     pg._PASSES.clear()
@@ -87,7 +87,7 @@ def test_a_swept_pass_that_shows_up_again_raises(monkeypatch):
     import time
     pg._PASSES.clear()
     pg._SWEPT.clear()
-    pg._PASSES[777] = {"id": 777, "acc": {}, "stacks": {}, "uses": {}, "born": time.monotonic() - 2 * pg._STALE_PASS_SECONDS}
+    pg._PASSES[777] = pg._Pass(777, born=time.monotonic() - 2 * pg._STALE_PASS_SECONDS)
     assert pg._pass_state() is None and 777 in pg._SWEPT
     monkeypatch.setattr(pg, "_current_graph_task_id", lambda: 777)
     with pytest.raises(RuntimeError, match="was idle for more than"):
@@ -126,3 +126,133 @@ def test_private_autograd_entry_points_are_optional(monkeypatch):
     assert pg._graph_task_id() == -1 and pg._pass_state() is None
     p = torch.nn.Parameter(torch.zeros(3))
     assert pg._grad_plan(p, None) is None and pg._grad_targets([p]) is None
+
+
+# ---- the in-place gradient protocol itself (_grad_targets, _layer_grad_targets) through real backward passes on the CPU: a tiny
+# Function stands in for a layer, its backward writes the way the weight-gradient kernels do (copy_ for beta = 0, add_ for beta = 1)
+class _Scale(torch.autograd.Function):
+    """y = x * w + b.  `seen` receives what each backward call got from _grad_targets - as facts, not tensors: a reference to a
+    `returned` alias kept here would stop autograd from adopting it as .grad."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, seen):
+        ctx.save_for_backward(x)
+        ctx.leaves, ctx.seen = (w, b), seen
+        return x * w + b
+
+    @staticmethod
+    def backward(ctx, gy):
+        (x,) = ctx.saved_tensors
+        grads = (gy * x, gy.clone())
+        tg = pg._grad_targets(list(ctx.leaves))
+        if tg is None:
+            ctx.seen.append(None)
+            return None, grads[0], grads[1], None
+        for d, g in zip(tg.dest, grads):
+            if tg.accumulate:
+                d.add_(g)
+            else:
+                d.copy_(g)
+        ctx.seen.append({"accumulate": tg.accumulate, "dest": tg.dest,
+                         "returned": [None if r is None else (r is not d, r.data_ptr(), tuple(r.shape)) for r, d in zip(tg.returned, tg.dest)]})
+        return (None, *tg.returned, None)
+
+
+def _scale_pass(uses, buffers=False, seed=0):
+    """One backward pass through `uses` uses of one (w, b) pair -> (w, b, what each backward call saw, last use first)."""
+    g = torch.Generator().manual_seed(seed)
+    w, b = torch.nn.Parameter(torch.randn(5, 3, generator=g)), torch.nn.Parameter(torch.randn(5, 3, generator=g))
+    if buffers:
+        for p in (w, b):
+            p._uno_grad_buffer = torch.full_like(p, float("nan"))         # a first contribution overwrites: nothing of this survives
+    seen = []
+    loss = sum((_Scale.apply(torch.randn(5, 3, generator=g), w, b, seen) * torch.randn(5, 3, generator=g)).sum() for _ in range(uses))
+    loss.backward()
+    assert not pg._PASSES, "a finished backward pass left its state behind"
+    return w, b, seen
+
+
+@pytest.fixture
+def cpu_leaves(monkeypatch):
+    """lift the protocol's device requirement: CPU leaves take the in-place path"""
+    monkeypatch.setattr(pg, "_on_device", lambda p: True)
+    pg._PASSES.clear()
+
+
+@pytest.mark.parametrize("uses", [1, 2, 3])
+@pytest.mark.parametrize("buffers", [True, False])
+def test_grad_targets_first_and_later_contributions(cpu_leaves, monkeypatch, uses, buffers):
+    w, b, seen = _scale_pass(uses, buffers)
+    assert len(seen) == uses and all(s is not None for s in seen)
+    first = seen[0]
+    assert first["accumulate"] is False and len(first["dest"]) == 2
+    for p, d, r in zip((w, b), first["dest"], first["returned"]):
+        if buffers:
+            assert d is p._uno_grad_buffer
+            assert p.grad.data_ptr() == p._uno_grad_buffer.data_ptr()   # autograd adopted the alias: the gradient lives in the buffer
+        else:
+            assert d.shape == p.shape and d.dtype == p.dtype and d.data_ptr() != p.data_ptr()
+        assert r == (True, d.data_ptr(), tuple(d.shape))                # a tensor of its own on the same memory
+    for later in seen[1:]:
+        assert later["accumulate"] is True and later["returned"] == [None, None]
+        assert all(d is d0 for d, d0 in zip(later["dest"], first["dest"]))
+    monkeypatch.setattr(pg, "INPLACE_PARAM_GRADS", False)               # the same graph, summed by autograd
+    w_ref, b_ref, seen_ref = _scale_pass(uses, buffers)
+    assert seen_ref == [None] * uses
+    assert torch.equal(w.grad, w_ref.grad) and torch.equal(b.grad, b_ref.grad)
+
+
+def test_grad_targets_leave_a_parameter_that_has_a_grad_alone(cpu_leaves):
+    """accumulation across passes takes the ordinary path; one such parameter in a kernel call's list takes the others with it, and
+    nothing is recorded for them (a record without a write would hand the next call an accumulate flag over garbage)"""
+    w, b = torch.nn.Parameter(torch.ones(4)), torch.nn.Parameter(torch.ones(4))
+    w.grad = torch.full((4,), 2.0)
+    got = {}
+
+    class Probe(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x):
+            return x.clone()
+
+        @staticmethod
+        def backward(ctx, g):
+            got["alone"] = pg._grad_targets([w])
+            got["mixed"] = pg._grad_targets([w, b]), pg._grad_targets([b, w])
+            got["acc"] = dict(pg._pass_state().acc)
+            return g
+
+    Probe.apply(w * b).sum().backward()
+    assert got["alone"] is None and got["mixed"] == (None, None) and got["acc"] == {}
+    assert not pg._PASSES
+    assert torch.equal(w.grad, torch.full((4,), 3.0)) and torch.equal(b.grad, torch.ones(4))
+
+
+def test_layer_grad_targets_need_the_leaves_and_a_matching_bias(cpu_leaves):
+    w, b = torch.nn.Parameter(torch.zeros(6, 4, 1, 1)), torch.nn.Parameter(torch.zeros(6))
+    got = {}
+
+    class Probe(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x):
+            return x.clone()
+
+        @staticmethod
+        def backward(ctx, g):
+            got["none"] = [pg._layer_grad_targets(None, True), pg._layer_grad_targets(None, False),
+                           pg._layer_grad_targets((w, None), True),       # a bias gradient with nowhere to go
+                           pg._layer_grad_targets((w, b), False)]         # the bias gradient is not produced: the pair is not written together
+            got["acc"] = dict(pg._pass_state().acc)
+            lt = pg._layer_grad_targets((w, b), True)
+            got["first"] = (lt.accumulate, tuple(lt.out_w.shape), tuple(lt.out_b.shape), tuple(lt.gw.shape), tuple(lt.gb.shape),
+                            lt.gw.data_ptr() == lt.out_w.data_ptr(), lt.gb.data_ptr() == lt.out_b.data_ptr())
+            lt2 = pg._layer_grad_targets((w, b), True)
+            got["later"] = (lt2.accumulate, lt2.out_w is lt.out_w, lt2.out_b is lt.out_b, lt2.gw, lt2.gb)
+            return g
+
+    # outside a backward pass there is no in-place path at all
+    assert pg._layer_grad_targets((w, b), True) is None
+    Probe.apply(torch.zeros(2, requires_grad=True)).sum().backward()
+    assert got["none"] == [None] * 4 and got["acc"] == {}
+    assert got["first"] == (False, (6, 4, 1, 1), (6,), (6, 4), (6,), True, True)
+    assert got["later"] == (True, True, True, None, None)
+    assert not pg._PASSES

@@ -1,9 +1,14 @@
-"""In-place parameter gradients: the state of the backward passes in flight and the spectrum stacks that batch a spectral layer's
-weight gradient over its uses in one graph.  The only module that touches autograd's private entry points (the id of the running
-graph task, the engine's final-callback queue): the layers call _grad_targets, _stack_take, _stack_grad_slot, _stack_arrived,
-_note_use and release_pass_state and do not look inside the pass dictionaries."""
+"""In-place parameter gradients: what a gradient target is (_GradTargets, and _layer_grad_targets for the weight and optional bias of a
+1x1 layer), the state of the backward passes in flight (_Pass and its records) and the spectrum stacks that batch a spectral
+layer's weight gradient over its uses in one graph (_SpectrumStack; a forward pass holds a _StackSlot of it).  The only module
+that touches autograd's private entry points (the id of the running graph task, the engine's final-callback queue): the layers
+call _grad_targets, _layer_grad_targets, _stack_take, _stack_grad_slot, _stack_arrived, _note_use and release_pass_state, read
+the records' fields and do not look inside the pass state."""
 import threading
 import time
+import warnings
+from dataclasses import dataclass, field
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -20,11 +25,44 @@ from . import _native
 #     node): the kernel adds (beta = 1) into that same tensor and the backward returns None for the parameter.
 # A parameter that already HAS a .grad when the pass starts (accumulation across passes) takes the ordinary path.
 INPLACE_PARAM_GRADS = True
-# State of the backward passes in flight, keyed by autograd's graph-task id (a nested pass - re-entrant activation checkpointing,
-# torch.autograd.grad inside a hook - is its own task with its own state; the outer pass finds its state untouched when it resumes):
-#   acc:    id(parameter) -> [tensor its gradient is being summed in, parameter, contributions so far, touched by a nested pass]
-#   stacks: id(stack) -> (stack, weight leaves, weight shape, [slots whose gradient spectrum arrived in this pass])
-#   uses:   id(weights1 leaf) -> [leaf, [spectral-layer backward calls of this pass that did NOT go through a stack]]
+
+
+@dataclass(eq=False, slots=True)
+class _Summed:
+    """A parameter whose gradient this pass is summing in place."""
+    tensor: torch.Tensor        # where the gradient is being summed
+    param: torch.Tensor
+    count: int                  # contributions so far
+    nested: bool                # touched by a nested pass (see _end_of_pass)
+
+
+@dataclass(eq=False, slots=True)
+class _StackInFlight:
+    """A spectrum stack that a backward call of this pass has reached."""
+    stack: "_SpectrumStack"
+    leaves: tuple               # (weights1, weights2) leaves
+    wshape: tuple
+    slots: list                 # slots whose gradient spectrum arrived in this pass
+
+
+@dataclass(eq=False, slots=True)
+class _UseCount:
+    leaf: torch.Tensor          # weights1 leaf of a spectral layer
+    n: int                      # the layer's backward calls of this pass, stacked or not
+
+
+@dataclass(eq=False, slots=True)
+class _Pass:
+    """State of one backward pass in flight."""
+    id: int                                                 # autograd's graph-task id
+    born: float = field(default_factory=time.monotonic)
+    acc: dict = field(default_factory=dict)                 # id(parameter) -> _Summed
+    stacks: dict = field(default_factory=dict)              # id(stack) -> _StackInFlight
+    uses: dict = field(default_factory=dict)                # id(weights1 leaf) -> _UseCount
+
+
+# The backward passes in flight, keyed by autograd's graph-task id (a nested pass - re-entrant activation checkpointing,
+# torch.autograd.grad inside a hook - is its own task with its own state; the outer pass finds its state untouched when it resumes)
 _PASSES = {}
 _PASSES_LOCK = threading.Lock()
 _STALE_PASS_SECONDS = 3600.0
@@ -48,7 +86,7 @@ def _sweep_stale_passes():
     all (an hour in a debugger), it raises at its next contribution instead of training on a partial gradient (_SWEPT)."""
     now = time.monotonic()
     with _PASSES_LOCK:
-        for tid in [t for t, ps in _PASSES.items() if now - ps["born"] > _STALE_PASS_SECONDS]:
+        for tid in [t for t, ps in _PASSES.items() if now - ps.born > _STALE_PASS_SECONDS]:
             _PASSES.pop(tid, None)
             _SWEPT[tid] = now
         while len(_SWEPT) > 256:
@@ -69,7 +107,7 @@ def _graph_task_id() -> int:
 
 
 def _pass_state():
-    """The dictionaries of the running backward pass (registered with the engine on first use), or None outside a pass."""
+    """The _Pass of the running backward pass (registered with the engine on first use), or None outside a pass."""
     tid = _graph_task_id()
     if tid < 0:
         if _PASSES:
@@ -87,7 +125,7 @@ def _pass_state():
         with _PASSES_LOCK:
             ps = _PASSES.get(tid)
             if ps is None:
-                ps = _PASSES[tid] = {"id": tid, "acc": {}, "stacks": {}, "uses": {}, "born": time.monotonic()}
+                ps = _PASSES[tid] = _Pass(tid)
                 # final callbacks belong to the graph task that is current when they are queued: this one runs when THIS pass completes
                 _queue_callback(lambda: _end_of_pass(tid))
     return ps
@@ -104,30 +142,34 @@ def _end_of_pass(tid):
         ps = _PASSES.pop(tid, None)
     if ps is None:
         return
-    acc, stacks, uses = ps["acc"], ps["stacks"], ps["uses"]
-    for leaf, count in uses.values():
-        if not getattr(leaf, "_uno_nostack", False):
-            leaf._uno_uses = count[0]
-    for st, leaves, wshape, slots in stacks.values():
-        _stack_flush_partial(st, leaves, wshape, slots)
-    for t, param, count, nested in acc.values():
+    for use in ps.uses.values():
+        if not getattr(use.leaf, "_uno_nostack", False):
+            use.leaf._uno_uses = use.n
+    for fl in ps.stacks.values():
+        _stack_flush_partial(fl.stack, fl.leaves, fl.wshape, fl.slots)
+    for s in ps.acc.values():
         # nested: a pass that ran INSIDE this one gave the parameter a .grad of its own before this pass's AccumulateGrad ran; the
         # tensor summed here was then added to that .grad as a whole (complete: AccumulateGrad runs after every contribution)
-        if count[0] > 1 and not nested[0] and param.grad is not None and param.grad.data_ptr() != t.data_ptr():
+        if s.count > 1 and not s.nested and s.param.grad is not None and s.param.grad.data_ptr() != s.tensor.data_ptr():
             raise RuntimeError("uno_amd: a parameter's gradient was accumulated in place by the library's kernels, but autograd also "
                                "received gradients for it from other operations and replaced the buffer; set "
                                "uno_amd._param_grads.INPLACE_PARAM_GRADS = False for this model")
 
 
+def _on_device(p) -> bool:
+    """The kernels write device memory: only a parameter that lives there takes the in-place path."""
+    return p.is_cuda
+
+
 def _grad_plan(p, ps):
     """('acc', tensor): later contribution of this pass | ('new', registered buffer or None): first contribution | None: ordinary path"""
-    if not (INPLACE_PARAM_GRADS and _PASS_STATE_AVAILABLE) or not isinstance(p, torch.Tensor) or not p.is_leaf or not p.requires_grad or not p.is_cuda:
+    if not (INPLACE_PARAM_GRADS and _PASS_STATE_AVAILABLE) or not isinstance(p, torch.Tensor) or not p.is_leaf or not p.requires_grad or not _on_device(p):
         return None
     if ps is None:
         return None
-    acc = ps["acc"].get(id(p))
+    acc = ps.acc.get(id(p))
     if acc is not None:
-        return "acc", acc[0]
+        return "acc", acc.tensor
     if p.grad is not None:
         return None
     if len(_PASSES) > 1:
@@ -135,9 +177,9 @@ def _grad_plan(p, ps):
         # in place, its tensor - possibly the registered buffer - must not be overwritten by a beta = 0 write from here
         busy = False
         for other in list(_PASSES.values()):
-            rec = other["acc"].get(id(p)) if other is not ps else None
+            rec = other.acc.get(id(p)) if other is not ps else None
             if rec is not None:
-                rec[3][0] = True
+                rec.nested = True
                 busy = True
         if busy:
             return None
@@ -147,23 +189,54 @@ def _grad_plan(p, ps):
     return "new", buf
 
 
+class _GradTargets(NamedTuple):
+    """Where ONE kernel call writes the gradients of the parameters it produces together.  All or nothing: every parameter's plan
+    (_grad_plan) is a first contribution, or every one is a later contribution; otherwise there is no record (_grad_targets gives
+    None, nothing is noted in the pass state, and the caller takes the fresh-tensor path)."""
+    dest: tuple                 # the tensors the call writes, in the order of the parameters
+    accumulate: bool            # the call adds (a later contribution of the pass) instead of overwriting (the first)
+    returned: tuple             # what the backward hands autograd for each: an alias of dest on the first contribution, None later
+
+
 def _grad_targets(params):
-    """Targets of the parameters ONE kernel call writes together: all or nothing, one accumulate flag.
-    -> list of (destination tensor, accumulate flag, value to return to autograd) or None"""
+    """_GradTargets of the parameters ONE kernel call writes together, or None: ordinary path (see _GradTargets for the rule)."""
     ps = _pass_state()
     plans = [_grad_plan(p, ps) for p in params]
     if any(pl is None for pl in plans) or len({pl[0] for pl in plans}) != 1:
         return None
     if plans[0][0] == "acc":
         for p in params:
-            ps["acc"][id(p)][2][0] += 1
-        return [(pl[1], True, None) for pl in plans]
-    out = []
+            ps.acc[id(p)].count += 1
+        return _GradTargets(tuple(pl[1] for pl in plans), True, (None,) * len(plans))
+    dest = []
     for p, pl in zip(params, plans):
         buf = pl[1] if pl[1] is not None else torch.empty(p.shape, dtype=p.dtype, device=p.device)
-        ps["acc"][id(p)] = (buf, p, [1], [False])       # (tensor the gradient is summed in, parameter, contributions so far, nested)
-        out.append((buf, False, buf.view(buf.shape)))
-    return out
+        ps.acc[id(p)] = _Summed(buf, p, 1, False)
+        dest.append(buf)
+    return _GradTargets(tuple(dest), False, tuple(buf.view(buf.shape) for buf in dest))
+
+
+class _LayerGradTargets(NamedTuple):
+    """_GradTargets of the weight and optional bias of a 1x1 layer, as its kernels and its backward take them."""
+    out_w: torch.Tensor
+    out_b: Optional[torch.Tensor]       # None: the layer has no bias
+    accumulate: bool
+    gw: Optional[torch.Tensor]          # for autograd: viewed (Co, Ci) | None on a later contribution
+    gb: Optional[torch.Tensor]
+
+
+def _layer_grad_targets(leaves, has_bias):
+    """leaves = (weight leaf, bias leaf or None) of a 1x1 layer, or None; has_bias: the call produces the bias gradient.
+    -> _LayerGradTargets, or None: the leaves are unknown, the bias leaf's presence does not match has_bias (its gradient is not
+    wanted, or there is nowhere to put it), or _grad_targets gives none.  Not None: committed, the caller's kernel call writes them."""
+    if leaves is None or (leaves[1] is not None) != has_bias:
+        return None
+    tg = _grad_targets([leaves[0]] + ([leaves[1]] if has_bias else []))
+    if tg is None:
+        return None
+    gw = tg.returned[0]
+    return _LayerGradTargets(tg.dest[0], tg.dest[1] if has_bias else None, tg.accumulate,
+                             None if gw is None else gw.view(gw.shape[0], -1), tg.returned[1] if has_bias else None)
 
 
 # ---- weight gradient of a spectral layer that is used SEVERAL times in one graph (the 40-step roll-out of ns_train_2d.py:46-68
@@ -182,6 +255,14 @@ def _grad_targets(params):
 TIME_BATCHED_WGRAD = True
 
 
+class _PointwiseInfo(NamedTuple):
+    """The block's 1x1 convolution whose split-K partial sums a stack holds (_SpectrumStack.P)."""
+    Ci: int
+    Co: int
+    has_bias: bool
+    leaves: tuple               # (weight leaf, bias leaf or None)
+
+
 class _SpectrumStack:
     __slots__ = ("X", "G", "n", "sealed", "done", "version", "P", "Pinfo")
 
@@ -189,15 +270,26 @@ class _SpectrumStack:
         self.X = torch.empty((cap, *shape), dtype=torch.complex64, device=device)     # truncated input spectra, slot per use
         self.G = None               # truncated output-gradient spectra (allocated for the slots in use when the first one arrives)
         self.P = None               # (n, floats) split-K partial sums of the block's 1x1 convolution weight gradient, row per use
-        self.Pinfo = None           # (Ci, Co, has_bias, (weight leaf, bias leaf)) of those
+        self.Pinfo = None           # _PointwiseInfo of those
         self.n = 0                  # slots handed out
         self.sealed = False         # a backward pass has started on it: no new uses
         self.done = False           # its gradient has been produced: late backward calls (retain_graph) run on their own
         self.version = version
 
 
+class _StackSlot(NamedTuple):
+    """One use's place in its layer's stack."""
+    stack: _SpectrumStack
+    slot: int
+
+    @property
+    def xt(self):
+        """where the forward pass leaves this use's truncated input spectrum"""
+        return self.stack.X[self.slot]
+
+
 def _stack_take(leaf, shape, device, wanted):
-    """Forward pass of a spectral layer: (stack, slot) for this use's truncated input spectrum, or None (layer used once per pass,
+    """Forward pass of a spectral layer: _StackSlot for this use's truncated input spectrum, or None (layer used once per pass,
     no gradient wanted, stacking off)."""
     if not (TIME_BATCHED_WGRAD and wanted and INPLACE_PARAM_GRADS and _PASS_STATE_AVAILABLE) or not isinstance(leaf, torch.Tensor) or not leaf.is_leaf:
         return None
@@ -216,11 +308,13 @@ def _stack_take(leaf, shape, device, wanted):
         except (AttributeError, RuntimeError):
             return None
     st.n += 1
-    return st, st.n - 1
+    return _StackSlot(st, st.n - 1)
 
 
-def _stack_grad_slot(st, slot, Co):
-    """Backward pass: where K1 writes the truncated spectrum of this use's output gradient, or None when the stack is finished."""
+def _stack_grad_slot(use, Co):
+    """Backward pass of the use `use` (_StackSlot): where K1 writes the truncated spectrum of its output gradient, or None when the
+    stack is finished."""
+    st, slot = use
     if st.done:
         return None
     st.sealed = True
@@ -233,20 +327,25 @@ def _stack_grad_slot(st, slot, Co):
 def _stack_wgrad(st, lo, hi, leaves, wshape, in_place):
     xt, go = st.X[lo:hi].flatten(0, 1), st.G[lo:hi].flatten(0, 1)
     tg = _grad_targets(leaves) if in_place else None
-    gw1, gw2 = _native.mode_wgrad(xt, go, tuple(wshape[:4]), 2, out=[tg[0][0], tg[1][0]] if tg else None,
-                                  accumulate=bool(tg and tg[0][1]))
-    return (tg[0][2], tg[1][2]) if tg else (gw1, gw2)
+    gw1, gw2 = _native.mode_wgrad(xt, go, tuple(wshape[:4]), 2, out=tg.dest if tg else None, accumulate=bool(tg and tg.accumulate))
+    return tg.returned if tg else (gw1, gw2)
 
 
-def _stack_arrived(st, slot, leaves, wshape, in_place):
-    """This use's gradient spectrum is in its slot.  -> (gw1, gw2) when it was the last of the stack's uses, else (None, None)."""
+def _count_use(ps, leaf):
+    ps.uses.setdefault(id(leaf), _UseCount(leaf, 0)).n += 1
+
+
+def _stack_arrived(use, leaves, wshape, in_place):
+    """The gradient spectrum of the use `use` (_StackSlot) is in its slot.  -> (gw1, gw2) when it was the last of the stack's uses,
+    else (None, None)."""
+    st, slot = use
     ps = _pass_state()
-    ps["uses"].setdefault(id(leaves[0]), [leaves[0], [0]])[1][0] += 1      # every use of the pass counts: the next stacks hold them all
-    rec = ps["stacks"].setdefault(id(st), (st, leaves, wshape, []))
-    rec[3].append(slot)
-    if len(rec[3]) < st.n:
+    _count_use(ps, leaves[0])                   # every use of the pass counts: the next stacks hold them all
+    rec = ps.stacks.setdefault(id(st), _StackInFlight(st, leaves, wshape, []))
+    rec.slots.append(slot)
+    if len(rec.slots) < st.n:
         return None, None
-    del ps["stacks"][id(st)]
+    del ps.stacks[id(st)]
     out = _stack_wgrad(st, 0, st.n, leaves, wshape, in_place)
     st.done, st.G = True, None
     return out
@@ -265,8 +364,9 @@ def _stack_pointwise(stack, leaves, gy, x1, x2, has_bias, act_x):
         if st.Pinfo is not None:
             return NotImplemented               # the stack's buffer has been consumed (late call on a retained graph)
         st.P = torch.empty((st.n, nf), dtype=torch.float32, device=gy.device)
-        st.Pinfo = (Ci, Co, has_bias, leaves)
-    fits = st.P.shape[1] == nf and st.Pinfo[:3] == (Ci, Co, has_bias)
+        st.Pinfo = _PointwiseInfo(Ci, Co, has_bias, leaves)
+    info = st.Pinfo
+    fits = st.P.shape[1] == nf and (info.Ci, info.Co, info.has_bias) == (Ci, Co, has_bias)
     if fits:
         _native.channel_wgrad2(gy, x1, x2, need_bias=has_bias, act_x=act_x, partials_out=st.P[slot])
     else:
@@ -274,16 +374,13 @@ def _stack_pointwise(stack, leaves, gy, x1, x2, has_bias, act_x):
     if not st.done:
         return (None, None) if fits else NotImplemented
     # the spectral half of this backward call completed the stack: every row is written
-    Ci0, Co0, hb0, lv = st.Pinfo
-    tg = _grad_targets([lv[0]] + ([lv[1]] if hb0 else []))
-    gw, gb = _native.channel_wgrad_finish(st.P, Ci0, Co0, hb0, out_w=tg[0][0] if tg else None,
-                                          out_b=tg[1][0] if (tg and hb0) else None, accumulate=bool(tg and tg[0][1]))
+    lt = _layer_grad_targets(info.leaves, info.has_bias)
+    gw, gb = _native.channel_wgrad_finish(st.P, info.Ci, info.Co, info.has_bias, out_w=lt.out_w if lt else None,
+                                          out_b=lt.out_b if lt else None, accumulate=bool(lt and lt.accumulate))
     st.P = None
     if not fits:
-        _native.channel_wgrad2(gy, x1, x2, need_bias=hb0, act_x=act_x, out_w=gw, out_b=gb, accumulate=True)
-    if tg:
-        gw, gb = (None if tg[0][2] is None else tg[0][2].view(Co0, Ci0)), (tg[1][2] if hb0 else None)
-    return gw, gb
+        _native.channel_wgrad2(gy, x1, x2, need_bias=info.has_bias, act_x=act_x, out_w=gw, out_b=gb, accumulate=True)
+    return (lt.gw, lt.gb) if lt else (gw, gb)
 
 
 def _runs(slots):
@@ -295,10 +392,16 @@ def _runs(slots):
             lo = k
 
 
+def _add_to_grad(p, g):
+    if p.grad is None:
+        p.grad = g
+    else:
+        p.grad.add_(g)
+
+
 def _stack_flush_partial(st, leaves, wshape, slots):
     """End of a pass that back-propagated only `slots` of the stack's uses: their weight gradient goes to .grad directly (the
     parameters' AccumulateGrad nodes have run), the remaining uses - if a later pass reaches them - run one by one."""
-    import warnings
     slots = sorted(slots)
     with torch.no_grad():
         tot = None
@@ -306,23 +409,16 @@ def _stack_flush_partial(st, leaves, wshape, slots):
             g = _stack_wgrad(st, lo, hi, leaves, wshape, False)
             tot = g if tot is None else (tot[0] + g[0], tot[1] + g[1])
         for p, g in zip(leaves, tot):
-            if p.grad is None:
-                p.grad = g
-            else:
-                p.grad.add_(g)
+            _add_to_grad(p, g)
         if st.P is not None:                    # the block's 1x1 convolution: second stage over the rows that were written
-            Ci0, Co0, hb0, lv = st.Pinfo
+            info = st.Pinfo
             ptot = None
             for lo, hi in _runs(slots):
-                g = _native.channel_wgrad_finish(st.P[lo:hi], Ci0, Co0, hb0)
-                ptot = g if ptot is None else (ptot[0] + g[0], (ptot[1] + g[1]) if hb0 else None)
-            for p, g in ((lv[0], ptot[0]), (lv[1] if hb0 else None, ptot[1])):
+                g = _native.channel_wgrad_finish(st.P[lo:hi], info.Ci, info.Co, info.has_bias)
+                ptot = g if ptot is None else (ptot[0] + g[0], (ptot[1] + g[1]) if info.has_bias else None)
+            for p, g in ((info.leaves[0], ptot[0]), (info.leaves[1] if info.has_bias else None, ptot[1])):
                 if p is not None:
-                    g = g.view(p.shape)
-                    if p.grad is None:
-                        p.grad = g
-                    else:
-                        p.grad.add_(g)
+                    _add_to_grad(p, g.view(p.shape))
             st.P = None
     st.done, st.G = True, None
     leaves[0]._uno_uses, leaves[0]._uno_nostack = 0, True
@@ -335,7 +431,7 @@ def _note_use(leaf):
     """A spectral layer's backward ran outside a stack: count it (what the next forward passes size their stack by)."""
     ps = _pass_state()
     if ps is not None and isinstance(leaf, torch.Tensor) and leaf.is_leaf:
-        ps["uses"].setdefault(id(leaf), [leaf, [0]])[1][0] += 1
+        _count_use(ps, leaf)
 
 
 def _stack_wanted(ctx, iw, x, half_weights):

@@ -35,7 +35,7 @@ def _half_weights(w1, w2):
 
 def _xt_slot(stack):
     """where a forward pass leaves its truncated input spectrum: the slot of the layer's stack, or None (a fresh tensor)"""
-    return None if stack is None else stack[0].X[stack[1]]
+    return None if stack is None else stack.xt
 
 
 def _xt_dest(stack, B, Ci, m1, m2, device):
@@ -136,10 +136,10 @@ def _stage_wgrad(stack, gslot, xt, gO, w1, w2, leaves, both_gw, need_gx):
     gradient; in `gslot` of the layer's stack when that took it).  -> (gX or None, gw1, gw2 as autograd should receive them): the
     input-gradient spectrum gX comes from the same launch when the caller needs it and the weights are complex64 (uno_mode_backward)."""
     if gslot is not None:
-        return (None, *_stack_arrived(stack[0], stack[1], leaves, w1.shape, both_gw))
+        return (None, *_stack_arrived(stack, leaves, w1.shape, both_gw))
     tg = _grad_targets(leaves) if both_gw else None
     _note_use(leaves[0])
-    out, acc = [tg[0][0], tg[1][0]] if tg else None, bool(tg and tg[0][1])
+    out, acc = (tg.dest, tg.accumulate) if tg else (None, False)
     gX = None
     if need_gx and w1.dtype == torch.complex64:
         gX, (gw1, gw2) = _native.mode_backward(xt, gO, [w1, w2], out=out, accumulate=acc)
@@ -147,18 +147,18 @@ def _stage_wgrad(stack, gslot, xt, gO, w1, w2, leaves, both_gw, need_gx):
     else:
         gw1, gw2 = _native.mode_wgrad(xt, gO, tuple(w1.shape[:4]), 2, out=out, accumulate=acc)
     if tg:
-        gw1, gw2 = tg[0][2], tg[1][2]
+        gw1, gw2 = tg.returned
     return gX, gw1, gw2
 
 
 def _spectral_backward(gs, xt, w1, w2, H, W, need_gx, need_gw, both_gw, leaves, stack, join=None, addend=None):
     """Backward of the spectral branch: -> (gx or None, gw1, gw2 as autograd should receive them, whether the layer's stack took the call).
-    leaves = (weights1, weights2) as the caller passed them (in-place gradient targets); stack = (stack, slot) of the forward pass
+    leaves = (weights1, weights2) as the caller passed them (in-place gradient targets); stack = the forward pass's _StackSlot
     or None; join: GradJoin whose deferred spectra are merged into this layer's before the inverse transform; addend: _fused_addend(...)
     of the point-wise branch's contribution to gx (float32 only) - the call then runs stage by stage."""
     B, Co = gs.shape[:2]
     Ci, _, m1, m2 = w1.shape[:4]
-    gslot = _stack_grad_slot(stack[0], stack[1], Co) if (stack is not None and need_gw) else None
+    gslot = _stack_grad_slot(stack, Co) if (stack is not None and need_gw) else None
     merging = join is not None and need_gx and bool(join.spectra)
     if addend is not None and not need_gx:
         raise RuntimeError("uno_amd: an addend for the input gradient needs the input gradient")
@@ -167,10 +167,9 @@ def _spectral_backward(gs, xt, w1, w2, H, W, need_gx, need_gw, both_gw, leaves, 
         if need_gw:
             _note_use(leaves[0])
         gx, gw1, gw2 = _native.spectral_conv2d_backward(gs, xt, w1, w2, H, W, need_gx=need_gx, need_gw=need_gw,
-                                                        gw_out=(tg[0][0], tg[1][0]) if tg else None,
-                                                        accumulate_gw=bool(tg and tg[0][1]))
+                                                        gw_out=tg.dest if tg else None, accumulate_gw=bool(tg and tg.accumulate))
         if tg:
-            gw1, gw2 = tg[0][2], tg[1][2]
+            gw1, gw2 = tg.returned
         return gx, gw1, gw2, False
     # stage by stage: the gradient spectrum goes to its slot of the layer's stack and / or the deferred gradient spectra of x's
     # other consumer are added to this layer's before ONE inverse transform
@@ -380,7 +379,7 @@ class _OperatorBlock2dCatFn(torch.autograd.Function):
         need_gc = ctx.needs_input_grad[4] or (has_bias and ctx.needs_input_grad[5])
         lw1, lw2, lcw, lcb = ctx.leaves
         both_gw = ctx.needs_input_grad[2] and ctx.needs_input_grad[3]
-        gslot = _stack_grad_slot(ctx.stack[0], ctx.stack[1], Co) if (ctx.stack is not None and need_gw) else None
+        gslot = _stack_grad_slot(ctx.stack, Co) if (ctx.stack is not None and need_gw) else None
         # gradient at the 1x1 convolution's output; the resampling runs right before the K1 that reads gs as well (_OperatorBlock2dFn.forward)
         g_src = gs.view(B, Co, -1) if mix_last else resample_adjoint(gs, H, W).view(B, Co, -1)
         gO = _native.dft2d_forward(gs, m1, m2, 1.0, True, True, out=gslot)             # c (.) keep (.) DFT_trunc(gs)

@@ -8,7 +8,7 @@ import torch.nn.functional as F
 from torch.autograd.function import once_differentiable
 
 from . import _native
-from ._param_grads import _grad_targets, _stack_pointwise
+from ._param_grads import _layer_grad_targets, _stack_pointwise
 
 
 # activation dtypes the device kernels take: float32 (the reference's contract) and bfloat16 (mixed precision, BASELINE.json
@@ -78,12 +78,12 @@ def channel_mix(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None
 def _wgrad_into(leaves, gy, x1, x2, need_w, need_b, act_x=False, stack=None, window=None):
     """Weight / bias gradient of a channel-mix layer (K9), written in place where the layer's leaf parameters allow it.
     leaves = (weight leaf, bias leaf or None) or None.  -> (gw or None shaped (Co, Ci), gb or None) to return to autograd.
-    stack = (stack, slot) of the block's spectral layer when that is batching its weight gradient over the uses of the pass: the
+    stack = the _StackSlot of the block's spectral layer when that is batching its weight gradient over the uses of the pass: the
     second stage of this gradient is deferred to the last use as well (_stack_pointwise).  window: see _native.channel_mix2."""
     if not (need_w or need_b):
         return None, None
     has_bias = need_b
-    tg = None
+    lt = None
     fused = x2 is None or (x1.shape[1] % 64 == 0 and gy.shape[2] >= 64)
     if window is not None:
         if not fused:
@@ -94,14 +94,12 @@ def _wgrad_into(leaves, gy, x1, x2, need_w, need_b, act_x=False, stack=None, win
         out = _stack_pointwise(stack, leaves, gy, x1, x2, has_bias, act_x)
         if out is not NotImplemented:
             return out
-    if fused and leaves is not None and need_w and (leaves[1] is not None) == has_bias:
-        tg = _grad_targets([leaves[0]] + ([leaves[1]] if has_bias else []))        # committed: the call below writes them
-    if tg is not None:
-        _native.channel_wgrad2(gy, x1, x2, need_bias=has_bias, act_x=act_x, out_w=tg[0][0], out_b=tg[1][0] if has_bias else None,
-                               accumulate=tg[0][1], window=window)
-        Co, Ci = gy.shape[1], x1.shape[1] + (x2.shape[1] if x2 is not None else 0)
-        gw = None if tg[0][2] is None else tg[0][2].view(Co, Ci)
-        return gw, (tg[1][2] if has_bias else None)
+    if fused and need_w:
+        lt = _layer_grad_targets(leaves, has_bias)        # committed: the call below writes them
+    if lt is not None:
+        _native.channel_wgrad2(gy, x1, x2, need_bias=has_bias, act_x=act_x, out_w=lt.out_w, out_b=lt.out_b, accumulate=lt.accumulate,
+                               window=window)
+        return lt.gw, lt.gb
     if window is not None:
         return _native.channel_wgrad2(gy, x1, x2, need_bias=has_bias, act_x=act_x, window=window)
     if x2 is None:
@@ -243,6 +241,20 @@ def _mix2_wgrad(gy, x1, x2, need_bias, act_x=False):
     return torch.cat([gw1, gw2], dim=1), gb
 
 
+def _clear_window_border(g, window):
+    """What a windowed kernel did not write of the planes of g (B, C, pixels): the columns right of the window, the rows below it (a
+    gradient's consumers - the transforms and resampling of the producing block - read whole planes).  -> g"""
+    rows, cols, pitch = window
+    _native.clear_border(g.view(g.shape[0], g.shape[1], -1, pitch), rows, cols)
+    return g
+
+
+def _first_source_grad(ctx, x1, w, gy, window=None):
+    """W[:, :C1]^T gy [* gelu'(x1)]: the gradient of the first source of a two-source layer, from a launch of its own."""
+    return _native.channel_mix(gy, w[:, :x1.shape[1]].contiguous(), None, transpose_w=True, dgelu_of=x1 if ctx.gelu_first else None,
+                               window=window)
+
+
 class _ChannelMixCatFn(torch.autograd.Function):
     """y[b] = W . cat(a1[b], x2[b]) + bias without the concatenation: W[:, :C1] . a1 writes y, W[:, C1:] . x2
     accumulates into it; the input gradients come out as two contiguous tensors (no strided slices of a joint one).
@@ -280,7 +292,7 @@ class _ChannelMixCatFn(torch.autograd.Function):
         if ctx.defer is not None and ctx.defer.owner and ctx.needs_input_grad[1]:     # owner still pending: its backward has not run yet
             # x2's gradient is accumulated later into the buffer of x2's other consumer (GradJoin): no tensor, no sum
             if ctx.needs_input_grad[0]:
-                g1 = _native.channel_mix(gy, w[:, :C1].contiguous(), None, transpose_w=True, dgelu_of=x1 if ctx.gelu_first else None)
+                g1 = _first_source_grad(ctx, x1, w, gy)
             w2 = w[:, C1:].contiguous()
             B, C2 = x2.shape[0], x2.shape[1]
             ctx.defer.pending.append((lambda out, dg=None: _native.channel_mix(
@@ -289,7 +301,7 @@ class _ChannelMixCatFn(torch.autograd.Function):
         elif ctx.needs_input_grad[0] and ctx.needs_input_grad[1]:
             g1, g2 = _mix2_input_grads(gy, w, C1, dgelu_of=x1 if ctx.gelu_first else None)
         elif ctx.needs_input_grad[0]:
-            g1 = _native.channel_mix(gy, w[:, :C1].contiguous(), None, transpose_w=True, dgelu_of=x1 if ctx.gelu_first else None)
+            g1 = _first_source_grad(ctx, x1, w, gy)
         elif ctx.needs_input_grad[1]:
             g2 = _native.channel_mix(gy, w[:, C1:].contiguous(), None, transpose_w=True)
         if ctx.defer is not None and g2 is not None:        # the owner's backward came first after all
@@ -299,29 +311,21 @@ class _ChannelMixCatFn(torch.autograd.Function):
 
     @staticmethod
     def _backward_window(ctx, x1, x2, w, gy, window):
-        rows, cols, pitch = window
         C1 = x1.shape[1]
         B, C2 = x2.shape[0], x2.shape[1]
-        dg = x1 if ctx.gelu_first else None
-
-        def cleared(g):
-            # what the windowed kernel did not write: the columns right of the window, the rows below it (a gradient's consumers -
-            # the transforms and resampling of the producing block - read whole planes)
-            _native.clear_border(g.view(g.shape[0], g.shape[1], -1, pitch), rows, cols)
-            return g
-
         g1 = g2 = None
         deferred = ctx.defer is not None and ctx.defer.owner and ctx.needs_input_grad[1]
         if deferred and ctx.defer.accepts_extra and ctx.needs_input_grad[0] and C1 % 64 == 0 and not ctx.defer.extra:
             # x2 is the lift's output: both input gradients from ONE pass over gy (two destinations); x2's stays a tensor of its own,
             # valid on the window, that the lift's backward kernel adds to the owner's gradient as it reads the two (no border to clear:
             # that kernel reads the domain only)
-            g1, g2w = _native.channel_mix2(gy, None, w, None, transpose_w=True, split_out=C1, dgelu_of=dg, window=window)
-            cleared(g1)
+            g1, g2w = _native.channel_mix2(gy, None, w, None, transpose_w=True, split_out=C1, dgelu_of=x1 if ctx.gelu_first else None,
+                                           window=window)
+            _clear_window_border(g1, window)
             ctx.defer.extra.append((g2w, window))
         elif deferred:
             if ctx.needs_input_grad[0]:
-                g1 = cleared(_native.channel_mix(gy, w[:, :C1].contiguous(), None, transpose_w=True, dgelu_of=dg, window=window))
+                g1 = _clear_window_border(_first_source_grad(ctx, x1, w, gy, window), window)
             w2 = w[:, C1:].contiguous()
             # accumulates into the window of the other consumer's (whole-plane) gradient: nothing to clear.  NOT fusable: a fused
             # gelu'(pre) epilogue would reach the window only, and the border of the joined gradient holds the owner's own non-zero
@@ -330,9 +334,9 @@ class _ChannelMixCatFn(torch.autograd.Function):
                 gy, w2, None, transpose_w=True, out=out.view(B, C2, -1), window=window), False))
         else:
             if ctx.needs_input_grad[0]:
-                g1 = cleared(_native.channel_mix(gy, w[:, :C1].contiguous(), None, transpose_w=True, dgelu_of=dg, window=window))
+                g1 = _clear_window_border(_first_source_grad(ctx, x1, w, gy, window), window)
             if ctx.needs_input_grad[1]:
-                g2 = cleared(_native.channel_mix(gy, w[:, C1:].contiguous(), None, transpose_w=True, window=window))
+                g2 = _clear_window_border(_native.channel_mix(gy, w[:, C1:].contiguous(), None, transpose_w=True, window=window), window)
                 if ctx.defer is not None:        # the owner's backward came first after all
                     g2 = ctx.defer.late(g2)
         gw, gb = _wgrad_into(ctx.leaves, gy, x1, x2, ctx.needs_input_grad[2], ctx.has_bias and ctx.needs_input_grad[3], act_x=ctx.gelu_first,
@@ -388,25 +392,19 @@ class _ChannelMixCatProjectFn(torch.autograd.Function):
     def _backward_fused(ctx, x1, x2, w, y, w2, gout, mode):
         window = ctx.window
         need_b = ctx.has_bias and ctx.needs_input_grad[3]
-        Co, Ci = y.shape[1], x1.shape[1] + x2.shape[1]
-        tg = None
-        if ctx.leaves is not None and (ctx.leaves[1] is not None) == need_b:
-            tg = _grad_targets([ctx.leaves[0]] + ([ctx.leaves[1]] if need_b else []))        # committed: the call below writes them
+        lt = _layer_grad_targets(ctx.leaves, need_b)        # committed: the call below writes them
         g1, g2, gw, gb, gw2, gb2 = _native.project_backward(
             x1, x2, w, y, w2, gout, act_in=ctx.gelu_first, need_bias=need_b, need_bias2=ctx.has_b2 and ctx.needs_input_grad[5], window=window,
-            out_w=None if tg is None else tg[0][0], out_b=None if tg is None or not need_b else tg[1][0],
-            accumulate=False if tg is None else tg[0][1])
-        if tg is not None:
-            gw = None if tg[0][2] is None else tg[0][2].view(Co, Ci)
-            gb = tg[1][2] if need_b else None
+            out_w=None if lt is None else lt.out_w, out_b=None if lt is None else lt.out_b, accumulate=False if lt is None else lt.accumulate)
+        if lt is not None:
+            gw, gb = lt.gw, lt.gb
         if window is not None:
-            rows, cols, pitch = window
-            _native.clear_border(g1.view(g1.shape[0], g1.shape[1], -1, pitch), rows, cols)
+            _clear_window_border(g1, window)
             if mode == 2:
                 ctx.defer.extra.append((g2, window))        # (no border to clear: the lift's backward kernel reads the domain only)
                 g2 = None
             else:
-                _native.clear_border(g2.view(g2.shape[0], g2.shape[1], -1, pitch), rows, cols)
+                _clear_window_border(g2, window)
         return g1, g2, gw, gb, gw2, gb2, None, None, None, None
 
 
