@@ -298,6 +298,21 @@ long long uno_gelu_project_bwd_ws_bytes(int B, int C, long long P);
 int uno_gelu_project_backward(const float* pre, const float* w, const float* gout, float* gpre, float* gw, float* gb,
                               void* ws, int B, int C, long long P, void* stream);
 
+/* The projection over TWO sources (additive: the ABI version stays 14, no existing entry point changes).  The reference's UNO_P and
+ * UNO_S256 end in `x_fc1 = F.gelu(self.fc1(x_c6)); x_fc1 = torch.cat([x_fc1, x_fc], dim=3); x_out = self.fc2(x_fc1)`
+ * (navier_stokes_uno2d.py:121-125, 320-324) with x_fc = gelu(fc(x)), the first lift activation, and fc2 = Linear(C1 + C2, 1):
+ *   out[b][p] = bias[0] + sum_{c<C1} w[c] * gelu(pre[b][c][p]) + sum_{d<C2} w[C1+d] * f(s[b][d][p])
+ * pre (B, C1, P), s (B, C2, P), w (C1 + C2), out (B, P); f = gelu when act2 = 1 (s is kept pre-activation), the identity when
+ * act2 = 0; C1, C2 >= 1 and C1 + C2 <= 1024.  The concatenation is never built: each source is read once.
+ * backward: gpre = gelu'(pre) * w[c] * gout,  gs = f'(s) * w[C1+d] * gout (gs may be NULL: not written),
+ *   gw[e] = sum gout * (gelu(pre) | f(s)) for all C1 + C2 entries,  gb[0] = sum gout (gb may be NULL);
+ * ws: scratch of uno_gelu_project2_bwd_ws_bytes() bytes (fixed-order partial sums: two calls give the same bits).  Float32, dense. */
+int uno_gelu_project2_forward(const float* pre, const float* s, const float* w, const float* bias, float* out, int B, int C1, int C2,
+                              long long P, int act2, void* stream);
+long long uno_gelu_project2_bwd_ws_bytes(int B, int C1, int C2, long long P);
+int uno_gelu_project2_backward(const float* pre, const float* s, const float* w, const float* gout, float* gpre, float* gs, float* gw,
+                               float* gb, void* ws, int B, int C1, int C2, long long P, int act2, void* stream);
+
 /* The same three calls on a WINDOW of a wider plane (ABI 10).  The reference crops the domain padding before its last two layers
  * (darcy_flow_uno2d.py:125-131: `x_c5[..., :-padding, :-padding]`, then fc1 - GELU - fc2 on S x S points); here those layers read
  * the padded (S + pad)^2 tensors in place and touch the domain only: the pixel axis of the call is rows x cols logical pixels,

@@ -84,6 +84,9 @@ _SIGNATURES = {
     "uno_gelu_project_forward": (C.c_int, [_fp, _fp, _fp, _fp, _i, _i, C.c_longlong, _fp]),
     "uno_gelu_project_bwd_ws_bytes": (C.c_longlong, [_i, _i, C.c_longlong]),
     "uno_gelu_project_backward": (C.c_int, [_fp] * 7 + [_i, _i, C.c_longlong, _fp]),
+    "uno_gelu_project2_forward": (C.c_int, [_fp] * 5 + [_i, _i, _i, C.c_longlong, _i, _fp]),
+    "uno_gelu_project2_bwd_ws_bytes": (C.c_longlong, [_i, _i, _i, C.c_longlong]),
+    "uno_gelu_project2_backward": (C.c_int, [_fp] * 9 + [_i, _i, _i, C.c_longlong, _i, _fp]),
     "uno_gelu_pad": (C.c_int, [_fp, _fp, _fp] + [_i] * 6 + [_fp]),
     "uno_transpose_batched": (C.c_int, [_fp, _fp, _i, C.c_longlong, _i] + [C.c_longlong] * 4 + [_fp]),
     "uno_instnorm_forward": (C.c_int, [_fp] * 6 + [C.c_longlong, _i, C.c_longlong, C.c_float, _i, _fp]),
@@ -983,6 +986,51 @@ def gelu_project_backward(pre, w, gout, need_bias=True, window=None):
                 _stream(pre))
     _check(rc, "uno_gelu_project_backward")
     return gpre, gw, gb
+
+
+def _project2_operands(pre, s, w):
+    _require(pre, torch.float32, "pre")
+    _require(s, torch.float32, "s")
+    _require(w, torch.float32, "weight")
+    B, C1, P = pre.shape
+    if s.dim() != 3 or s.shape[0] != B or s.shape[2] != P:
+        raise RuntimeError(f"uno_amd: second source {tuple(s.shape)} does not match (batch, *, pixels) of {tuple(pre.shape)}")
+    C2 = s.shape[1]
+    if w.numel() != C1 + C2:
+        raise RuntimeError(f"uno_amd: weight has {w.numel()} entries for {C1} + {C2} channels")
+    return B, C1, C2, P
+
+
+def gelu_project2_forward(pre, s, w, bias=None, act2=False):
+    """pre (B, C1, P), s (B, C2, P) f32, w (C1 + C2,), bias (1,) or None -> out (B, P) = bias + sum_c w[c] gelu(pre[:, c])
+    + sum_d w[C1 + d] f(s[:, d]), f = gelu if act2 else the identity (K11, two-source form)."""
+    B, C1, C2, P = _project2_operands(pre, s, w)
+    if bias is not None:
+        _require(bias, torch.float32, "bias")
+    out = torch.empty((B, P), dtype=torch.float32, device=pre.device)
+    with torch.cuda.device(pre.device):
+        rc = lib().uno_gelu_project2_forward(_ptr(pre), _ptr(s), _ptr(w), _opt(bias), _ptr(out), B, C1, C2, P, 1 if act2 else 0, _stream(pre))
+    _check(rc, "uno_gelu_project2_forward")
+    return out
+
+
+def gelu_project2_backward(pre, s, w, gout, act2=False, need_gs=True, need_bias=True):
+    """-> gpre (B, C1, P), gs (B, C2, P) or None, gw (C1 + C2,), gb (1,) or None."""
+    B, C1, C2, P = _project2_operands(pre, s, w)
+    _require(gout, torch.float32, "grad_output")
+    if tuple(gout.shape) != (B, P):
+        raise RuntimeError("uno_amd: grad_output shape does not match (batch, pixels)")
+    L = lib()
+    gpre = torch.empty_like(pre)
+    gs = torch.empty_like(s) if need_gs else None
+    gw = torch.empty((C1 + C2,), dtype=torch.float32, device=pre.device)
+    gb = torch.empty((1,), dtype=torch.float32, device=pre.device) if need_bias else None
+    with torch.cuda.device(pre.device):
+        ws = torch.empty(max(1, L.uno_gelu_project2_bwd_ws_bytes(B, C1, C2, P)), dtype=torch.uint8, device=pre.device)
+        rc = L.uno_gelu_project2_backward(_ptr(pre), _ptr(s), _ptr(w), _ptr(gout), _ptr(gpre), _opt(gs), _ptr(gw), _opt(gb), _ptr(ws),
+                                          B, C1, C2, P, 1 if act2 else 0, _stream(pre))
+    _check(rc, "uno_gelu_project2_backward")
+    return gpre, gs, gw, gb
 
 
 class _DeviceView:

@@ -483,6 +483,44 @@ int uno_gelu_project_backward_bf16(const void* pre, const float* w, const void* 
     return gelu_project_backward_impl(pre, w, gout, gpre, gw, gb, ws, B, C, P, 1, stream);
 }
 
+// two-source form of K11 (float32, dense): entries [0, C1) of w go with gelu(pre), entries [C1, C1 + C2) with s (gelu(s) when act2)
+static bool gelu_project2_sizes(const char* who, int B, int C1, int C2, long long P, int act2) {
+    if (B < 0 || C1 < 1 || C2 < 1 || P < 0) { set_error("%s: bad sizes B=%d C1=%d C2=%d P=%lld", who, B, C1, C2, P); return false; }
+    if ((long long)C1 + C2 > 1024) { set_error("%s: C1 + C2 = %lld channels, at most 1024", who, (long long)C1 + C2); return false; }
+    if (act2 != 0 && act2 != 1) { set_error("%s: act2 is 0 or 1 (got %d)", who, act2); return false; }
+    return true;
+}
+
+int uno_gelu_project2_forward(const float* pre, const float* s, const float* w, const float* bias, float* out, int B, int C1, int C2,
+                              long long P, int act2, void* stream) {
+    if (!gelu_project2_sizes("uno_gelu_project2_forward", B, C1, C2, P, act2)) return -1;
+    if (B == 0 || P == 0) return 0;
+    if (!pre || !s || !w || !out) { set_error("uno_gelu_project2_forward: null pointer"); return -1; }
+    GeluProjectSecond two;
+    two.s = s; two.C1 = C1; two.act = act2;
+    return launch_gelu_project_fwd(pre, w, bias, out, B, C1 + C2, P, 0, (hipStream_t)stream, &two);
+}
+
+long long uno_gelu_project2_bwd_ws_bytes(int B, int C1, int C2, long long P) {
+    if (B < 1 || C1 < 1 || C2 < 1 || P < 1 || (long long)C1 + C2 > 1024) return 0;
+    return 4LL * gelu_project_ws_floats(B, C1 + C2, P);
+}
+
+int uno_gelu_project2_backward(const float* pre, const float* s, const float* w, const float* gout, float* gpre, float* gs, float* gw,
+                               float* gb, void* ws, int B, int C1, int C2, long long P, int act2, void* stream) {
+    if (!gelu_project2_sizes("uno_gelu_project2_backward", B, C1, C2, P, act2)) return -1;
+    if (!gw) { set_error("uno_gelu_project2_backward: null pointer"); return -1; }
+    if (B == 0 || P == 0) {
+        if (hipMemsetAsync(gw, 0, sizeof(float) * (C1 + C2), (hipStream_t)stream) != hipSuccess ||
+            (gb && hipMemsetAsync(gb, 0, sizeof(float), (hipStream_t)stream) != hipSuccess)) { set_error("uno_gelu_project2_backward: memset failed"); return -5; }
+        return 0;
+    }
+    if (!pre || !s || !w || !gout || !gpre || !ws) { set_error("uno_gelu_project2_backward: null pointer"); return -1; }
+    GeluProjectSecond two;
+    two.s = s; two.gs = gs; two.C1 = C1; two.act = act2;
+    return launch_gelu_project_bwd(pre, w, gout, gpre, gw, gb, (float*)ws, B, C1 + C2, P, 0, (hipStream_t)stream, PixelWindow(), &two);
+}
+
 static int gelu_pad_impl(const void* s, const void* gy, void* out, int n_img, int H, int W, int Hp, int Wp, int backward, int bf16, void* stream) {
     if (n_img < 0 || H < 1 || W < 1 || Hp < H || Wp < W) { set_error("uno_gelu_pad: bad sizes (%d, %d) -> (%d, %d)", H, W, Hp, Wp); return -1; }
     if (n_img == 0) return 0;

@@ -5,6 +5,10 @@
 //        378-381), and its backward  gpre = gelu'(pre) * w[c] * gout,  gw[c] = sum gout * gelu(pre),  gb = sum gout.
 //        Stock ops: GELU (2 passes over the C-channel tensor) + a GEMM with one useful output row; backward 3 + 2 + 2 passes.
 //        Here: forward reads pre once; backward reads pre once and writes gpre once.
+//        Two-source form (TWO):  out[b][p] = bias + sum_{c<C1} w[c] * gelu(pre[b][c][p]) + sum_{d<C2} w[C1+d] * f(s[b][d][p]),
+//        f = gelu or the identity - fc2 applied to cat([gelu(fc1(.)), gelu(fc(x))]) (navier_stokes_uno2d.py:121-125, 320-324: UNO_P,
+//        UNO_S256) without the concatenation; backward also gs = f'(s) * w[C1+d] * gout (optional).  The channel loop walks the
+//        C = C1 + C2 entries of w and takes each row from its source; the one-source kernels are the TWO = false instantiations.
 //   K12  gelu_pad:  out[n][h][w] = gelu(s[n][h][w]) for h < H, w < W, else 0       the lift's last GELU followed by the domain
 //        padding F.pad(x, [0, pad, 0, pad]) (darcy_flow_uno2d.py:103-107), and its backward gs = gelu'(s) * gy[n][h][w].
 //
@@ -47,9 +51,15 @@ constexpr int GP_MAXC = 1024;
 // SPLIT: small tensors (a 64 x 64 grid at batch 32 gives 512 one-wave pixel tiles for 256 CUs, each walking all C channels): the
 // four waves of a workgroup share ONE 256-pixel tile and take a quarter of the channels each; partial sums meet in LDS and are
 // added in wave order (fixed -> bit-reproducible).
-template <bool SPLIT, typename T>
+// the second source of the TWO form: channels [C1, C) of w belong to s (B, C - C1, P), activated when act; gs: its gradient (may be
+// null).  The one-source kernels take the empty record.
+template <typename T, bool TWO> struct ProjSecond {};
+template <typename T> struct ProjSecond<T, true> { const T* s; T* gs; int C1, act; };
+
+template <bool SPLIT, typename T, bool TWO>
 __global__ __launch_bounds__(256) void gelu_project_fwd_kernel(const T* __restrict__ pre, const float* __restrict__ w,
-                                                               const float* __restrict__ bias, T* __restrict__ out, int C, int P) {
+                                                               const float* __restrict__ bias, T* __restrict__ out, int C, int P,
+                                                               ProjSecond<T, TWO> two) {
     __shared__ float sw[GP_MAXC];
     __shared__ float sred[SPLIT ? 4 * 64 * 4 : 1];
     for (int c = threadIdx.x; c < C; c += blockDim.x) sw[c] = w[c];
@@ -61,22 +71,38 @@ __global__ __launch_bounds__(256) void gelu_project_fwd_kernel(const T* __restri
     if (!SPLIT && !live) return;
     const int Cs = SPLIT ? (C + 3) / 4 : C;
     const int c_lo = SPLIT ? min(wave * Cs, C) : 0, c_hi = SPLIT ? min(c_lo + Cs, C) : C;
-    const T* src = pre + (size_t)b * C * P;
+    int C1 = C;
+    if constexpr (TWO) C1 = two.C1;
+    const T* src = pre + (size_t)b * C1 * P;
+    // row of channel c (wave-uniform choice of the source)
+    auto row = [&](int c) {
+        if constexpr (TWO) {
+            if (c >= C1) return two.s + ((size_t)b * (C - C1) + (c - C1)) * P;
+        }
+        return src + (size_t)c * P;
+    };
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
     // channels in groups of 4, the next group's loads issued before the current one is consumed (-11 % against the
     // compiler's own unrolling, which drains each group of loads before issuing the next; the same change made the
     // backward kernel 12 % slower - it keeps the plain loop)
     auto load = [&](int c0, float v[4][4]) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) load4_guard(src + (size_t)max(min(c0 + j, c_hi - 1), 0) * P, px, P, v[j]);
+        for (int j = 0; j < 4; ++j) load4_guard(row(max(min(c0 + j, c_hi - 1), 0)), px, P, v[j]);
     };
     auto use = [&](int c0, const float v[4][4]) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             if (c0 + j < c_hi) {
                 const float wc = sw[c0 + j];
+                bool plain = false;
+                if constexpr (TWO) plain = c0 + j >= C1 && !two.act;
+                if (plain) {
 #pragma unroll
-                for (int i = 0; i < 4; ++i) acc[i] = fmaf(wc, gelu_f(v[j][i]), acc[i]);
+                    for (int i = 0; i < 4; ++i) acc[i] = fmaf(wc, v[j][i], acc[i]);
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) acc[i] = fmaf(wc, gelu_f(v[j][i]), acc[i]);
+                }
             }
         }
     };
@@ -110,10 +136,12 @@ __global__ __launch_bounds__(256) void gelu_project_fwd_kernel(const T* __restri
 // batch 32 gave 128 workgroups of 256 threads for 256 CUs); partial weight / bias gradients per workgroup: part[blk][C + 1].
 // Per channel every wave reduces its 256 pixels by butterfly and parks the sum in LDS; one barrier at the end, then the
 // four wave sums are added in wave order (fixed order -> bit-reproducible).
-template <typename T>
+// TWO: channels [C1, C) read s and write gs (dense only); every partial-sum slot keeps its place in part[..][C + 1].
+template <typename T, bool TWO>
 __global__ __launch_bounds__(256) void gelu_project_bwd_kernel(const T* __restrict__ pre, const float* __restrict__ w,
                                                                const T* __restrict__ gout, T* __restrict__ gpre,
-                                                               float* __restrict__ part, int C, int P, int Cs, PixMap pm, int rev) {
+                                                               float* __restrict__ part, int C, int P, int Cs, PixMap pm, int rev,
+                                                               ProjSecond<T, TWO> two) {
     // pm: pixel window (uno_common.h) - pre, gout (one plane per batch entry) and gpre on one window; dense: pm.PS == P
     // blockIdx.z = channel split: channels [z Cs, min(C, (z + 1) Cs)); small tensors (one-wave workgroups) are split over
     // channels as well, so that the chip sees 4x the waves (a 64 x 64 grid at batch 32 gave 512 waves walking 128 channels each)
@@ -131,8 +159,10 @@ __global__ __launch_bounds__(256) void gelu_project_bwd_kernel(const T* __restri
     // leaves the guards in logical pixels
     const int PS = pm.PS, fx = live ? pix_phys(pm, px) - px : 0;
     if (live) load4_guard(gout + (size_t)b * PS + fx, px, P, g);
-    const T* src = pre + (size_t)b * C * PS + fx;
-    T* dst = gpre + (size_t)b * C * PS + fx;
+    int C1 = C;
+    if constexpr (TWO) C1 = two.C1;
+    const T* src = pre + (size_t)b * C1 * PS + fx;
+    T* dst = gpre + (size_t)b * C1 * PS + fx;
     float* mine = swave + wave * (C + 1);
     auto wave_sum = [&](float s, int slot) {
 #pragma unroll
@@ -145,16 +175,35 @@ __global__ __launch_bounds__(256) void gelu_project_bwd_kernel(const T* __restri
         float s = 0.f;
         if (live) {
             float v[4], o[4];
-            load4_guard(src + (size_t)c * PS, px, P, v);
-            const float wc = sw[c];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const float cdf = 0.5f * (1.f + uno_erf(v[i] * 0.70710678118654752440f));
-                const float pdf = 0.39894228040143267794f * __expf(-0.5f * v[i] * v[i]);
-                o[i] = fmaf(v[i], pdf, cdf) * (wc * g[i]);
-                s = fmaf(g[i], v[i] * cdf, s);              // g is zero past the row end
+            const T* in = src + (size_t)c * PS;
+            T* to = dst + (size_t)c * PS;
+            bool plain = false;
+            if constexpr (TWO) {
+                if (c >= C1) {              // wave-uniform: the second source's row, its gradient row (or none)
+                    const size_t r = ((size_t)b * (C - C1) + (c - C1)) * PS;
+                    in = two.s + r;
+                    to = two.gs ? two.gs + r : nullptr;
+                    plain = !two.act;
+                }
             }
-            store4_guard(dst + (size_t)c * PS, px, P, o);
+            load4_guard(in, px, P, v);
+            const float wc = sw[c];
+            if (plain) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    o[i] = wc * g[i];
+                    s = fmaf(g[i], v[i], s);
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const float cdf = 0.5f * (1.f + uno_erf(v[i] * 0.70710678118654752440f));
+                    const float pdf = 0.39894228040143267794f * __expf(-0.5f * v[i] * v[i]);
+                    o[i] = fmaf(v[i], pdf, cdf) * (wc * g[i]);
+                    s = fmaf(g[i], v[i] * cdf, s);              // g is zero past the row end
+                }
+            }
+            if (!TWO || to) store4_guard(to, px, P, o);
         }
         wave_sum(s, c);
     }
@@ -191,20 +240,29 @@ __global__ __launch_bounds__(256) void gelu_project_reduce_kernel(const float* _
 // 256-thread workgroups unless that leaves the GPU under-filled (< 4 workgroups per CU)
 static int gelu_project_threads(int B, long long P) { return (long long)B * ((P + 1023) / 1024) >= 1024 ? 256 : 64; }
 
-int launch_gelu_project_fwd(const void* pre, const float* w, const float* bias, void* out, int B, int C, long long P, int bf16, hipStream_t s) {
+// two: the second source of the TWO form (float32 only), C = C1 + C2 then; null: one source
+int launch_gelu_project_fwd(const void* pre, const float* w, const float* bias, void* out, int B, int C, long long P, int bf16, hipStream_t s,
+                            const GeluProjectSecond* two) {
     typedef unsigned short bf_t;
     if (C > GP_MAXC || P > 0x7fffffffLL || B > 65535) { set_error("gelu_project: C <= %d, pixels < 2^31, batch < 65536", GP_MAXC); return -2; }
+    if (two && (bf16 || two->C1 < 1 || two->C1 >= C || !two->s)) { set_error("gelu_project: two sources are float32 with 1 <= C1 < C"); return -2; }
     const int threads = gelu_project_threads(B, P);
     const bool split = threads == 64 && C >= 16;
     const unsigned nb = (unsigned)((P + 4 * threads - 1) / (4 * threads));
     {
         ProfScope prof("uno::gelu_project_fwd_kernel", (bf16 ? 2.0 : 4.0) * B * (double)P * (C + 1), s);
-        if (bf16) {
-            if (split) hipLaunchKernelGGL((gelu_project_fwd_kernel<true, bf_t>), dim3(nb, B), dim3(256), 0, s, (const bf_t*)pre, w, bias, (bf_t*)out, C, (int)P);
-            else hipLaunchKernelGGL((gelu_project_fwd_kernel<false, bf_t>), dim3(nb, B), dim3(threads), 0, s, (const bf_t*)pre, w, bias, (bf_t*)out, C, (int)P);
+        if (two) {
+            const ProjSecond<float, true> t2{(const float*)two->s, nullptr, two->C1, two->act};
+            if (split) hipLaunchKernelGGL((gelu_project_fwd_kernel<true, float, true>), dim3(nb, B), dim3(256), 0, s, (const float*)pre, w, bias, (float*)out, C, (int)P, t2);
+            else hipLaunchKernelGGL((gelu_project_fwd_kernel<false, float, true>), dim3(nb, B), dim3(threads), 0, s, (const float*)pre, w, bias, (float*)out, C, (int)P, t2);
+        } else if (bf16) {
+            const ProjSecond<bf_t, false> none;
+            if (split) hipLaunchKernelGGL((gelu_project_fwd_kernel<true, bf_t, false>), dim3(nb, B), dim3(256), 0, s, (const bf_t*)pre, w, bias, (bf_t*)out, C, (int)P, none);
+            else hipLaunchKernelGGL((gelu_project_fwd_kernel<false, bf_t, false>), dim3(nb, B), dim3(threads), 0, s, (const bf_t*)pre, w, bias, (bf_t*)out, C, (int)P, none);
         } else {
-            if (split) hipLaunchKernelGGL((gelu_project_fwd_kernel<true, float>), dim3(nb, B), dim3(256), 0, s, (const float*)pre, w, bias, (float*)out, C, (int)P);
-            else hipLaunchKernelGGL((gelu_project_fwd_kernel<false, float>), dim3(nb, B), dim3(threads), 0, s, (const float*)pre, w, bias, (float*)out, C, (int)P);
+            const ProjSecond<float, false> none;
+            if (split) hipLaunchKernelGGL((gelu_project_fwd_kernel<true, float, false>), dim3(nb, B), dim3(256), 0, s, (const float*)pre, w, bias, (float*)out, C, (int)P, none);
+            else hipLaunchKernelGGL((gelu_project_fwd_kernel<false, float, false>), dim3(nb, B), dim3(threads), 0, s, (const float*)pre, w, bias, (float*)out, C, (int)P, none);
         }
     }
     const hipError_t e = hipGetLastError();
@@ -221,9 +279,10 @@ long long gelu_project_ws_floats(int B, int C, long long P) {
 }
 
 int launch_gelu_project_bwd(const void* pre, const float* w, const void* gout, void* gpre, float* gw, float* gb, float* ws, int B,
-                            int C, long long P, int bf16, hipStream_t s, const PixelWindow& win) {
+                            int C, long long P, int bf16, hipStream_t s, const PixelWindow& win, const GeluProjectSecond* two) {
     typedef unsigned short bf_t;
     if (C > GP_MAXC || P > 0x7fffffffLL || B > 65535) { set_error("gelu_project: C <= %d, pixels < 2^31, batch < 65536", GP_MAXC); return -2; }
+    if (two && (bf16 || win.cols || two->C1 < 1 || two->C1 >= C || !two->s)) { set_error("gelu_project: two sources are float32, dense, with 1 <= C1 < C"); return -2; }
     if (const char* why = pix_window_error(win, P)) { set_error("gelu_project: %s", why); return -2; }
     if (win.cols && (long long)C * win.plane > 0x7fffffffLL) { set_error("gelu_project: window planes too large"); return -2; }
     const PixMap pm = pix_map(win, P);
@@ -232,10 +291,14 @@ int launch_gelu_project_bwd(const void* pre, const float* w, const void* gout, v
     const int nsplit = gelu_project_splits(B, C, P), Cs = (C + nsplit - 1) / nsplit;
     const int rev = next_sweep_reversed(SWEEP_PROJ);
     {
-        ProfScope prof("uno::gelu_project_bwd_kernel", (bf16 ? 2.0 : 4.0) * B * (double)P * (2 * C + 1), s);
+        const int Cw = two && !two->gs ? two->C1 : C;           // channels whose gradient rows are written
+        ProfScope prof("uno::gelu_project_bwd_kernel", (bf16 ? 2.0 : 4.0) * B * (double)P * (C + Cw + 1), s);
         const size_t lds = (threads / 64) * (C + 1) * sizeof(float);
-        if (bf16) hipLaunchKernelGGL(gelu_project_bwd_kernel<bf_t>, dim3(nb, B, nsplit), dim3(threads), lds, s, (const bf_t*)pre, w, (const bf_t*)gout, (bf_t*)gpre, ws, C, (int)P, Cs, pm, rev);
-        else hipLaunchKernelGGL(gelu_project_bwd_kernel<float>, dim3(nb, B, nsplit), dim3(threads), lds, s, (const float*)pre, w, (const float*)gout, (float*)gpre, ws, C, (int)P, Cs, pm, rev);
+        if (two) {
+            const ProjSecond<float, true> t2{(const float*)two->s, (float*)two->gs, two->C1, two->act};
+            hipLaunchKernelGGL((gelu_project_bwd_kernel<float, true>), dim3(nb, B, nsplit), dim3(threads), lds, s, (const float*)pre, w, (const float*)gout, (float*)gpre, ws, C, (int)P, Cs, pm, rev, t2);
+        } else if (bf16) hipLaunchKernelGGL((gelu_project_bwd_kernel<bf_t, false>), dim3(nb, B, nsplit), dim3(threads), lds, s, (const bf_t*)pre, w, (const bf_t*)gout, (bf_t*)gpre, ws, C, (int)P, Cs, pm, rev, ProjSecond<bf_t, false>());
+        else hipLaunchKernelGGL((gelu_project_bwd_kernel<float, false>), dim3(nb, B, nsplit), dim3(threads), lds, s, (const float*)pre, w, (const float*)gout, (float*)gpre, ws, C, (int)P, Cs, pm, rev, ProjSecond<float, false>());
     }
     hipLaunchKernelGGL(gelu_project_reduce_kernel, dim3((C + 1 + 3) / 4), dim3(256), 0, s, ws, gw, gb, C, (int)(nb * B), Cs);
     const hipError_t e = hipGetLastError();

@@ -347,10 +347,14 @@ int launch_adam_advance(int* step, float* scalars, const double* hyper, double l
                         hipStream_t s);
 int launch_adam(float* p, const float* g, float* m, float* v, long long n, int is_complex, double lr, double beta1, double beta2,
                 double eps, double wd, int step, hipStream_t s);
-int launch_gelu_project_fwd(const void* pre, const float* w, const float* bias, void* out, int B, int C, long long P, int bf16, hipStream_t s);
+// K11's second source (pointwise_fused.hip): entries [C1, C) of w belong to s (B, C - C1, P), activated when act; gs (backward): may be null
+struct GeluProjectSecond { const void* s = nullptr; void* gs = nullptr; int C1 = 0, act = 0; };
+int launch_gelu_project_fwd(const void* pre, const float* w, const float* bias, void* out, int B, int C, long long P, int bf16, hipStream_t s,
+                            const GeluProjectSecond* two = nullptr);
 long long gelu_project_ws_floats(int B, int C, long long P);
 int launch_gelu_project_bwd(const void* pre, const float* w, const void* gout, void* gpre, float* gw, float* gb, float* ws, int B,
-                            int C, long long P, int bf16, hipStream_t s, const PixelWindow& win = PixelWindow());
+                            int C, long long P, int bf16, hipStream_t s, const PixelWindow& win = PixelWindow(),
+                            const GeluProjectSecond* two = nullptr);
 int launch_gelu_pad(const void* s, const void* gy, void* out, int n_img, int H, int W, int Hp, int Wp, int backward, int bf16, hipStream_t st);
 int launch_transpose_batched(const float* in, float* out, int B, long long R, int C, long long ld_in, long long sb_in, long long ld_out,
                              long long sb_out, hipStream_t st);

@@ -16,7 +16,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..integral_operators import (GradJoin, OperatorBlock_2D, OperatorBlock_3D, channel_mix, channel_mix_cat, channel_mix_cat_project,
-                                  enable_native_resample3d_any, enable_one_buffer_any_grid, gelu_channel_mix, gelu_channel_mix_pad, gelu_pad2d, gelu_project, lift_gelu_pad)
+                                  enable_native_resample3d_any, enable_one_buffer_any_grid, gelu_channel_mix, gelu_channel_mix_pad, gelu_pad2d, gelu_project, gelu_project2,
+                                  lift_gelu_pad)
 
 
 class UNO_9(nn.Module):
@@ -176,6 +177,84 @@ class UNO(nn.Module):
         if p != 0:      # the reference pads both sides but crops one (navier_stokes_uno2d.py:201,217-218); kept
             c6 = c6[..., :-p, :-p]
         return gelu_project(channel_mix(c6.contiguous(), self.fc1.weight, self.fc1.bias), self.fc2.weight, self.fc2.bias)
+
+
+class UNO_P(UNO):
+    """Navier-Stokes 2-D U-NO with the more aggressive contraction (grids D/2, D/4, D/8 and back) - own counterpart of the reference's
+    `UNO_P` (navier_stokes_uno2d.py:24-138).  Against `UNO`: hard-coded modes 14 / 6 / 3, factor 1, fc1 = Linear(2w, 3w), and fc2 reads
+    the concatenation of gelu(fc1(.)) with the FIRST lift activation gelu(fc(x)) (:121-125) - here the two-source projection
+    (gelu_project2) on fc1's output and fc's kept pre-activation; the concatenation is never built.  The padding is cropped on both
+    sides (:116-117).  Sub-module names, registration order and `get_grid` follow the reference (state_dict compatible)."""
+
+    # output grid of L0 .. L6 as divisors of the padded grid (reference :99-113)
+    _DIV = (2, 4, 8, 8, 4, 2, 1)
+
+    def __init__(self, in_width, width, pad=0, factor=1, block_cls=OperatorBlock_2D):
+        nn.Module.__init__(self)
+        self.in_width, self.width, self.factor, self.padding = in_width, width, factor, pad
+        w, f = width, factor
+        self.fc = nn.Linear(in_width, w // 2)
+        self.fc0 = nn.Linear(w // 2, w)
+        self.L0 = block_cls(w, 2 * f * w, 32, 32, 14, 14)
+        self.L1 = block_cls(2 * f * w, 4 * f * w, 16, 16, 6, 6)
+        self.L2 = block_cls(4 * f * w, 8 * f * w, 8, 8, 3, 3)
+        self.L3 = block_cls(8 * f * w, 8 * f * w, 8, 8, 3, 3)
+        self.L4 = block_cls(8 * f * w, 4 * f * w, 16, 16, 3, 3)
+        self.L5 = block_cls(8 * f * w, 2 * f * w, 32, 32, 6, 6)
+        self.L6 = block_cls(4 * f * w, w, 64, 64, 14, 14)
+        self.fc1 = nn.Linear(2 * w, 3 * w)
+        self.fc2 = nn.Linear(3 * w + w // 2, 1)
+        self._grid_cache = {}
+
+    def forward_cf(self, x):
+        """(B, T_in + 4, S, S) channels-first window + positional features -> (B, 1, S, S), as UNO.forward_cf."""
+        h = channel_mix(x, self.fc.weight, self.fc.bias)            # kept PRE-activation: fc0 and fc2 apply the GELU as they read it
+        lifted = F.gelu(gelu_channel_mix(h, self.fc0.weight, self.fc0.bias))
+        p = self.padding
+        if p != 0:
+            lifted = F.pad(lifted, [p, p, p, p])
+        d1, d2 = lifted.shape[-2], lifted.shape[-1]
+        g = [(d1 // k, d2 // k) for k in self._DIV]
+        c0 = self.L0(lifted, *g[0])
+        c1 = self.L1(c0, *g[1])
+        if hasattr(self.L6, "forward_cat") and all(b.non_lin and not b.normalize for b in (self.L2, self.L3)):
+            j2, j3 = GradJoin(), GradJoin()         # c2, c3 have one consumer each: gelu'(pre) in the consumer's last kernel (see UNO)
+            c2 = self.L2(c1, *g[2], out_join=j2)
+            c3 = self.L3(c2, *g[3], join=j2, out_join=j3)
+            c4 = torch.cat([self.L4(c3, *g[4], join=j3), c1], dim=1)
+        else:
+            c3 = self.L3(self.L2(c1, *g[2]), *g[3])
+            c4 = torch.cat([self.L4(c3, *g[4]), c1], dim=1)
+        c5 = torch.cat([self.L5(c4, *g[5]), c0], dim=1)
+        c6 = torch.cat([self.L6(c5, *g[6]), lifted], dim=1)
+        if p != 0:
+            c6 = c6[..., p:-p, p:-p]
+        return gelu_project2(channel_mix(c6.contiguous(), self.fc1.weight, self.fc1.bias), h, self.fc2.weight, self.fc2.bias, act2=True)
+
+
+class UNO_S256(UNO_P):
+    """Navier-Stokes 2-D U-NO for 256 x 256 simulations - own counterpart of the reference's `UNO_S256` (navier_stokes_uno2d.py:246-337):
+    `UNO_P`'s structure with grids D/4, D/16, D/32 and back (4x contraction and expansion per level), modes up to (32, 33), and a first
+    lift layer of 16 channels whatever the width (fc2 = Linear(3w + 16, 1))."""
+
+    _DIV = (4, 16, 32, 32, 16, 4, 1)
+
+    def __init__(self, in_width, width, pad=0, factor=1, block_cls=OperatorBlock_2D):
+        nn.Module.__init__(self)
+        self.in_width, self.width, self.factor, self.padding = in_width, width, factor, pad
+        w, f = width, factor
+        self.fc = nn.Linear(in_width, 16)
+        self.fc0 = nn.Linear(16, w)
+        self.L0 = block_cls(w, 2 * f * w, 64, 64, 32, 33)
+        self.L1 = block_cls(2 * f * w, 4 * f * w, 16, 16, 8, 9)
+        self.L2 = block_cls(4 * f * w, 8 * f * w, 8, 8, 4, 5)
+        self.L3 = block_cls(8 * f * w, 8 * f * w, 8, 8, 4, 5)
+        self.L4 = block_cls(8 * f * w, 4 * f * w, 16, 16, 4, 5)
+        self.L5 = block_cls(8 * f * w, 2 * f * w, 64, 64, 8, 9)
+        self.L6 = block_cls(4 * f * w, w, 256, 256, 32, 32)
+        self.fc1 = nn.Linear(2 * w, 3 * w)
+        self.fc2 = nn.Linear(3 * w + 16, 1)
+        self._grid_cache = {}
 
 
 class Uno3D_T20(nn.Module):

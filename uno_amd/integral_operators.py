@@ -30,7 +30,7 @@ import torch.nn.functional as F
 from ._param_grads import release_pass_state
 from .block2d import _OperatorBlock2dCatFn, _OperatorBlock2dFn, _SpectralConv2dFn, spectral_conv2d, spectral_conv2d_mixed
 from .pointwise import (GradJoin, _dev_act, channel_mix, channel_mix_cat, channel_mix_cat_project, gelu_channel_mix, gelu_channel_mix_pad,
-                        gelu_pad2d, gelu_project, instance_norm_gelu, lift_gelu_pad)
+                        gelu_pad2d, gelu_project, gelu_project2, instance_norm_gelu, lift_gelu_pad)
 from .resample import resample2d_bicubic_aa
 from .spectral3d import (_FftResample3dAnyFn, _FftResample3dFn, _OperatorBlock3dFn, _resample3d_plan, _resample3d_plan_any, spectral_conv3d)
 

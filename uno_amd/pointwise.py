@@ -613,6 +613,40 @@ def gelu_project(pre: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | N
     return channel_mix(F.gelu(pre), weight, bias)
 
 
+class _GeluProject2Fn(torch.autograd.Function):
+    """out[b, p] = bias + sum_c w[c] gelu(pre[b, c, p]) + sum_d w[C1 + d] f(s[b, d, p]) (K11's two-source form)."""
+
+    @staticmethod
+    def forward(ctx, pre, s, w, bias, act2):
+        pre, s, w = _plain(pre), _plain(s), _plain(w)
+        out = _native.gelu_project2_forward(pre, s, w, None if bias is None else _plain(bias), act2)
+        ctx.save_for_backward(pre, s, w)
+        ctx.has_bias, ctx.act2 = bias is not None, act2
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        pre, s, w = ctx.saved_tensors
+        gpre, gs, gw, gb = _native.gelu_project2_backward(pre, s, w, _plain(gout), ctx.act2, need_gs=ctx.needs_input_grad[1],
+                                                          need_bias=ctx.has_bias)
+        return gpre, gs, gw, gb, None
+
+
+def gelu_project2(pre: torch.Tensor, s: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None, act2: bool = False) -> torch.Tensor:
+    """channel_mix(torch.cat([F.gelu(pre), f(s)], 1), weight, bias), f = F.gelu if act2 else the identity - the end of the reference's
+    UNO_P / UNO_S256 (navier_stokes_uno2d.py:121-125, 320-324: `fc2(torch.cat([F.gelu(fc1(x)), x_fc], 3))`, fc2 = Linear(C1 + C2, 1)).
+    With ONE output channel on a HIP device, float32, both sources are read once by a single streaming pass (K11, two-source form):
+    no GELU output, no concatenation, no one-row GEMM.  `s` is the pre-activation of the second source when act2."""
+    C1, C2 = pre.shape[1], s.shape[1]
+    if (weight.shape[0] == 1 and pre.is_cuda and s.is_cuda and pre.dtype == torch.float32 and s.dtype == torch.float32
+            and weight.dtype == torch.float32 and C1 >= 1 and C2 >= 1 and C1 + C2 <= 1024):
+        B = pre.shape[0]
+        out = _GeluProject2Fn.apply(pre.reshape(B, C1, -1), s.reshape(B, C2, -1), weight.reshape(C1 + C2), bias, bool(act2))
+        return out.view(B, 1, *pre.shape[2:])
+    return channel_mix(torch.cat([F.gelu(pre), F.gelu(s) if act2 else s], 1), weight, bias)
+
+
 class _GeluPadFn(torch.autograd.Function):
     """zero-pad(gelu(s)) at the end of the last two axes (K12)."""
 
