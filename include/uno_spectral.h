@@ -313,6 +313,21 @@ long long uno_gelu_project2_bwd_ws_bytes(int B, int C1, int C2, long long P);
 int uno_gelu_project2_backward(const float* pre, const float* s, const float* w, const float* gout, float* gpre, float* gs, float* gw,
                                float* gb, void* ws, int B, int C1, int C2, long long P, int act2, void* stream);
 
+/* Per-time-step relative L2 error in one pass (additive: the ABI version stays 14).  The reference's NS-3D loop computes, for every
+ * batch and under no_grad, `sum_t LpLoss(size_average=False)(out[..., t], y[..., t])` (ns_train_3d.py:55-62, 84-98) - the number it
+ * prints and selects checkpoints by; its 2-D test loop (ns_train_2d.py:133-150) needs the same per step and for the whole trajectory.
+ * pred, target: dense float32 (B, P, T), T innermost (the model's (B, S, S, T_f) output, P = S * S).  Written by the call:
+ *   sums   (B, T, 2)   [b][t][0] = sum_p (pred - target)^2,  [b][t][1] = sum_p target^2
+ *   rel    (B, T + 1)  [b][t] = sqrt(num) / sqrt(den) for t < T;  [b][T] = sqrt(sum_t num) / sqrt(sum_t den), the whole trajectory
+ *   totals (2)         [0] = sum_b sum_{t<T} rel[b][t] (the reference's temp_step_loss);  [1] = sum_b rel[b][T]
+ * 1 <= T <= 256, P >= 1, any B * P * T (64-bit offsets); B == 0 returns 0 without touching the device.  No clamping: a zero target
+ * slice gives +inf (NaN for 0 / 0) as torch.norm(.) / torch.norm(.) does.  Two launches, no atomics; the chunk decomposition is a
+ * function of (P, T) alone (not of the CU count or uno_reserve_cus), so two calls give the same bits.
+ * ws: scratch of uno_rel_l2_steps_ws_bytes() bytes (never shrinks as P grows).  Forward only: the training loss is not this call. */
+long long uno_rel_l2_steps_ws_bytes(int B, long long P, int T);
+int uno_rel_l2_steps(const float* pred, const float* target, float* sums, float* rel, float* totals, void* ws, int B, long long P, int T,
+                     void* stream);
+
 /* The same three calls on a WINDOW of a wider plane (ABI 10).  The reference crops the domain padding before its last two layers
  * (darcy_flow_uno2d.py:125-131: `x_c5[..., :-padding, :-padding]`, then fc1 - GELU - fc2 on S x S points); here those layers read
  * the padded (S + pad)^2 tensors in place and touch the domain only: the pixel axis of the call is rows x cols logical pixels,

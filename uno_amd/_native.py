@@ -87,6 +87,8 @@ _SIGNATURES = {
     "uno_gelu_project2_forward": (C.c_int, [_fp] * 5 + [_i, _i, _i, C.c_longlong, _i, _fp]),
     "uno_gelu_project2_bwd_ws_bytes": (C.c_longlong, [_i, _i, _i, C.c_longlong]),
     "uno_gelu_project2_backward": (C.c_int, [_fp] * 9 + [_i, _i, _i, C.c_longlong, _i, _fp]),
+    "uno_rel_l2_steps_ws_bytes": (C.c_longlong, [_i, C.c_longlong, _i]),
+    "uno_rel_l2_steps": (C.c_int, [_fp] * 6 + [_i, C.c_longlong, _i, _fp]),
     "uno_gelu_pad": (C.c_int, [_fp, _fp, _fp] + [_i] * 6 + [_fp]),
     "uno_transpose_batched": (C.c_int, [_fp, _fp, _i, C.c_longlong, _i] + [C.c_longlong] * 4 + [_fp]),
     "uno_instnorm_forward": (C.c_int, [_fp] * 6 + [C.c_longlong, _i, C.c_longlong, C.c_float, _i, _fp]),
@@ -1031,6 +1033,30 @@ def gelu_project2_backward(pre, s, w, gout, act2=False, need_gs=True, need_bias=
                                           B, C1, C2, P, 1 if act2 else 0, _stream(pre))
     _check(rc, "uno_gelu_project2_backward")
     return gpre, gs, gw, gb
+
+
+def rel_l2_steps(pred, target):
+    """pred, target dense f32 (B, ..., T), 1 <= T <= 256 -> sums (B, T, 2), rel (B, T + 1), totals (2,) (uno_rel_l2_steps, K17):
+    sums[b][t] = [sum (pred - target)^2, sum target^2] over the middle axes, rel[b][t] = sqrt(num) / sqrt(den) with rel[b][T] the
+    whole-trajectory ratio, totals = [sum of the per-step ratios, sum of the whole-trajectory ratios].  Forward only; launches on the
+    current stream and allocates through torch, so it can be captured into a hipGraph."""
+    _require(pred, torch.float32, "pred")
+    _require(target, torch.float32, "target")
+    if pred.shape != target.shape or pred.device != target.device:
+        raise RuntimeError(f"uno_amd: pred {tuple(pred.shape)} on {pred.device} and target {tuple(target.shape)} on {target.device} differ")
+    if pred.dim() < 2:
+        raise RuntimeError(f"uno_amd: step errors take (batch, ..., time) tensors (got {tuple(pred.shape)})")
+    B, T = pred.shape[0], pred.shape[-1]
+    P = _count(pred.shape[1:-1])
+    L = lib()
+    with torch.cuda.device(pred.device):
+        sums = torch.empty((B, T, 2), dtype=torch.float32, device=pred.device)
+        rel = torch.empty((B, T + 1), dtype=torch.float32, device=pred.device)
+        totals = torch.zeros((2,), dtype=torch.float32, device=pred.device) if B == 0 else torch.empty((2,), dtype=torch.float32, device=pred.device)
+        ws = torch.empty(max(1, L.uno_rel_l2_steps_ws_bytes(B, P, T)), dtype=torch.uint8, device=pred.device)
+        rc = L.uno_rel_l2_steps(_ptr(pred), _ptr(target), _ptr(sums), _ptr(rel), _ptr(totals), _ptr(ws), B, P, T, _stream(pred))
+    _check(rc, "uno_rel_l2_steps")
+    return sums, rel, totals
 
 
 class _DeviceView:

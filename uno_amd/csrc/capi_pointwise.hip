@@ -521,6 +521,26 @@ int uno_gelu_project2_backward(const float* pre, const float* s, const float* w,
     return launch_gelu_project_bwd(pre, w, gout, gpre, gw, gb, (float*)ws, B, C1 + C2, P, 0, (hipStream_t)stream, PixelWindow(), &two);
 }
 
+// K17: per-time-step relative L2 error (forward only), dense float32 (B, P, T)
+static bool rel_l2_steps_sizes(const char* who, int B, long long P, int T) {
+    if (B < 0 || P < 1 || T < 1) { set_error("%s: bad sizes B=%d P=%lld T=%d", who, B, P, T); return false; }
+    if (T > 256) { set_error("%s: T = %d time steps, at most 256", who, T); return false; }
+    return true;
+}
+
+long long uno_rel_l2_steps_ws_bytes(int B, long long P, int T) {
+    if (B < 1 || P < 1 || T < 1 || T > 256) return 0;
+    return 4LL * rel_l2_steps_ws_floats(B, P, T);
+}
+
+int uno_rel_l2_steps(const float* pred, const float* target, float* sums, float* rel, float* totals, void* ws, int B, long long P, int T,
+                     void* stream) {
+    if (!rel_l2_steps_sizes("uno_rel_l2_steps", B, P, T)) return -1;
+    if (B == 0) return 0;
+    if (!pred || !target || !sums || !rel || !totals || !ws) { set_error("uno_rel_l2_steps: null pointer"); return -1; }
+    return launch_rel_l2_steps(pred, target, sums, rel, totals, (float*)ws, B, P, T, (hipStream_t)stream);
+}
+
 static int gelu_pad_impl(const void* s, const void* gy, void* out, int n_img, int H, int W, int Hp, int Wp, int backward, int bf16, void* stream) {
     if (n_img < 0 || H < 1 || W < 1 || Hp < H || Wp < W) { set_error("uno_gelu_pad: bad sizes (%d, %d) -> (%d, %d)", H, W, Hp, Wp); return -1; }
     if (n_img == 0) return 0;

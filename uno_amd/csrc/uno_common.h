@@ -384,5 +384,10 @@ int launch_lift_forward_fused(const float* x, const float* w1, const float* b1, 
 int launch_lift_backward_fused(const float* x, const float* w1, const float* b1, const float* w0, const float* b0, const float* g, float* part,
                                float* part1, int B, int Cin, int H, int W, int Hp, int Wp, hipStream_t s, const float* g2 = nullptr);
 int launch_channel_wgrad_finish(const float* parts, float* gw, float* gb, int Ci, int Co, long long nparts, int accumulate, hipStream_t s);
+// rel_l2_steps.hip (K17): per-time-step relative L2 error of dense (B, P, T) tensors, 1 <= T <= 256; ws: rel_l2_steps_ws_floats() floats
+long long rel_l2_steps_chunks(long long P, int T, long long* chunk_pixels);       // chunk count: a function of (P, T) alone
+long long rel_l2_steps_ws_floats(int B, long long P, int T);
+int launch_rel_l2_steps(const float* pred, const float* target, float* sums, float* rel, float* totals, float* ws, int B, long long P, int T,
+                        hipStream_t s);
 
 }  // namespace uno

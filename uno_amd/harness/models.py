@@ -319,6 +319,85 @@ class Uno3D_T20(nn.Module):
         return out.permute(0, 2, 3, 4, 1).contiguous()
 
 
+class Uno3D_T10(Uno3D_T20):
+    """Navier-Stokes 3-D U-NO mapping 10 input steps to 10 output steps - own counterpart of the reference's `Uno3D_T10`
+    (navier_stokes_uno3d.py:412-602): the T20 network with a time axis that keeps its (padded) length through all seven blocks
+    (5 time modes everywhere) and a `padding` crop.  Input (B, S, S, T, 1) -> output (B, S, S, T, 1).  Every layer's grid pair is
+    inside the pruned-DFT kernels' range at S <= 64 (tests/test_harness_ns3d_models.py holds the census)."""
+
+    def __init__(self, in_width, width, pad=2, factor=1, pad_both=False, block_cls=OperatorBlock_3D):
+        nn.Module.__init__(self)
+        self.in_width, self.width, self.pad, self.pad_both = in_width, width, pad, pad_both
+        w, f = width, factor
+        self.fc = nn.Linear(in_width, in_width * 2)
+        self.fc0 = nn.Linear(in_width * 2, w)
+        self.conv0 = block_cls(w, 2 * f * w, 48, 48, 10, 22, 22, 5, Normalize=True)
+        self.conv1 = block_cls(2 * f * w, 4 * f * w, 32, 32, 10, 14, 14, 5)
+        self.conv2 = block_cls(4 * f * w, 8 * f * w, 16, 16, 10, 6, 6, 5)
+        self.conv3 = block_cls(8 * f * w, 16 * f * w, 16, 16, 10, 6, 6, 5, Normalize=True)
+        self.conv6 = block_cls(16 * f * w, 4 * f * w, 32, 32, 10, 6, 6, 5)
+        self.conv7 = block_cls(8 * f * w, 2 * f * w, 48, 48, 10, 14, 14, 5, Normalize=True)
+        self.conv8 = block_cls(4 * f * w, 2 * w, 64, 64, 10, 22, 22, 5)
+        self.fc1 = nn.Linear(3 * w, 4 * w)
+        self.fc2 = nn.Linear(4 * w, 1)
+        self._grid_cache = {}
+
+    # time length of conv2, conv3, conv6, conv7, conv8 and the crop, from the padded input length d3 / the padding
+    @staticmethod
+    def _time_plan(d3, padding):
+        return (d3, d3, d3, d3, d3), padding
+
+    def forward(self, x):
+        x = torch.cat((x, self.get_grid(x.shape, x.device)), dim=-1).permute(0, 4, 1, 2, 3).contiguous()
+        lifted = F.gelu(gelu_channel_mix(channel_mix(x, self.fc.weight, self.fc.bias), self.fc0.weight, self.fc0.bias))
+        self.padding = int(self.pad * 0.1 * lifted.shape[-1])
+        lifted = F.pad(lifted, [self.padding, self.padding, 0, 0, 0, 0] if self.pad_both else [0, self.padding, 0, 0, 0, 0])
+        d1, d2, d3 = lifted.shape[-3:]
+        (t2, t3, t6, t7, t8), crop = self._time_plan(d3, self.padding)
+        c0 = self.conv0(lifted, int(3 * d1 / 4), int(3 * d2 / 4), d3)
+        c1 = self.conv1(c0, d1 // 2, d2 // 2, d3)
+        c2 = self.conv2(c1, d1 // 4, d2 // 4, t2)
+        c3 = self.conv3(c2, d1 // 4, d2 // 4, t3)
+        c6 = self.conv6(c3, d1 // 2, d2 // 2, t6)
+        c6 = torch.cat([c6, self._resize(c1, c6)], dim=1)
+        c7 = self.conv7(c6, int(3 * d1 / 4), int(3 * d2 / 4), t7)
+        c7 = torch.cat([c7, self._resize(c0, c7)], dim=1)
+        c8 = self.conv8(c7, d1, d2, t8)
+        c8 = torch.cat([c8, self._resize(lifted, c8)], dim=1)
+        if self.padding != 0:           # (the crop is written from `padding` as the reference writes it: -0 would empty the tensor)
+            c8 = c8[..., crop:-crop] if self.pad_both else c8[..., :-crop]
+        out = gelu_project(channel_mix(c8.contiguous(), self.fc1.weight, self.fc1.bias), self.fc2.weight, self.fc2.bias)
+        return out.permute(0, 2, 3, 4, 1).contiguous()
+
+
+class Uno3D_T9(Uno3D_T10):
+    """Navier-Stokes 3-D U-NO mapping 6 input steps to 9 output steps - own counterpart of the reference's `Uno3D_T9`
+    (navier_stokes_uno3d.py:605-797): modes 20 / 18 / 6 / 6 / 6 / 14 / 20 in space and 3 (4 in conv8) in time, a time axis that grows
+    to int(8 * d3 / 6) at conv3 / conv6 and int(9 * d3 / 6) at conv7 / conv8, and an int(9 * padding / 6) crop.  Input
+    (B, S, S, 6, 1) -> output (B, S, S, 9, 1).  conv1 keeps 18 modes on the half grid, so S >= 36 (the reference raises below)."""
+
+    def __init__(self, in_width, width, pad=2, factor=1, pad_both=False, block_cls=OperatorBlock_3D):
+        nn.Module.__init__(self)
+        self.in_width, self.width, self.pad, self.pad_both = in_width, width, pad, pad_both
+        w, f = width, factor
+        self.fc = nn.Linear(in_width, in_width * 2)
+        self.fc0 = nn.Linear(in_width * 2, w)
+        self.conv0 = block_cls(w, 2 * f * w, 48, 48, 6, 20, 20, 3, Normalize=True)
+        self.conv1 = block_cls(2 * f * w, 4 * f * w, 32, 32, 6, 18, 18, 3)
+        self.conv2 = block_cls(4 * f * w, 8 * f * w, 16, 16, 6, 6, 6, 3)
+        self.conv3 = block_cls(8 * f * w, 16 * f * w, 16, 16, 8, 6, 6, 3, Normalize=True)
+        self.conv6 = block_cls(16 * f * w, 4 * f * w, 32, 32, 8, 6, 6, 3)
+        self.conv7 = block_cls(8 * f * w, 2 * f * w, 48, 48, 9, 14, 14, 3, Normalize=True)
+        self.conv8 = block_cls(4 * f * w, 2 * w, 64, 64, 9, 20, 20, 4)
+        self.fc1 = nn.Linear(3 * w, 4 * w)
+        self.fc2 = nn.Linear(4 * w, 1)
+        self._grid_cache = {}
+
+    @staticmethod
+    def _time_plan(d3, padding):
+        return (d3, int(8 * d3 / 6), int(8 * d3 / 6), int(9 * d3 / 6), int(9 * d3 / 6)), int(9 * padding / 6)
+
+
 class Uno3D_T40(Uno3D_T20):
     """Navier-Stokes 3-D U-NO mapping 10 input steps to 40 output steps - own counterpart of the reference's `Uno3D_T40`
     (navier_stokes_uno3d.py:22-237): the T20 network with a narrower lift (width // 2), a deeper bottom level (conv3 at an eighth of

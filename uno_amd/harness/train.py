@@ -16,7 +16,7 @@ import time
 import torch
 import torch.distributed as dist
 
-from .losses import lp_loss_rel_sum
+from .losses import lp_loss_rel_sum, step_errors
 from .optim import ComplexAdam
 
 
@@ -218,11 +218,39 @@ def ns2d_rollout_loss(model, xx, yy, T_f, step=1):
     return loss
 
 
-def ns3d_loss(model, x, y):
-    """Space-time loss of the NS-3D training step (reference ns_train_3d.py:53,64): one forward, global relative L2."""
+def ns3d_step_error(out, y):
+    """The number the reference's NS-3D loop prints and selects checkpoints by (ns_train_3d.py:55-62): the sum over the time steps
+    of the per-step relative L2 error summed over the batch.  out, y: (B, S, S, T_f); a 0-dim device tensor, no gradient."""
+    return step_errors(out, y).step_sum
+
+
+def ns3d_loss(model, x, y, with_step_error=False):
+    """Space-time loss of the NS-3D training step (reference ns_train_3d.py:53,64): one forward, global relative L2.
+    with_step_error=True: -> (loss, step error), the latter from the same forward's detached output under no_grad (:55-62)."""
     B, S, T_f = x.shape[0], x.shape[1], y.shape[-1]
     out = model(x).view(B, S, S, T_f)
-    return lp_loss_rel_sum(out.reshape(B, -1), y.reshape(B, -1))
+    loss = lp_loss_rel_sum(out.reshape(B, -1), y.reshape(B, -1))
+    if not with_step_error:
+        return loss
+    with torch.no_grad():
+        return loss, ns3d_step_error(out.detach(), y.reshape(B, S, S, T_f))
+
+
+def ns3d_evaluate(model, batches):
+    """Validation pass of the NS-3D loop (reference ns_train_3d.py:82-98): eval mode, no_grad, the per-batch step errors summed on the
+    device (no host synchronisation); the previous training mode is restored.  The caller divides by nval * T_f."""
+    was_training = model.training
+    model.eval()
+    total = None
+    try:
+        with torch.no_grad():
+            for x, y in batches:
+                B, S, T_f = x.shape[0], x.shape[1], y.shape[-1]
+                err = ns3d_step_error(model(x).view(B, S, S, T_f), y.reshape(B, S, S, T_f))
+                total = err if total is None else total + err
+    finally:
+        model.train(was_training)
+    return total
 
 
 class GraphedStep:
