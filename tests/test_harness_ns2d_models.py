@@ -6,11 +6,11 @@ test doubles; -m gpu tests the product path (two-source GELU projection, K11's T
 
 Bounds: 1e-5 for prediction and loss, 5e-4 for the gradient norms - those of tests/test_harness_ns.py for `UNO`, which has the same
 layer kinds (the oracle-block floor measured on the host is 1.4e-7 and 8.3e-6)."""
-import numpy as np
 import pytest
 import torch
 
 from conftest import Case, load_cases, rel_err
+from harness_checks import assert_graphed_step_equals_eager, check_grads, check_init, check_strict_load
 from oracle import spectral_oracle as so
 from uno_amd.harness import UNO_P, UNO_S256, ns2d_rollout_loss
 
@@ -30,42 +30,10 @@ def _build(name, block_cls):
     return c, model, steps
 
 
-def _check_init(model, c):
-    for k, p in model.named_parameters():
-        ck = getattr(c, f"ck64.{k}")
-        q = p.detach().to(torch.complex128 if p.is_complex() else torch.float64)
-        got = np.array([float(q.abs().sum()), float(torch.linalg.vector_norm(q))])
-        assert np.allclose(got, ck, rtol=1e-12), f"seeded init of {k} differs from the reference's"
-    sd = model.state_dict()
-    assert list(sd.keys()) == [str(k) for k in c.sd_keys]
-    for v, row in zip(sd.values(), c.sd_shapes):
-        assert list(v.shape) == [int(d) for d in row if d >= 0]
-
-
-def _check_strict_load(model, c):
-    """a state dict built from the reference's key / shape list loads with strict=True and is what the model then holds"""
-    g = torch.Generator().manual_seed(3)
-    ref = model.state_dict()
-    sd = {str(k): torch.randn(*[int(d) for d in row if d >= 0], generator=g).to(ref[str(k)].dtype) for k, row in zip(c.sd_keys, c.sd_shapes)}
-    twin = type(model)(model.in_width, model.width, pad=model.padding, block_cls=type(model.L0))
-    res = twin.load_state_dict(sd, strict=True)
-    assert not res.missing_keys and not res.unexpected_keys
-    for k, v in twin.state_dict().items():
-        assert torch.equal(v, sd[k]), k
-
-
-def _check_grads(model, c, rtol):
-    gmax = max(float(getattr(c, f"gradnorm.{k}")) for k, _ in model.named_parameters())
-    for k, p in model.named_parameters():
-        ref = float(getattr(c, f"gradnorm.{k}"))
-        got = float(torch.linalg.vector_norm(p.grad))
-        assert abs(got - ref) <= rtol * ref + 1e-5 * gmax, (k, got, ref)
-
-
 def _parity(name, block_cls, dev):
     c, model, steps = _build(name, block_cls)
-    _check_init(model, c)
-    _check_strict_load(model, c)
+    check_init(model, c)
+    check_strict_load(model, c, lambda: type(model)(model.in_width, model.width, pad=model.padding, block_cls=type(model.L0)))
     model = model.to(dev)
     xx, yy = torch.from_numpy(c.xx).to(dev), torch.from_numpy(c.yy).to(dev)
     with torch.no_grad():
@@ -77,7 +45,7 @@ def _parity(name, block_cls, dev):
     print(f"[{name} {dev}] first prediction {e:.2e}, loss {abs(float(loss.detach()) - float(c.loss)) / abs(float(c.loss)):.2e}")
     assert e < TOL_PRED
     assert abs(float(loss.detach()) - float(c.loss)) < TOL_PRED * abs(float(c.loss))
-    _check_grads(model, c, TOL_GRAD)
+    check_grads(model, c, TOL_GRAD)
 
 
 @pytest.mark.parametrize("name", list(CASES))
@@ -116,28 +84,13 @@ def test_graphed_step_equals_eager_step_uno_p():
     """harness.GraphedStep on UNO_P(14, 4), S = 64, batch 2, T_f = 3, two batches: loss, gradients and updated parameters of the replay
     are bit-equal to the eager step's (tests/test_harness_ns.py: test_graphed_step_equals_eager_step) - the two-source projection and its
     fixed-order partial sums included."""
-    from uno_amd.harness import ComplexAdam, GraphedStep
+    from uno_amd.harness import ComplexAdam
     dev = torch.device("cuda:0")
 
-    def make():
+    def make(cap):
         torch.manual_seed(5)
         m = UNO_P(14, 4).to(dev)
         return m, ComplexAdam(m.parameters(), lr=1e-3, weight_decay=1e-4)
     g = torch.Generator().manual_seed(9)
     batches = [(torch.randn(2, 64, 64, 10, generator=g).to(dev), torch.randn(2, 64, 64, 3, generator=g).to(dev)) for _ in range(2)]
-    me, oe = make()
-    mg, og = make()
-    gs = GraphedStep(mg, og, lambda a, b: ns2d_rollout_loss(mg, a, b, T_f=3, step=1), batches[0])
-    # (the capture's warm-up passes have put the graphed model's spectral weight gradients in their time-batched mode: see the UNO test)
-    ns2d_rollout_loss(me, *batches[0], T_f=3, step=1).backward()
-    for xx, yy in batches:
-        oe.zero_grad(set_to_none=True)
-        le = ns2d_rollout_loss(me, xx, yy, T_f=3, step=1)
-        le.backward()
-        ge = {k: p.grad.clone() for k, p in me.named_parameters()}
-        oe.step()
-        lg = gs.step(xx, yy)
-        assert float(lg) == float(le)
-        for (k, pe), (_, pg) in zip(me.named_parameters(), mg.named_parameters()):
-            assert torch.equal(ge[k], pg.grad), k
-            assert torch.equal(pe, pg), k
+    assert_graphed_step_equals_eager(make, lambda m, a, b: ns2d_rollout_loss(m, a, b, T_f=3, step=1), batches)

@@ -6,13 +6,13 @@ doubles here; tests/test_hip_ns3d_models.py runs the product path.
 
 Bounds: 1e-5 for prediction and loss, 5e-4 for the gradient norms - those of test_ns3d_cpu_oracle_blocks (tests/test_harness_ns.py) for
 `Uno3D_T20`, which has the same layer kinds."""
-import numpy as np
 import pytest
 import torch
-import torch.nn as nn
 
 from conftest import Case, load_cases, rel_err
+from harness_checks import check_grads, check_init, check_strict_load
 from oracle import spectral_oracle as so
+from test_model_census_cpu import RecordingBlock, record
 from uno_amd.harness import Uno3D_T9, Uno3D_T10, Uno3D_T20, ns3d_loss
 
 Z10, _ = load_cases("harness_ns3d_t10.npz")
@@ -31,42 +31,10 @@ def build(name, block_cls):
     return c, cls(in_width, width, pad=pad, pad_both=bool(both), **kw), T_f
 
 
-def check_init(model, c):
-    for k, p in model.named_parameters():
-        ck = getattr(c, f"ck64.{k}")
-        q = p.detach().to(torch.complex128 if p.is_complex() else torch.float64)
-        got = np.array([float(q.abs().sum()), float(torch.linalg.vector_norm(q))])
-        assert np.allclose(got, ck, rtol=1e-12), f"seeded init of {k} differs from the reference's"
-    sd = model.state_dict()
-    assert list(sd.keys()) == [str(k) for k in c.sd_keys]
-    for v, row in zip(sd.values(), c.sd_shapes):
-        assert list(v.shape) == [int(d) for d in row if d >= 0]
-
-
-def check_strict_load(model, c):
-    """a state dict built from the reference's key / shape list loads with strict=True and is what the model then holds"""
-    g = torch.Generator().manual_seed(3)
-    ref = model.state_dict()
-    sd = {str(k): torch.randn(*[int(d) for d in row if d >= 0], generator=g).to(ref[str(k)].dtype) for k, row in zip(c.sd_keys, c.sd_shapes)}
-    twin = type(model)(model.in_width, model.width, pad=model.pad, pad_both=model.pad_both, block_cls=type(model.conv0))
-    res = twin.load_state_dict(sd, strict=True)
-    assert not res.missing_keys and not res.unexpected_keys
-    for k, v in twin.state_dict().items():
-        assert torch.equal(v, sd[k]), k
-
-
-def check_grads(model, c, rtol):
-    gmax = max(float(getattr(c, f"gradnorm.{k}")) for k, _ in model.named_parameters())
-    for k, p in model.named_parameters():
-        ref = float(getattr(c, f"gradnorm.{k}"))
-        got = float(torch.linalg.vector_norm(p.grad))
-        assert abs(got - ref) <= rtol * ref + 1e-5 * gmax, (k, got, ref)
-
-
 def parity(name, block_cls, dev, tol_pred, tol_grad):
     c, model, T_f = build(name, block_cls)
     check_init(model, c)
-    check_strict_load(model, c)
+    check_strict_load(model, c, lambda: type(model)(model.in_width, model.width, pad=model.pad, pad_both=model.pad_both, block_cls=type(model.conv0)))
     model = model.to(dev)
     xx, yy = torch.from_numpy(c.xx).to(dev), torch.from_numpy(c.yy).to(dev)
     B, S = xx.shape[0], xx.shape[1]
@@ -95,19 +63,6 @@ def test_both_are_uno3d_t20_with_the_same_constructor_arguments():
         assert m.get_grid.__func__ is Uno3D_T20.get_grid and m._resize is Uno3D_T20._resize
 
 
-class _RecordingBlock(nn.Module):
-    """Stands in for OperatorBlock_3D: records (input grid, output grid, modes) of every call and returns zeros of the output shape."""
-    log = []
-
-    def __init__(self, in_codim, out_codim, dim1, dim2, dim3, modes1, modes2, modes3, Normalize=False, Non_Lin=True):
-        super().__init__()
-        self.out_codim, self.modes = int(out_codim), (modes1, modes2, modes3)
-
-    def forward(self, x, dim1, dim2, dim3):
-        self.log.append((tuple(x.shape[2:]), (dim1, dim2, dim3), self.modes))
-        return x.new_zeros(x.shape[0], self.out_codim, dim1, dim2, dim3)
-
-
 # (Uno3D_T9's conv1 keeps 18 modes on the half grid: S >= 36)
 @pytest.mark.parametrize("cls,T_in,T_out,S", [(Uno3D_T10, 10, 10, 64), (Uno3D_T10, 10, 10, 48), (Uno3D_T10, 10, 10, 32), (Uno3D_T9, 6, 9, 64), (Uno3D_T9, 6, 9, 48)])
 @pytest.mark.parametrize("pad", [0, 2, 3])
@@ -116,13 +71,12 @@ def test_census_every_layer_is_inside_the_pruned_dft_range(cls, T_in, T_out, S, 
     """Every pointwise_op_3D grid pair of both models at S = 64 (and at the fixtures' 48 and 32) is inside the pruned-DFT resampling kernels' range (neither model needs
     the any-grid opt-in that Uno3D_T40 takes), and every SpectralConv3d_Uno call keeps no more modes than its grids hold."""
     from uno_amd.spectral3d import _resample3d_pruned_applies
-    _RecordingBlock.log.clear()
-    model = cls(6, 2, pad=pad, pad_both=both, block_cls=_RecordingBlock)
+    model = record(cls, 6, 2, pad=pad, pad_both=both)
     with torch.no_grad():
         out = model(torch.zeros(1, S, S, T_in, 1))
     if not both:            # (padded on both sides Uno3D_T9 returns 10 steps as the reference does: 6 + 1 + 1 -> int(9 * 8 / 6) = 12, less 1 + 1)
         assert out.shape == (1, S, S, T_out, 1)
-    assert len(_RecordingBlock.log) == 7
-    for din, dout, modes in _RecordingBlock.log:
-        assert _resample3d_pruned_applies(din, dout), (din, dout)
-        so.check_modes_3d(*din, *dout, *modes)
+    assert len(RecordingBlock.calls) == 7
+    for (*_, m1, m2, m3, _norm, _non_lin), ((_c, *din), dout) in zip(RecordingBlock.ctor, RecordingBlock.calls):      # (the blocks are called in construction order)
+        assert _resample3d_pruned_applies(tuple(din), tuple(dout)), (din, dout)
+        so.check_modes_3d(*din, *dout, m1, m2, m3)

@@ -6,6 +6,7 @@ they are derived); 1e-4 for the metric, a sum of ratios of norms of that predict
 import pytest
 import torch
 
+from harness_checks import assert_graphed_step_equals_eager
 from test_harness_ns3d_models import CASES, build, parity
 from uno_amd.harness import Uno3D_T10, ns3d_evaluate, ns3d_loss, ns3d_step_error
 
@@ -56,26 +57,12 @@ def test_evaluate_is_the_sum_of_the_per_batch_metrics():
 def test_graphed_step_equals_eager_step_uno3d_t10():
     """harness.GraphedStep on Uno3D_T10(6, 2, pad=3), S = 32, batch 2, two batches: loss, gradients and updated parameters of the replay
     are bit-equal to the eager step's (the pattern of test_graphed_step_equals_eager_step_uno_p, tests/test_harness_ns2d_models.py)."""
-    from uno_amd.harness import ComplexAdam, GraphedStep
+    from uno_amd.harness import ComplexAdam
 
-    def make():
+    def make(cap):
         torch.manual_seed(5)
         m = Uno3D_T10(6, 2, pad=3).to(dev())
         return m, ComplexAdam(m.parameters(), lr=1e-3, weight_decay=1e-4)
     g = torch.Generator().manual_seed(9)
     batches = [(torch.randn(2, 32, 32, 10, 1, generator=g).to(dev()), torch.randn(2, 32, 32, 10, generator=g).to(dev())) for _ in range(2)]
-    me, oe = make()
-    mg, og = make()
-    gs = GraphedStep(mg, og, lambda a, b: ns3d_loss(mg, a, b), batches[0])
-    ns3d_loss(me, *batches[0]).backward()           # (as the capture's warm-up passes: the first backward pass of a model is set-up too)
-    for xx, yy in batches:
-        oe.zero_grad(set_to_none=True)
-        le = ns3d_loss(me, xx, yy)
-        le.backward()
-        ge = {k: p.grad.clone() for k, p in me.named_parameters()}
-        oe.step()
-        lg = gs.step(xx, yy)
-        assert float(lg) == float(le)
-        for (k, pe), (_, pg) in zip(me.named_parameters(), mg.named_parameters()):
-            assert torch.equal(ge[k], pg.grad), k
-            assert torch.equal(pe, pg), k
+    assert_graphed_step_equals_eager(make, ns3d_loss, batches)

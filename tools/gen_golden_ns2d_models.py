@@ -2,7 +2,7 @@
 
 Development machine only (it imports the reference checkout, which never enters this repository and never travels to the GPU box):
 
-    python tools/gen_golden_ns2d_models.py [--ref /root/reference] [--out tests/golden]
+    python tools/gen_golden_ns2d_models.py --ref <reference checkout> [--out tests/golden]
 
 Writes tests/golden/harness_ns2d_p.npz and tests/golden/harness_ns2d_s256.npz in the format of harness_ns.npz
 (oracle/gen_golden.py, ns2d_case): per case `<case>.<field>` with
@@ -18,10 +18,11 @@ from __future__ import annotations
 
 import argparse
 import os
-import sys
 
 import numpy as np
 import torch
+
+from _reference import import_reference
 
 # (file, case, class, (in_width, width, pad), model seed, data seed, S, T_in, steps)
 CASES = [
@@ -67,21 +68,13 @@ def case(n2, LpLoss, name, cls, ctor, seed, data_seed, S, T_in, steps):
 def main():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     ap = argparse.ArgumentParser()
-    ap.add_argument("--ref", default="/root/reference")
+    ap.add_argument("--ref", required=True, help="the reference checkout (development machine only)")
     ap.add_argument("--out", default=os.path.join(root, "tests", "golden"))
     args = ap.parse_args()
-    if not os.path.isdir(args.ref):
-        sys.exit(f"reference checkout not found at {args.ref}; golden vectors can only be regenerated on the development machine")
-    sys.path.insert(0, args.ref)
-    os.environ.setdefault("MPLBACKEND", "Agg")
-    cwd = os.getcwd()
-    os.chdir("/tmp")                        # (the reference's modules write nothing, but they import from the working directory first)
-    import navier_stokes_uno2d as n2        # the genuine reference module
-    from utilities3 import LpLoss
-    os.chdir(cwd)
+    n2, utilities3 = import_reference(args.ref, "navier_stokes_uno2d", "utilities3")
     files = {}
     for fname, *row in CASES:
-        files.setdefault(fname, {}).update(case(n2, LpLoss, *row))
+        files.setdefault(fname, {}).update(case(n2, utilities3.LpLoss, *row))
     for fname, z in files.items():
         path = os.path.join(args.out, fname)
         np.savez_compressed(path, **z)

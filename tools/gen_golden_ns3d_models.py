@@ -23,10 +23,11 @@ from __future__ import annotations
 
 import argparse
 import os
-import sys
 
 import numpy as np
 import torch
+
+from _reference import import_reference
 
 # (file, case, class, (in_width, width, pad, pad_both), model seed, data seed, S, batch, T_in, T_f)
 # Uno3D_T9's conv1 keeps 18 modes on the half grid: the reference raises below S = 36, hence S = 48
@@ -91,18 +92,10 @@ def main():
     ap.add_argument("--ref", required=True, help="the reference checkout (development machine only)")
     ap.add_argument("--out", default=os.path.join(root, "tests", "golden"))
     args = ap.parse_args()
-    if not os.path.isdir(args.ref):
-        sys.exit(f"reference checkout not found at {args.ref}; golden vectors can only be regenerated on the development machine")
-    sys.path.insert(0, args.ref)
-    os.environ.setdefault("MPLBACKEND", "Agg")
-    cwd = os.getcwd()
-    os.chdir("/tmp")                        # (the reference's modules write nothing, but they import from the working directory first)
-    import navier_stokes_uno3d as n3        # the genuine reference module
-    from utilities3 import LpLoss
-    os.chdir(cwd)
+    n3, utilities3 = import_reference(args.ref, "navier_stokes_uno3d", "utilities3")
     files = {}
     for fname, *row in CASES:
-        files.setdefault(fname, {}).update(case(n3, LpLoss, *row))
+        files.setdefault(fname, {}).update(case(n3, utilities3.LpLoss, *row))
     for fname, z in files.items():
         path = os.path.join(args.out, fname)
         np.savez_compressed(path, **z)

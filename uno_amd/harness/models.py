@@ -20,6 +20,22 @@ from ..integral_operators import (GradJoin, OperatorBlock_2D, OperatorBlock_3D, 
                                   lift_gelu_pad)
 
 
+def _block_cat(block, xs, *dims):
+    """block(torch.cat(xs, dim=1), *dims); product blocks take the sources as they are."""
+    if hasattr(block, "forward_cat"):
+        return block.forward_cat(xs, *dims)
+    return block(torch.cat(list(xs), dim=1), *dims)
+
+
+def _cached(cache: dict, key, build):
+    grid = cache.get(key)
+    if grid is None:
+        grid = build()
+        cache.clear()
+        cache[key] = grid
+    return grid
+
+
 class UNO_9(nn.Module):
     """in_width = 3 ([a(x,y), x, y]); width = lifted channel count; pad = domain padding (scaled by
     ceil(S/85)); factor = channel growth per level.  Input (B, S, S, 1) -> output (B, S, S, 1)."""
@@ -43,15 +59,12 @@ class UNO_9(nn.Module):
         self._grid_cache = {}
 
     def get_grid(self, shape, device):
-        key = (tuple(shape[:3]), str(device))
-        grid = self._grid_cache.get(key)
-        if grid is None:
+        def build():
             b, sx, sy = shape[0], shape[1], shape[2]
             gx = torch.linspace(0, 1, sx, dtype=torch.float64).to(torch.float32).reshape(1, sx, 1, 1).expand(b, sx, sy, 1)
             gy = torch.linspace(0, 1, sy, dtype=torch.float64).to(torch.float32).reshape(1, 1, sy, 1).expand(b, sx, sy, 1)
-            grid = torch.cat((gx, gy), dim=-1).contiguous().to(device)
-            self._grid_cache = {key: grid}
-        return grid
+            return torch.cat((gx, gy), dim=-1).contiguous().to(device)
+        return _cached(self._grid_cache, (tuple(shape[:3]), str(device)), build)
 
     def forward(self, x):
         S1, S2 = x.shape[1], x.shape[2]
@@ -95,43 +108,34 @@ class UNO_9(nn.Module):
         return out[:, :, :S1, :S2].permute(0, 2, 3, 1).contiguous()     # crop the padding, back to (B, S, S, 1) (one channel: tiny)
 
 
-def _block_cat(block, xs, *dims):
-    """block(torch.cat(xs, dim=1), *dims); product blocks take the sources as they are."""
-    if hasattr(block, "forward_cat"):
-        return block.forward_cat(xs, *dims)
-    return block(torch.cat(list(xs), dim=1), *dims)
-
-
-def _cached(cache: dict, key, build):
-    grid = cache.get(key)
-    if grid is None:
-        grid = build()
-        cache.clear()
-        cache[key] = grid
-    return grid
-
-
 class UNO(nn.Module):
     """Navier-Stokes 2-D U-NO (7 blocks, channel growth factor 3/4) - own counterpart of the reference's
     `UNO` (navier_stokes_uno2d.py:145-238): one autoregressive step (B, S, S, T_in) -> (B, S, S, 1).  Input
     channels = T_in + 4 positional features (sin/cos of the two coordinates, :229-238).  Sub-module names and
-    registration order follow the reference (state_dict compatible).  Channels-first lift/projection as in UNO_9."""
+    registration order follow the reference (state_dict compatible).  Channels-first lift/projection as in UNO_9.
+
+    The NS-2-D family is this class: `UNO_P` and `UNO_S256` contribute their table of blocks, their widths around the U and their
+    grids; constructor and forward pass are said here once."""
+
+    # (dim1, dim2, modes1, modes2) of L0 .. L6: the default grids are overridden at call time, the modes are fixed
+    _BLOCKS = ((48, 48, 22, 22), (32, 32, 14, 14), (16, 16, 6, 6), (16, 16, 6, 6), (32, 32, 6, 6), (48, 48, 14, 14), (64, 64, 22, 22))
+    _LIFT = None            # width of the first lift layer (None: width // 2)
+    _FC1 = 4                # fc1 = Linear(2w, _FC1 * w)
+    _TWO_SOURCE = False     # fc2 also reads the first lift activation, and the padding is cropped on both sides (UNO_P)
 
     def __init__(self, in_width, width, pad=0, factor=3 / 4, block_cls=OperatorBlock_2D):
         super().__init__()
         self.in_width, self.width, self.factor, self.padding = in_width, width, factor, pad
         w, f = width, factor
-        self.fc = nn.Linear(in_width, w // 2)
-        self.fc0 = nn.Linear(w // 2, w)
-        self.L0 = block_cls(w, 2 * f * w, 48, 48, 22, 22)
-        self.L1 = block_cls(2 * f * w, 4 * f * w, 32, 32, 14, 14)
-        self.L2 = block_cls(4 * f * w, 8 * f * w, 16, 16, 6, 6)
-        self.L3 = block_cls(8 * f * w, 8 * f * w, 16, 16, 6, 6)
-        self.L4 = block_cls(8 * f * w, 4 * f * w, 32, 32, 6, 6)
-        self.L5 = block_cls(8 * f * w, 2 * f * w, 48, 48, 14, 14)
-        self.L6 = block_cls(4 * f * w, w, 64, 64, 22, 22)
-        self.fc1 = nn.Linear(2 * w, 4 * w)
-        self.fc2 = nn.Linear(4 * w, 1)
+        lift = w // 2 if self._LIFT is None else self._LIFT
+        self.fc = nn.Linear(in_width, lift)
+        self.fc0 = nn.Linear(lift, w)
+        cin = (w, 2 * f * w, 4 * f * w, 8 * f * w, 8 * f * w, 8 * f * w, 4 * f * w)
+        cout = (2 * f * w, 4 * f * w, 8 * f * w, 8 * f * w, 4 * f * w, 2 * f * w, w)
+        for i, row in enumerate(self._BLOCKS):
+            setattr(self, f"L{i}", block_cls(cin[i], cout[i], *row))
+        self.fc1 = nn.Linear(2 * w, self._FC1 * w)
+        self.fc2 = nn.Linear(self._FC1 * w + (lift if self._TWO_SOURCE else 0), 1)
         self._grid_cache = {}
 
     def get_grid(self, shape, device):
@@ -142,6 +146,11 @@ class UNO(nn.Module):
             return torch.cat((torch.sin(gx), torch.sin(gy), torch.cos(gx), torch.cos(gy)), dim=-1).contiguous().to(device)
         return _cached(self._grid_cache, (tuple(shape[:3]), str(device)), build)
 
+    def _grids(self, d1, d2):
+        """output grids of L0 .. L6 from the padded grid"""
+        a, b, c = (int(d1 * self.factor), int(d2 * self.factor)), (d1 // 2, d2 // 2), (d1 // 4, d2 // 4)
+        return a, b, c, c, b, a, (d1, d2)
+
     def forward(self, x):
         # channels-first input in ONE pass: the cat kernel reads the permuted view of x and the (cached, channels-first) grid features
         z = torch.cat((x.permute(0, 3, 1, 2), self.get_grid(x.shape, x.device).permute(0, 3, 1, 2)), dim=1)
@@ -150,33 +159,34 @@ class UNO(nn.Module):
     def forward_cf(self, x):
         """(B, T_in + 4, S, S) channels-first window + positional features -> (B, 1, S, S).  The roll-out keeps its window in this
         layout (harness.ns2d_rollout_loss): one concatenation per step instead of one for the window and one for the layout."""
-        lifted = F.gelu(gelu_channel_mix(channel_mix(x, self.fc.weight, self.fc.bias), self.fc0.weight, self.fc0.bias))
+        h = channel_mix(x, self.fc.weight, self.fc.bias)            # kept PRE-activation: fc0 (and a two-source fc2) apply the GELU as they read it
+        lifted = F.gelu(gelu_channel_mix(h, self.fc0.weight, self.fc0.bias))
         p = self.padding
         if p != 0:              # (F.pad with zero widths still copies the tensor: 40 copies per roll-out)
             lifted = F.pad(lifted, [p, p, p, p])
-        d1, d2 = lifted.shape[-2], lifted.shape[-1]
+        g = self._grids(lifted.shape[-2], lifted.shape[-1])
+        c0 = self.L0(lifted, *g[0])
+        c1 = self.L1(c0, *g[1])
         if hasattr(self.L6, "forward_cat") and all(b.non_lin and not b.normalize for b in (self.L2, self.L3)):
             # c2 and c3 have ONE consumer each: that block applies gelu'(pre) of its producer in the kernel that completes the
             # gradient (`out_join`, as in UNO_9) - no separate GELU-backward pass for L2 / L3.  (The skip tensors are NOT joined
             # here the way UNO_9 joins them: at 64^2 x 32 samples every kernel of this model is a 10-30 us launch and the joined
             # form trades two big element-wise sums for more small launches - measured 81.4 -> 84.3 ms per step.)
             j2, j3 = GradJoin(), GradJoin()
-            c0 = self.L0(lifted, int(d1 * self.factor), int(d2 * self.factor))
-            c1 = self.L1(c0, d1 // 2, d2 // 2)
-            c2 = self.L2(c1, d1 // 4, d2 // 4, out_join=j2)
-            c3 = self.L3(c2, d1 // 4, d2 // 4, join=j2, out_join=j3)
-            c4 = torch.cat([self.L4(c3, d1 // 2, d2 // 2, join=j3), c1], dim=1)
+            c2 = self.L2(c1, *g[2], out_join=j2)
+            c3 = self.L3(c2, *g[3], join=j2, out_join=j3)
+            c4 = self.L4(c3, *g[4], join=j3)
         else:
-            c0 = self.L0(lifted, int(d1 * self.factor), int(d2 * self.factor))
-            c1 = self.L1(c0, d1 // 2, d2 // 2)
-            c2 = self.L2(c1, d1 // 4, d2 // 4)
-            c3 = self.L3(c2, d1 // 4, d2 // 4)
-            c4 = torch.cat([self.L4(c3, d1 // 2, d2 // 2), c1], dim=1)
-        c5 = torch.cat([self.L5(c4, int(d1 * self.factor), int(d2 * self.factor)), c0], dim=1)
-        c6 = torch.cat([self.L6(c5, d1, d2), lifted], dim=1)
-        if p != 0:      # the reference pads both sides but crops one (navier_stokes_uno2d.py:201,217-218); kept
-            c6 = c6[..., :-p, :-p]
-        return gelu_project(channel_mix(c6.contiguous(), self.fc1.weight, self.fc1.bias), self.fc2.weight, self.fc2.bias)
+            c4 = self.L4(self.L3(self.L2(c1, *g[2]), *g[3]), *g[4])
+        c4 = torch.cat([c4, c1], dim=1)
+        c5 = torch.cat([self.L5(c4, *g[5]), c0], dim=1)
+        c6 = torch.cat([self.L6(c5, *g[6]), lifted], dim=1)
+        if p != 0:      # the reference's `UNO` pads both sides but crops one (navier_stokes_uno2d.py:201,217-218); kept
+            c6 = c6[..., p:-p, p:-p] if self._TWO_SOURCE else c6[..., :-p, :-p]
+        out = channel_mix(c6.contiguous(), self.fc1.weight, self.fc1.bias)
+        if self._TWO_SOURCE:
+            return gelu_project2(out, h, self.fc2.weight, self.fc2.bias, act2=True)
+        return gelu_project(out, self.fc2.weight, self.fc2.bias)
 
 
 class UNO_P(UNO):
@@ -186,50 +196,16 @@ class UNO_P(UNO):
     (gelu_project2) on fc1's output and fc's kept pre-activation; the concatenation is never built.  The padding is cropped on both
     sides (:116-117).  Sub-module names, registration order and `get_grid` follow the reference (state_dict compatible)."""
 
+    _BLOCKS = ((32, 32, 14, 14), (16, 16, 6, 6), (8, 8, 3, 3), (8, 8, 3, 3), (16, 16, 3, 3), (32, 32, 6, 6), (64, 64, 14, 14))
+    _FC1, _TWO_SOURCE = 3, True
     # output grid of L0 .. L6 as divisors of the padded grid (reference :99-113)
     _DIV = (2, 4, 8, 8, 4, 2, 1)
 
     def __init__(self, in_width, width, pad=0, factor=1, block_cls=OperatorBlock_2D):
-        nn.Module.__init__(self)
-        self.in_width, self.width, self.factor, self.padding = in_width, width, factor, pad
-        w, f = width, factor
-        self.fc = nn.Linear(in_width, w // 2)
-        self.fc0 = nn.Linear(w // 2, w)
-        self.L0 = block_cls(w, 2 * f * w, 32, 32, 14, 14)
-        self.L1 = block_cls(2 * f * w, 4 * f * w, 16, 16, 6, 6)
-        self.L2 = block_cls(4 * f * w, 8 * f * w, 8, 8, 3, 3)
-        self.L3 = block_cls(8 * f * w, 8 * f * w, 8, 8, 3, 3)
-        self.L4 = block_cls(8 * f * w, 4 * f * w, 16, 16, 3, 3)
-        self.L5 = block_cls(8 * f * w, 2 * f * w, 32, 32, 6, 6)
-        self.L6 = block_cls(4 * f * w, w, 64, 64, 14, 14)
-        self.fc1 = nn.Linear(2 * w, 3 * w)
-        self.fc2 = nn.Linear(3 * w + w // 2, 1)
-        self._grid_cache = {}
+        super().__init__(in_width, width, pad, factor, block_cls)
 
-    def forward_cf(self, x):
-        """(B, T_in + 4, S, S) channels-first window + positional features -> (B, 1, S, S), as UNO.forward_cf."""
-        h = channel_mix(x, self.fc.weight, self.fc.bias)            # kept PRE-activation: fc0 and fc2 apply the GELU as they read it
-        lifted = F.gelu(gelu_channel_mix(h, self.fc0.weight, self.fc0.bias))
-        p = self.padding
-        if p != 0:
-            lifted = F.pad(lifted, [p, p, p, p])
-        d1, d2 = lifted.shape[-2], lifted.shape[-1]
-        g = [(d1 // k, d2 // k) for k in self._DIV]
-        c0 = self.L0(lifted, *g[0])
-        c1 = self.L1(c0, *g[1])
-        if hasattr(self.L6, "forward_cat") and all(b.non_lin and not b.normalize for b in (self.L2, self.L3)):
-            j2, j3 = GradJoin(), GradJoin()         # c2, c3 have one consumer each: gelu'(pre) in the consumer's last kernel (see UNO)
-            c2 = self.L2(c1, *g[2], out_join=j2)
-            c3 = self.L3(c2, *g[3], join=j2, out_join=j3)
-            c4 = torch.cat([self.L4(c3, *g[4], join=j3), c1], dim=1)
-        else:
-            c3 = self.L3(self.L2(c1, *g[2]), *g[3])
-            c4 = torch.cat([self.L4(c3, *g[4]), c1], dim=1)
-        c5 = torch.cat([self.L5(c4, *g[5]), c0], dim=1)
-        c6 = torch.cat([self.L6(c5, *g[6]), lifted], dim=1)
-        if p != 0:
-            c6 = c6[..., p:-p, p:-p]
-        return gelu_project2(channel_mix(c6.contiguous(), self.fc1.weight, self.fc1.bias), h, self.fc2.weight, self.fc2.bias, act2=True)
+    def _grids(self, d1, d2):
+        return [(d1 // k, d2 // k) for k in self._DIV]
 
 
 class UNO_S256(UNO_P):
@@ -237,45 +213,52 @@ class UNO_S256(UNO_P):
     `UNO_P`'s structure with grids D/4, D/16, D/32 and back (4x contraction and expansion per level), modes up to (32, 33), and a first
     lift layer of 16 channels whatever the width (fc2 = Linear(3w + 16, 1))."""
 
+    _BLOCKS = ((64, 64, 32, 33), (16, 16, 8, 9), (8, 8, 4, 5), (8, 8, 4, 5), (16, 16, 4, 5), (64, 64, 8, 9), (256, 256, 32, 32))
+    _LIFT = 16
     _DIV = (4, 16, 32, 32, 16, 4, 1)
 
-    def __init__(self, in_width, width, pad=0, factor=1, block_cls=OperatorBlock_2D):
-        nn.Module.__init__(self)
-        self.in_width, self.width, self.factor, self.padding = in_width, width, factor, pad
-        w, f = width, factor
-        self.fc = nn.Linear(in_width, 16)
-        self.fc0 = nn.Linear(16, w)
-        self.L0 = block_cls(w, 2 * f * w, 64, 64, 32, 33)
-        self.L1 = block_cls(2 * f * w, 4 * f * w, 16, 16, 8, 9)
-        self.L2 = block_cls(4 * f * w, 8 * f * w, 8, 8, 4, 5)
-        self.L3 = block_cls(8 * f * w, 8 * f * w, 8, 8, 4, 5)
-        self.L4 = block_cls(8 * f * w, 4 * f * w, 16, 16, 4, 5)
-        self.L5 = block_cls(8 * f * w, 2 * f * w, 64, 64, 8, 9)
-        self.L6 = block_cls(4 * f * w, w, 256, 256, 32, 32)
-        self.fc1 = nn.Linear(2 * w, 3 * w)
-        self.fc2 = nn.Linear(3 * w + 16, 1)
-        self._grid_cache = {}
+
+def _grids3d(d1, d2, bottom, times):
+    """Output grids of conv0 .. conv8 of the 3-D models: space contracts to 3/4, 1/2, 1/4 and `bottom` of the padded grid and expands
+    back over the same levels; `times` is the time length per block."""
+    a, b, c = (int(3 * d1 / 4), int(3 * d2 / 4)), (d1 // 2, d2 // 2), (d1 // 4, d2 // 4)
+    return [(*s, t) for s, t in zip((a, b, c, bottom, b, a, (d1, d2)), times)]
 
 
 class Uno3D_T20(nn.Module):
     """Navier-Stokes 3-D (space-time) U-NO mapping 10 input steps to 20 output steps - own counterpart of the
     reference's `Uno3D_T20` (navier_stokes_uno3d.py:239-409): 7 OperatorBlock_3D that also stretch the time axis,
     skip connections through (identity) trilinear resizes, time-axis padding int(pad * 0.1 * T).
-    Input (B, S, S, T, 1) -> output (B, S, S, 2T, 1); in_width = 1 + 5 positional features."""
+    Input (B, S, S, T, 1) -> output (B, S, S, 2T, 1); in_width = 1 + 5 positional features.
+
+    The NS-3-D family is this class: `Uno3D_T10`, `Uno3D_T9` and `Uno3D_T40` contribute their table of blocks, the width of their
+    first lift layer and their plan of grids; constructor and forward pass are said here once."""
+
+    _NAMES = ("conv0", "conv1", "conv2", "conv3", "conv6", "conv7", "conv8")
+    # (dim1, dim2, dim3, modes1, modes2, modes3) of conv0 .. conv8: the default grids are overridden at call time, the modes are fixed
+    _BLOCKS = ((48, 48, 10, 22, 22, 5), (32, 32, 10, 14, 14, 5), (16, 16, 12, 6, 6, 5), (16, 16, 12, 6, 6, 6), (32, 32, 18, 6, 6, 6),
+               (48, 48, 20, 14, 14, 8), (64, 64, 20, 22, 22, 8))
+
+    @staticmethod
+    def _lift_width(in_width, width):
+        return in_width * 2
+
+    @staticmethod
+    def _plan(d1, d2, d3, padding):
+        """the output grids of conv0 .. conv8 and the crop of the time axis, from the padded grid and the padding"""
+        return _grids3d(d1, d2, (d1 // 4, d2 // 4), (d3, d3, int(d3 * 1.2), int(d3 * 1.2), int(d3 * 1.8), int(2.0 * d3), 2 * d3)), 2 * padding
 
     def __init__(self, in_width, width, pad=2, factor=1, pad_both=False, block_cls=OperatorBlock_3D):
         super().__init__()
         self.in_width, self.width, self.pad, self.pad_both = in_width, width, pad, pad_both
         w, f = width, factor
-        self.fc = nn.Linear(in_width, in_width * 2)
-        self.fc0 = nn.Linear(in_width * 2, w)
-        self.conv0 = block_cls(w, 2 * f * w, 48, 48, 10, 22, 22, 5, Normalize=True)
-        self.conv1 = block_cls(2 * f * w, 4 * f * w, 32, 32, 10, 14, 14, 5)
-        self.conv2 = block_cls(4 * f * w, 8 * f * w, 16, 16, 12, 6, 6, 5)
-        self.conv3 = block_cls(8 * f * w, 16 * f * w, 16, 16, 12, 6, 6, 6, Normalize=True)
-        self.conv6 = block_cls(16 * f * w, 4 * f * w, 32, 32, 18, 6, 6, 6)
-        self.conv7 = block_cls(8 * f * w, 2 * f * w, 48, 48, 20, 14, 14, 8, Normalize=True)
-        self.conv8 = block_cls(4 * f * w, 2 * w, 64, 64, 20, 22, 22, 8)
+        lift = self._lift_width(in_width, w)
+        self.fc = nn.Linear(in_width, lift)
+        self.fc0 = nn.Linear(lift, w)
+        cin = (w, 2 * f * w, 4 * f * w, 8 * f * w, 16 * f * w, 8 * f * w, 4 * f * w)
+        cout = (2 * f * w, 4 * f * w, 8 * f * w, 16 * f * w, 4 * f * w, 2 * f * w, 2 * w)
+        for i, (name, row) in enumerate(zip(self._NAMES, self._BLOCKS)):
+            setattr(self, name, block_cls(cin[i], cout[i], *row, Normalize=name in ("conv0", "conv3", "conv7")))
         self.fc1 = nn.Linear(3 * w, 4 * w)
         self.fc2 = nn.Linear(4 * w, 1)
         self._grid_cache = {}
@@ -302,19 +285,19 @@ class Uno3D_T20(nn.Module):
         lifted = F.gelu(gelu_channel_mix(channel_mix(x, self.fc.weight, self.fc.bias), self.fc0.weight, self.fc0.bias))
         self.padding = int(self.pad * 0.1 * lifted.shape[-1])
         lifted = F.pad(lifted, [self.padding, self.padding, 0, 0, 0, 0] if self.pad_both else [0, self.padding, 0, 0, 0, 0])
-        d1, d2, d3 = lifted.shape[-3:]
-        c0 = self.conv0(lifted, int(3 * d1 / 4), int(3 * d2 / 4), d3)
-        c1 = self.conv1(c0, d1 // 2, d2 // 2, d3)
-        c2 = self.conv2(c1, d1 // 4, d2 // 4, int(d3 * 1.2))
-        c3 = self.conv3(c2, d1 // 4, d2 // 4, int(d3 * 1.2))
-        c6 = self.conv6(c3, d1 // 2, d2 // 2, int(d3 * 1.8))
+        g, crop = self._plan(*lifted.shape[-3:], self.padding)
+        c0 = self.conv0(lifted, *g[0])
+        c1 = self.conv1(c0, *g[1])
+        c2 = self.conv2(c1, *g[2])
+        c3 = self.conv3(c2, *g[3])
+        c6 = self.conv6(c3, *g[4])
         c6 = torch.cat([c6, self._resize(c1, c6)], dim=1)
-        c7 = self.conv7(c6, int(3 * d1 / 4), int(3 * d2 / 4), int(2.0 * d3))
+        c7 = self.conv7(c6, *g[5])
         c7 = torch.cat([c7, self._resize(c0, c7)], dim=1)
-        c8 = self.conv8(c7, d1, d2, 2 * d3)
+        c8 = self.conv8(c7, *g[6])
         c8 = torch.cat([c8, self._resize(lifted, c8)], dim=1)
-        if self.padding != 0:
-            c8 = c8[..., 2 * self.padding:-2 * self.padding] if self.pad_both else c8[..., :-2 * self.padding]
+        if self.padding != 0:           # (the crop is written from `padding` as the reference writes it: -0 would empty the tensor)
+            c8 = c8[..., crop:-crop] if self.pad_both else c8[..., :-crop]
         out = gelu_project(channel_mix(c8.contiguous(), self.fc1.weight, self.fc1.bias), self.fc2.weight, self.fc2.bias)
         return out.permute(0, 2, 3, 4, 1).contiguous()
 
@@ -325,49 +308,12 @@ class Uno3D_T10(Uno3D_T20):
     (5 time modes everywhere) and a `padding` crop.  Input (B, S, S, T, 1) -> output (B, S, S, T, 1).  Every layer's grid pair is
     inside the pruned-DFT kernels' range at S <= 64 (tests/test_harness_ns3d_models.py holds the census)."""
 
-    def __init__(self, in_width, width, pad=2, factor=1, pad_both=False, block_cls=OperatorBlock_3D):
-        nn.Module.__init__(self)
-        self.in_width, self.width, self.pad, self.pad_both = in_width, width, pad, pad_both
-        w, f = width, factor
-        self.fc = nn.Linear(in_width, in_width * 2)
-        self.fc0 = nn.Linear(in_width * 2, w)
-        self.conv0 = block_cls(w, 2 * f * w, 48, 48, 10, 22, 22, 5, Normalize=True)
-        self.conv1 = block_cls(2 * f * w, 4 * f * w, 32, 32, 10, 14, 14, 5)
-        self.conv2 = block_cls(4 * f * w, 8 * f * w, 16, 16, 10, 6, 6, 5)
-        self.conv3 = block_cls(8 * f * w, 16 * f * w, 16, 16, 10, 6, 6, 5, Normalize=True)
-        self.conv6 = block_cls(16 * f * w, 4 * f * w, 32, 32, 10, 6, 6, 5)
-        self.conv7 = block_cls(8 * f * w, 2 * f * w, 48, 48, 10, 14, 14, 5, Normalize=True)
-        self.conv8 = block_cls(4 * f * w, 2 * w, 64, 64, 10, 22, 22, 5)
-        self.fc1 = nn.Linear(3 * w, 4 * w)
-        self.fc2 = nn.Linear(4 * w, 1)
-        self._grid_cache = {}
+    _BLOCKS = ((48, 48, 10, 22, 22, 5), (32, 32, 10, 14, 14, 5), (16, 16, 10, 6, 6, 5), (16, 16, 10, 6, 6, 5), (32, 32, 10, 6, 6, 5),
+               (48, 48, 10, 14, 14, 5), (64, 64, 10, 22, 22, 5))
 
-    # time length of conv2, conv3, conv6, conv7, conv8 and the crop, from the padded input length d3 / the padding
     @staticmethod
-    def _time_plan(d3, padding):
-        return (d3, d3, d3, d3, d3), padding
-
-    def forward(self, x):
-        x = torch.cat((x, self.get_grid(x.shape, x.device)), dim=-1).permute(0, 4, 1, 2, 3).contiguous()
-        lifted = F.gelu(gelu_channel_mix(channel_mix(x, self.fc.weight, self.fc.bias), self.fc0.weight, self.fc0.bias))
-        self.padding = int(self.pad * 0.1 * lifted.shape[-1])
-        lifted = F.pad(lifted, [self.padding, self.padding, 0, 0, 0, 0] if self.pad_both else [0, self.padding, 0, 0, 0, 0])
-        d1, d2, d3 = lifted.shape[-3:]
-        (t2, t3, t6, t7, t8), crop = self._time_plan(d3, self.padding)
-        c0 = self.conv0(lifted, int(3 * d1 / 4), int(3 * d2 / 4), d3)
-        c1 = self.conv1(c0, d1 // 2, d2 // 2, d3)
-        c2 = self.conv2(c1, d1 // 4, d2 // 4, t2)
-        c3 = self.conv3(c2, d1 // 4, d2 // 4, t3)
-        c6 = self.conv6(c3, d1 // 2, d2 // 2, t6)
-        c6 = torch.cat([c6, self._resize(c1, c6)], dim=1)
-        c7 = self.conv7(c6, int(3 * d1 / 4), int(3 * d2 / 4), t7)
-        c7 = torch.cat([c7, self._resize(c0, c7)], dim=1)
-        c8 = self.conv8(c7, d1, d2, t8)
-        c8 = torch.cat([c8, self._resize(lifted, c8)], dim=1)
-        if self.padding != 0:           # (the crop is written from `padding` as the reference writes it: -0 would empty the tensor)
-            c8 = c8[..., crop:-crop] if self.pad_both else c8[..., :-crop]
-        out = gelu_project(channel_mix(c8.contiguous(), self.fc1.weight, self.fc1.bias), self.fc2.weight, self.fc2.bias)
-        return out.permute(0, 2, 3, 4, 1).contiguous()
+    def _plan(d1, d2, d3, padding):
+        return _grids3d(d1, d2, (d1 // 4, d2 // 4), (d3,) * 7), padding
 
 
 class Uno3D_T9(Uno3D_T10):
@@ -376,26 +322,13 @@ class Uno3D_T9(Uno3D_T10):
     to int(8 * d3 / 6) at conv3 / conv6 and int(9 * d3 / 6) at conv7 / conv8, and an int(9 * padding / 6) crop.  Input
     (B, S, S, 6, 1) -> output (B, S, S, 9, 1).  conv1 keeps 18 modes on the half grid, so S >= 36 (the reference raises below)."""
 
-    def __init__(self, in_width, width, pad=2, factor=1, pad_both=False, block_cls=OperatorBlock_3D):
-        nn.Module.__init__(self)
-        self.in_width, self.width, self.pad, self.pad_both = in_width, width, pad, pad_both
-        w, f = width, factor
-        self.fc = nn.Linear(in_width, in_width * 2)
-        self.fc0 = nn.Linear(in_width * 2, w)
-        self.conv0 = block_cls(w, 2 * f * w, 48, 48, 6, 20, 20, 3, Normalize=True)
-        self.conv1 = block_cls(2 * f * w, 4 * f * w, 32, 32, 6, 18, 18, 3)
-        self.conv2 = block_cls(4 * f * w, 8 * f * w, 16, 16, 6, 6, 6, 3)
-        self.conv3 = block_cls(8 * f * w, 16 * f * w, 16, 16, 8, 6, 6, 3, Normalize=True)
-        self.conv6 = block_cls(16 * f * w, 4 * f * w, 32, 32, 8, 6, 6, 3)
-        self.conv7 = block_cls(8 * f * w, 2 * f * w, 48, 48, 9, 14, 14, 3, Normalize=True)
-        self.conv8 = block_cls(4 * f * w, 2 * w, 64, 64, 9, 20, 20, 4)
-        self.fc1 = nn.Linear(3 * w, 4 * w)
-        self.fc2 = nn.Linear(4 * w, 1)
-        self._grid_cache = {}
+    _BLOCKS = ((48, 48, 6, 20, 20, 3), (32, 32, 6, 18, 18, 3), (16, 16, 6, 6, 6, 3), (16, 16, 8, 6, 6, 3), (32, 32, 8, 6, 6, 3),
+               (48, 48, 9, 14, 14, 3), (64, 64, 9, 20, 20, 4))
 
     @staticmethod
-    def _time_plan(d3, padding):
-        return (d3, int(8 * d3 / 6), int(8 * d3 / 6), int(9 * d3 / 6), int(9 * d3 / 6)), int(9 * padding / 6)
+    def _plan(d1, d2, d3, padding):
+        times = (d3, d3, d3, int(8 * d3 / 6), int(8 * d3 / 6), int(9 * d3 / 6), int(9 * d3 / 6))
+        return _grids3d(d1, d2, (d1 // 4, d2 // 4), times), int(9 * padding / 6)
 
 
 class Uno3D_T40(Uno3D_T20):
@@ -406,44 +339,20 @@ class Uno3D_T40(Uno3D_T20):
     (64,64,52) at S = 64, pad 3): on product blocks the model opts its point-wise layers into the any-grid kernels, and with
     `one_buffer_any=True` its blocks into the one-buffer form on those grids (enable_one_buffer_any_grid)."""
 
+    _BLOCKS = ((48, 48, 10, 20, 20, 4), (32, 32, 10, 14, 14, 4), (16, 16, 16, 6, 6, 4), (16, 16, 16, 6, 6, 7), (32, 32, 24, 6, 6, 7),
+               (48, 48, 32, 14, 14, 10), (64, 64, 40, 20, 20, 14))
+
+    @staticmethod
+    def _lift_width(in_width, width):
+        return width // 2
+
+    @staticmethod
+    def _plan(d1, d2, d3, padding):
+        return _grids3d(d1, d2, (d1 // 8, d2 // 8), (d3, d3, int(d3 * 1.6), int(d3 * 1.6), int(d3 * 2.4), int(3.2 * d3), 4 * d3)), 4 * padding
+
     def __init__(self, in_width, width, pad=2, factor=1, pad_both=False, block_cls=OperatorBlock_3D, one_buffer_any=False):
-        nn.Module.__init__(self)
-        self.in_width, self.width, self.pad, self.pad_both = in_width, width, pad, pad_both
-        w, f = width, factor
-        self.fc = nn.Linear(in_width, w // 2)
-        self.fc0 = nn.Linear(w // 2, w)
-        self.conv0 = block_cls(w, 2 * f * w, 48, 48, 10, 20, 20, 4, Normalize=True)
-        self.conv1 = block_cls(2 * f * w, 4 * f * w, 32, 32, 10, 14, 14, 4)
-        self.conv2 = block_cls(4 * f * w, 8 * f * w, 16, 16, 16, 6, 6, 4)
-        self.conv3 = block_cls(8 * f * w, 16 * f * w, 16, 16, 16, 6, 6, 7, Normalize=True)
-        self.conv6 = block_cls(16 * f * w, 4 * f * w, 32, 32, 24, 6, 6, 7)
-        self.conv7 = block_cls(8 * f * w, 2 * f * w, 48, 48, 32, 14, 14, 10, Normalize=True)
-        self.conv8 = block_cls(4 * f * w, 2 * w, 64, 64, 40, 20, 20, 14)
-        self.fc1 = nn.Linear(3 * w, 4 * w)
-        self.fc2 = nn.Linear(4 * w, 1)
-        self._grid_cache = {}
+        super().__init__(in_width, width, pad, factor, pad_both, block_cls)
         if issubclass(block_cls, OperatorBlock_3D):
             enable_native_resample3d_any(self)
             if one_buffer_any:
                 enable_one_buffer_any_grid(self)
-
-    def forward(self, x):
-        x = torch.cat((x, self.get_grid(x.shape, x.device)), dim=-1).permute(0, 4, 1, 2, 3).contiguous()
-        lifted = F.gelu(gelu_channel_mix(channel_mix(x, self.fc.weight, self.fc.bias), self.fc0.weight, self.fc0.bias))
-        self.padding = int(self.pad * 0.1 * lifted.shape[-1])
-        lifted = F.pad(lifted, [self.padding, self.padding, 0, 0, 0, 0] if self.pad_both else [0, self.padding, 0, 0, 0, 0])
-        d1, d2, d3 = lifted.shape[-3:]
-        c0 = self.conv0(lifted, int(3 * d1 / 4), int(3 * d2 / 4), d3)
-        c1 = self.conv1(c0, d1 // 2, d2 // 2, d3)
-        c2 = self.conv2(c1, d1 // 4, d2 // 4, int(d3 * 1.6))
-        c3 = self.conv3(c2, d1 // 8, d2 // 8, int(d3 * 1.6))
-        c6 = self.conv6(c3, d1 // 2, d2 // 2, int(d3 * 2.4))
-        c6 = torch.cat([c6, self._resize(c1, c6)], dim=1)
-        c7 = self.conv7(c6, int(3 * d1 / 4), int(3 * d2 / 4), int(3.2 * d3))
-        c7 = torch.cat([c7, self._resize(c0, c7)], dim=1)
-        c8 = self.conv8(c7, d1, d2, 4 * d3)
-        c8 = torch.cat([c8, self._resize(lifted, c8)], dim=1)
-        if self.padding != 0:
-            c8 = c8[..., 4 * self.padding:-4 * self.padding] if self.pad_both else c8[..., :-4 * self.padding]
-        out = gelu_project(channel_mix(c8.contiguous(), self.fc1.weight, self.fc1.bias), self.fc2.weight, self.fc2.bias)
-        return out.permute(0, 2, 3, 4, 1).contiguous()
