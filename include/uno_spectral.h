@@ -328,6 +328,30 @@ long long uno_rel_l2_steps_ws_bytes(int B, long long P, int T);
 int uno_rel_l2_steps(const float* pred, const float* target, float* sums, float* rel, float* totals, void* ws, int B, long long P, int T,
                      void* stream);
 
+/* One step of the NS-2D evaluation roll-out in one launch (additive: the ABI version stays 14).  The reference's validation and test
+ * loops (ns_train_2d.py:94-107, 141-157) run the model T_f times under no_grad, feed each prediction back into the input window and
+ * report the sum of the per-step relative L2 errors and the error of the whole trajectory; between two forward passes they spend a
+ * `cat` for the window, a strided slice of the target, six launches of LpLoss and a `cat` that rebuilds the prediction.  Dense float32:
+ *   window (B, C, P)  channels-first; channels [0, T_in) are the frames, [T_in, C) the model's positional features (never touched)
+ *   frame  (B, P)     the model's new prediction
+ *   target (B, T, P)  the ground truth, TIME-MAJOR (one transposing copy per batch: every step reads a dense slice)
+ *   pred   (B, T, P)  or NULL
+ * uno_rollout_advance, step t:  ws[b][chunk][t] = (sum (frame - target[:, t])^2, sum target[:, t]^2) over the chunk's pixels;
+ *   pred[b][t][:] = frame[b][:] if pred is given;  if shift != 0 the window moves IN PLACE: window[b][k][:] = window[b][k + 1][:] for
+ *   k < T_in - 1, then window[b][T_in - 1][:] = frame[b][:] (one thread moves a pixel's whole column in ascending k: no second buffer).
+ *   frame, target, pred and ws must not overlap the window or each other.
+ * uno_rollout_finish, after the last step (every t of 0 ... T - 1 written): the finish launch of uno_rel_l2_steps on ws -
+ *   sums (B, T, 2), rel (B, T + 1), totals (2) with the meaning they have there; rel[b][T] = sqrt(sum_t num) / sqrt(sum_t den) is the
+ *   whole-trajectory error, so the prediction never has to be assembled for it.
+ * 1 <= T_in <= C, 1 <= T <= 256, 0 <= t < T, P >= 1 (64-bit offsets); B == 0 returns 0 without touching the device.  No atomics; the
+ * chunk decomposition is a function of P alone (about 1024 pixels per chunk, at most 64 chunks; not of the CU count or
+ * uno_reserve_cus), so two calls give the same bits.  No clamping: a zero target slice gives +inf (NaN for 0 / 0).  16-byte accesses
+ * where P % 4 == 0.  ws: uno_rollout_ws_bytes() = 8 * B * chunks(P) * T bytes (0 for bad sizes; never shrinks as P grows). */
+long long uno_rollout_ws_bytes(int B, long long P, int T);
+int uno_rollout_advance(float* window, const float* frame, const float* target, float* pred, void* ws, int B, int C, int T_in, long long P,
+                        int T, int t, int shift, void* stream);
+int uno_rollout_finish(const void* ws, float* sums, float* rel, float* totals, int B, long long P, int T, void* stream);
+
 /* The same three calls on a WINDOW of a wider plane (ABI 10).  The reference crops the domain padding before its last two layers
  * (darcy_flow_uno2d.py:125-131: `x_c5[..., :-padding, :-padding]`, then fc1 - GELU - fc2 on S x S points); here those layers read
  * the padded (S + pad)^2 tensors in place and touch the domain only: the pixel axis of the call is rows x cols logical pixels,

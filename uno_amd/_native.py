@@ -89,6 +89,9 @@ _SIGNATURES = {
     "uno_gelu_project2_backward": (C.c_int, [_fp] * 9 + [_i, _i, _i, C.c_longlong, _i, _fp]),
     "uno_rel_l2_steps_ws_bytes": (C.c_longlong, [_i, C.c_longlong, _i]),
     "uno_rel_l2_steps": (C.c_int, [_fp] * 6 + [_i, C.c_longlong, _i, _fp]),
+    "uno_rollout_ws_bytes": (C.c_longlong, [_i, C.c_longlong, _i]),
+    "uno_rollout_advance": (C.c_int, [_fp] * 5 + [_i, _i, _i, C.c_longlong, _i, _i, _i, _fp]),
+    "uno_rollout_finish": (C.c_int, [_fp] * 4 + [_i, C.c_longlong, _i, _fp]),
     "uno_gelu_pad": (C.c_int, [_fp, _fp, _fp] + [_i] * 6 + [_fp]),
     "uno_transpose_batched": (C.c_int, [_fp, _fp, _i, C.c_longlong, _i] + [C.c_longlong] * 4 + [_fp]),
     "uno_instnorm_forward": (C.c_int, [_fp] * 6 + [C.c_longlong, _i, C.c_longlong, C.c_float, _i, _fp]),
@@ -1056,6 +1059,83 @@ def rel_l2_steps(pred, target):
         ws = torch.empty(max(1, L.uno_rel_l2_steps_ws_bytes(B, P, T)), dtype=torch.uint8, device=pred.device)
         rc = L.uno_rel_l2_steps(_ptr(pred), _ptr(target), _ptr(sums), _ptr(rel), _ptr(totals), _ptr(ws), B, P, T, _stream(pred))
     _check(rc, "uno_rel_l2_steps")
+    return sums, rel, totals
+
+
+def rollout_ws(B, P, T, device):
+    """The workspace of one roll-out of T steps over (B, P) frames (uno_rollout_ws_bytes): rollout_advance fills it step by step,
+    rollout_finish reads it."""
+    return torch.empty(max(1, lib().uno_rollout_ws_bytes(int(B), int(P), int(T))), dtype=torch.uint8, device=device)
+
+
+def _rollout_ws_check(ws, B, P, T):
+    _require(ws, torch.uint8, "ws")
+    need = lib().uno_rollout_ws_bytes(B, P, T)
+    if ws.numel() < need:
+        raise RuntimeError(f"uno_amd: the roll-out workspace holds {ws.numel()} bytes, {need} are needed (rollout_ws)")
+
+
+def rollout_advance(window, frame, target, pred, ws, T_in, t, shift):
+    """One step of the NS-2D evaluation roll-out (uno_rollout_advance, K18), all dense f32 on one device: window (B, C, ...) channels-first
+    with the frames in channels [0, T_in); frame: the model's prediction, B x P values (P = the window's pixels per channel); target
+    (B, T, ...) time-major; pred like target, or None; ws from rollout_ws.  Writes the chunk sums of step t into ws, pred[:, t] = frame,
+    and with `shift` moves the window's frames up by one IN PLACE with `frame` as the newest.  Launches on the current stream."""
+    for x, name in ((window, "window"), (frame, "frame"), (target, "target")) + (((pred, "pred"),) if pred is not None else ()):
+        _require(x, torch.float32, name)
+        if x.device != window.device:
+            raise RuntimeError(f"uno_amd: {name} lives on {x.device}, the window on {window.device}")
+    if window.dim() < 3 or target.dim() < 3:
+        raise RuntimeError(f"uno_amd: the roll-out takes a (batch, channels, ...) window and a (batch, time, ...) target "
+                           f"(got {tuple(window.shape)} and {tuple(target.shape)})")
+    B, Cw = window.shape[0], window.shape[1]
+    P = _count(window.shape[2:])
+    T = target.shape[1]
+    if frame.dim() < 2 or frame.shape[0] != B or frame.numel() != B * P:
+        raise RuntimeError(f"uno_amd: frame {tuple(frame.shape)} does not hold one value per pixel of the window {tuple(window.shape)}")
+    if target.shape[0] != B or _count(target.shape[2:]) != P:
+        raise RuntimeError(f"uno_amd: target {tuple(target.shape)} does not match the window {tuple(window.shape)}")
+    if pred is not None and pred.shape != target.shape:
+        raise RuntimeError(f"uno_amd: pred {tuple(pred.shape)} and target {tuple(target.shape)} differ")
+    L = lib()
+    if ws.device != window.device:
+        raise RuntimeError(f"uno_amd: ws lives on {ws.device}, the window on {window.device}")
+    _rollout_ws_check(ws, B, P, T)
+    with torch.cuda.device(window.device):
+        rc = L.uno_rollout_advance(_ptr(window), _ptr(frame), _ptr(target), _opt(pred), _ptr(ws), B, Cw, int(T_in), P, T, int(t),
+                                   1 if shift else 0, _stream(window))
+    _check(rc, "uno_rollout_advance")
+
+
+def rollout_record(B, T, device):
+    """One flat f32 tensor that holds sums (B, T, 2), rel (B, T + 1) and totals (2) back to back (rollout_views): a graph replay's
+    results are taken out of the graph's memory with ONE clone."""
+    n = 2 * B * T + B * (T + 1) + 2
+    return torch.zeros((n,), dtype=torch.float32, device=device) if B == 0 else torch.empty((n,), dtype=torch.float32, device=device)
+
+
+def rollout_views(record, B, T):
+    """-> sums (B, T, 2), rel (B, T + 1), totals (2,): views of a rollout_record"""
+    a, b = 2 * B * T, 2 * B * T + B * (T + 1)
+    return record[:a].view(B, T, 2), record[a:b].view(B, T + 1), record[b:b + 2]
+
+
+def rollout_finish(ws, B, P, T, record=None):
+    """After the last rollout_advance of a roll-out: -> sums (B, T, 2), rel (B, T + 1), totals (2,) as rel_l2_steps returns them
+    (uno_rollout_finish: K17's finish launch on K18's workspace), views of one rollout_record (`record`, or a fresh one).  Launches on
+    the current stream and allocates through torch."""
+    B, P, T = int(B), int(P), int(T)
+    _rollout_ws_check(ws, B, P, T)
+    L = lib()
+    with torch.cuda.device(ws.device):
+        if record is None:
+            record = rollout_record(B, T, ws.device)
+        else:
+            _require(record, torch.float32, "record")
+            if record.device != ws.device or record.numel() != 2 * B * T + B * (T + 1) + 2:
+                raise RuntimeError(f"uno_amd: the record holds {record.numel()} floats on {record.device}: not a rollout_record of ({B}, {T})")
+        sums, rel, totals = rollout_views(record, B, T)
+        rc = L.uno_rollout_finish(_ptr(ws), _ptr(sums), _ptr(rel), _ptr(totals), B, P, T, _stream(ws))
+    _check(rc, "uno_rollout_finish")
     return sums, rel, totals
 
 

@@ -541,6 +541,37 @@ int uno_rel_l2_steps(const float* pred, const float* target, float* sums, float*
     return launch_rel_l2_steps(pred, target, sums, rel, totals, (float*)ws, B, P, T, (hipStream_t)stream);
 }
 
+// K18: one step of the NS-2D evaluation roll-out (forward only), dense float32; the finish launch is K17's
+static bool rollout_sizes(const char* who, int B, long long P, int T) {
+    if (B < 0 || P < 1 || T < 1) { set_error("%s: bad sizes B=%d P=%lld T=%d", who, B, P, T); return false; }
+    if (T > 256) { set_error("%s: T = %d time steps, at most 256", who, T); return false; }
+    return true;
+}
+
+long long uno_rollout_ws_bytes(int B, long long P, int T) {
+    if (B < 1 || P < 1 || T < 1 || T > 256) return 0;
+    return 4LL * rollout_ws_floats(B, P, T);
+}
+
+int uno_rollout_advance(float* window, const float* frame, const float* target, float* pred, void* ws, int B, int C, int T_in, long long P,
+                        int T, int t, int shift, void* stream) {
+    if (!rollout_sizes("uno_rollout_advance", B, P, T)) return -1;
+    if (C < 1 || T_in < 1 || T_in > C || t < 0 || t >= T) {
+        set_error("uno_rollout_advance: bad sizes C=%d T_in=%d (1 ... C) t=%d (0 ... T - 1 = %d)", C, T_in, t, T - 1);
+        return -1;
+    }
+    if (B == 0) return 0;
+    if (!window || !frame || !target || !ws) { set_error("uno_rollout_advance: null pointer"); return -1; }
+    return launch_rollout_advance(window, frame, target, pred, (float*)ws, B, C, T_in, P, T, t, shift, (hipStream_t)stream);
+}
+
+int uno_rollout_finish(const void* ws, float* sums, float* rel, float* totals, int B, long long P, int T, void* stream) {
+    if (!rollout_sizes("uno_rollout_finish", B, P, T)) return -1;
+    if (B == 0) return 0;
+    if (!ws || !sums || !rel || !totals) { set_error("uno_rollout_finish: null pointer"); return -1; }
+    return launch_rel_l2_steps_finish((const float*)ws, sums, rel, totals, B, T, rollout_chunks(P, nullptr), (hipStream_t)stream);
+}
+
 static int gelu_pad_impl(const void* s, const void* gy, void* out, int n_img, int H, int W, int Hp, int Wp, int backward, int bf16, void* stream) {
     if (n_img < 0 || H < 1 || W < 1 || Hp < H || Wp < W) { set_error("uno_gelu_pad: bad sizes (%d, %d) -> (%d, %d)", H, W, Hp, Wp); return -1; }
     if (n_img == 0) return 0;

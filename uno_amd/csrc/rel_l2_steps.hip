@@ -136,6 +136,17 @@ __global__ __launch_bounds__(RL2_FINISH_THREADS) void rel_l2_steps_finish_kernel
     }
 }
 
+// the finish launch alone: K18 (rollout.hip) fills a workspace of this layout step by step and finishes it with its own chunk count
+int launch_rel_l2_steps_finish(const float* ws, float* sums, float* rel, float* totals, int B, int T, long long nc, hipStream_t s) {
+    {
+        ProfScope prof("uno::rel_l2_steps_finish_kernel", 8.0 * B * (double)nc * T, s);
+        hipLaunchKernelGGL(rel_l2_steps_finish_kernel, dim3(1), dim3(RL2_FINISH_THREADS), 0, s, (const float2*)ws, sums, rel, totals, B, T, (int)nc);
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { set_error("rel_l2_steps finish launch: %s", hipGetErrorString(e)); return -5; }
+    return 0;
+}
+
 int launch_rel_l2_steps(const float* pred, const float* target, float* sums, float* rel, float* totals, float* ws, int B, long long P, int T,
                         hipStream_t s) {
     long long cp = 0;
@@ -145,15 +156,9 @@ int launch_rel_l2_steps(const float* pred, const float* target, float* sums, flo
         ProfScope prof("uno::rel_l2_steps_partial_kernel", 8.0 * B * (double)P * T, s);
         hipLaunchKernelGGL(rel_l2_steps_partial_kernel, dim3((unsigned)(nc * B)), dim3(RL2_THREADS), 0, s, pred, target, (float2*)ws, P, T, cp, (int)nc);
     }
-    hipError_t e = hipGetLastError();
+    const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_error("rel_l2_steps partial launch: %s", hipGetErrorString(e)); return -5; }
-    {
-        ProfScope prof("uno::rel_l2_steps_finish_kernel", 8.0 * B * (double)nc * T, s);
-        hipLaunchKernelGGL(rel_l2_steps_finish_kernel, dim3(1), dim3(RL2_FINISH_THREADS), 0, s, (const float2*)ws, sums, rel, totals, B, T, (int)nc);
-    }
-    e = hipGetLastError();
-    if (e != hipSuccess) { set_error("rel_l2_steps finish launch: %s", hipGetErrorString(e)); return -5; }
-    return 0;
+    return launch_rel_l2_steps_finish(ws, sums, rel, totals, B, T, nc, s);
 }
 
 }  // namespace uno

@@ -389,5 +389,12 @@ long long rel_l2_steps_chunks(long long P, int T, long long* chunk_pixels);     
 long long rel_l2_steps_ws_floats(int B, long long P, int T);
 int launch_rel_l2_steps(const float* pred, const float* target, float* sums, float* rel, float* totals, float* ws, int B, long long P, int T,
                         hipStream_t s);
+int launch_rel_l2_steps_finish(const float* ws, float* sums, float* rel, float* totals, int B, int T, long long nc, hipStream_t s);
+// rollout.hip (K18): one step of the NS-2D evaluation roll-out - chunk partials of step t into ws (K17's layout), pred[b][t] = frame, the
+// window's frames moved up by one in place; ws: rollout_ws_floats() floats
+long long rollout_chunks(long long P, long long* chunk_pixels);       // chunk count: a function of P alone
+long long rollout_ws_floats(int B, long long P, int T);
+int launch_rollout_advance(float* window, const float* frame, const float* target, float* pred, float* ws, int B, int C, int T_in, long long P,
+                           int T, int t, int shift, hipStream_t s);
 
 }  // namespace uno

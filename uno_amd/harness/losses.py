@@ -1,4 +1,4 @@
-from typing import NamedTuple
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -18,6 +18,12 @@ class StepErrors(NamedTuple):
     full: torch.Tensor          # (B,): the same ratio over the whole trajectory
     step_sum: torch.Tensor      # 0-dim: sum over batch and steps of per_step - the reference's temp_step_loss
     full_sum: torch.Tensor      # 0-dim: sum over the batch of full - LpLoss(size_average=False) of the whole trajectory
+
+
+class RolloutErrors(NamedTuple):
+    """What one evaluation roll-out of the NS-2D loop yields (harness.ns2d_rollout_errors)."""
+    errors: StepErrors          # of the T_f predicted frames against the ground truth
+    pred: Optional[torch.Tensor]        # (B, S, S, T_f) prediction - on the native path a view of the time-major buffer - or None
 
 
 NATIVE_STEP_ERRORS_MAX_T = 256

@@ -16,7 +16,7 @@ import time
 import torch
 import torch.distributed as dist
 
-from .losses import lp_loss_rel_sum, step_errors
+from .losses import NATIVE_STEP_ERRORS_MAX_T, RolloutErrors, StepErrors, _step_errors_stock, lp_loss_rel_sum, step_errors
 from .optim import ComplexAdam
 
 
@@ -218,6 +218,85 @@ def ns2d_rollout_loss(model, xx, yy, T_f, step=1):
     return loss
 
 
+def _rollout_native_applies(model, xx, yy, T_f, step):
+    return (step == 1 and hasattr(model, "forward_cf") and hasattr(model, "get_grid") and xx.dim() == 4 and yy.dim() == 4
+            and xx.is_cuda and yy.is_cuda and xx.dtype == torch.float32 and yy.dtype == torch.float32
+            and 1 <= T_f <= NATIVE_STEP_ERRORS_MAX_T and yy.shape[0] > 0 and xx[0].numel() > 0)
+
+
+def ns2d_rollout_errors(model, xx, yy, T_f, step=1, return_pred=False) -> RolloutErrors:
+    """The evaluation roll-out of the NS-2D loop (reference ns_train_2d.py:86-117, 133-168) under no_grad: the model runs T_f / step
+    times, each prediction goes back into the input window, and the prediction is measured against yy[..., :T_f] - per time step
+    (`errors.step_sum` is the reference's val_l2_step / test_l2_step for one batch, the number that selects checkpoints) and as a
+    whole trajectory (`errors.full_sum`, its test_l2).  xx (B, S, S, T_in), yy (B, S, S, >= T_f).  No host synchronisation; the
+    model's training mode is left as it is (ns2d_evaluate switches it).
+
+    float32 device tensors, step == 1, a model with forward_cf / get_grid, T_f <= 256 and B > 0 take the native path: the window is
+    built once channels-first next to the model's positional features (as ns2d_rollout_loss builds it), the ground truth is copied
+    once to time-major order, and between two forward passes ONE launch (uno_rollout_advance, K18) takes the step's sums, stores the
+    frame into the prediction and moves the window in place; one finish launch after the last step gives the five quantities.
+    Everything else takes the stock path, the reference's loop written out; with step > 1 its per-step quantities are still per
+    time slice (the reference's loss there is per group of `step` frames)."""
+    if T_f < 1 or step < 1 or T_f % step or yy.shape[-1] < T_f:
+        raise RuntimeError(f"ns2d_rollout_errors: T_f = {T_f} must be a positive multiple of step = {step} within the {yy.shape[-1]} frames of yy")
+    with torch.no_grad():
+        xx, yy = xx.detach(), yy.detach()
+        if not _rollout_native_applies(model, xx, yy, T_f, step):
+            pred = None
+            for t in range(0, T_f, step):
+                im = model(xx)
+                pred = im if pred is None else torch.cat((pred, im), -1)
+                xx = torch.cat((xx[..., step:], im), dim=-1)
+            return RolloutErrors(_step_errors_stock(pred, yy[..., :T_f]), pred if return_pred else None)
+        record, pred = _rollout_native(model, xx, yy, T_f, return_pred)
+        return _rollout_result(record, pred, yy.shape[0], T_f)
+
+
+def _rollout_native(model, xx, yy, T_f, return_pred):
+    """The native roll-out (call under no_grad) -> (the flat record of the five quantities, _native.rollout_record; the time-major
+    prediction (B, T_f, S, S) or None)"""
+    from .. import _native
+    B, T_in = xx.shape[0], xx.shape[-1]
+    P = xx.shape[1] * xx.shape[2]
+    grid = model.get_grid(xx.shape, xx.device)
+    # (B, T_in + features, S, S), DENSE in that order (a plain cat of the two permuted views would come out channels-last in memory)
+    z = torch.empty((B, T_in + grid.shape[-1], xx.shape[1], xx.shape[2]), dtype=torch.float32, device=xx.device)
+    torch.cat((xx.permute(0, 3, 1, 2), grid.permute(0, 3, 1, 2)), dim=1, out=z)
+    target = yy[..., :T_f].permute(0, 3, 1, 2).contiguous()                                                     # (B, T_f, S, S): time-major
+    pred = torch.empty_like(target) if return_pred else None
+    ws = _native.rollout_ws(B, P, T_f, xx.device)
+    for t in range(T_f):
+        im = model.forward_cf(z).contiguous()                   # (B, 1, S, S): complete before the launch below overwrites its input
+        _native.rollout_advance(z, im, target, pred, ws, T_in, t, t + 1 < T_f)
+    record = _native.rollout_record(B, T_f, xx.device)
+    _native.rollout_finish(ws, B, P, T_f, record=record)
+    return record, pred
+
+
+def _rollout_result(record, pred, B, T_f) -> RolloutErrors:
+    from .. import _native
+    sums, rel, totals = _native.rollout_views(record, B, T_f)
+    errors = StepErrors(sums, rel[:, :T_f], rel[:, T_f], totals[0], totals[1])
+    return RolloutErrors(errors, pred.permute(0, 2, 3, 1) if pred is not None else None)
+
+
+def ns2d_evaluate(model, batches, T_f, step=1):
+    """Validation / test pass of the NS-2D loop (reference ns_train_2d.py:86-117, 133-168): eval mode, no_grad, per batch one
+    ns2d_rollout_errors; -> (sum of the per-step errors, sum of the whole-trajectory errors) over all batches as 0-dim device tensors
+    (no host synchronisation).  The previous training mode is restored.  The caller divides by nval * (T_f / step) and by nval."""
+    was_training = model.training
+    model.eval()
+    step_total = full_total = None
+    try:
+        for xx, yy in batches:
+            e = ns2d_rollout_errors(model, xx, yy, T_f, step).errors
+            step_total = e.step_sum if step_total is None else step_total + e.step_sum
+            full_total = e.full_sum if full_total is None else full_total + e.full_sum
+    finally:
+        model.train(was_training)
+    return step_total, full_total
+
+
 def ns3d_step_error(out, y):
     """The number the reference's NS-3D loop prints and selects checkpoints by (ns_train_3d.py:55-62): the sum over the time steps
     of the per-step relative L2 error summed over the batch.  out, y: (B, S, S, T_f); a 0-dim device tensor, no gradient."""
@@ -306,6 +385,63 @@ class GraphedStep:
         else:
             self.opt.step()
         return self.static_loss.detach().clone()        # the graph-owned scalar is overwritten by the next replay
+
+
+class GraphedRollout:
+    """The whole native evaluation roll-out (ns2d_rollout_errors: window build, target transpose, T_f forward passes with one
+    uno_rollout_advance each, the finish launch) captured ONCE into a HIP graph and replayed per batch - GraphedStep's recipe, forward
+    only.  A replay has no per-launch host work: it pays where the host's enqueueing is the longer side (small batches and widths); at
+    UNO(14, 32), 64^2, batch 32 the device is, and replay and eager call take the same time.  Parameters are read through their pointers: a replay after an optimiser step (or a load_state_dict) sees the new weights.
+    The model's training mode at construction is the captured one.
+
+        gr = GraphedRollout(model, 40, (xx0, yy0))
+        e = gr.errors(xx, yy).errors          # device tensors, no host synchronisation
+        step_total, full_total = gr.evaluate(val_batches)
+
+    Every batch must have the example's shapes (a last, smaller batch goes through ns2d_rollout_errors)."""
+
+    def __init__(self, model, T_f, example_inputs, return_pred=False, warmup: int = 1):
+        if not torch.cuda.is_available():
+            raise RuntimeError("GraphedRollout needs the GPU (HIP graph capture)")
+        xx, yy = example_inputs
+        if not _rollout_native_applies(model, xx, yy, T_f, 1):
+            raise RuntimeError("GraphedRollout captures the native roll-out only: float32 device tensors (B, S, S, T), a model with "
+                               f"forward_cf / get_grid, 1 <= T_f <= {NATIVE_STEP_ERRORS_MAX_T}, a non-empty batch")
+        self.model, self.T_f, self.return_pred = model, T_f, return_pred
+        self.static_in = (xx.clone(), yy.clone())
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):                   # eager warm-up off the default stream, as capture requires (it also builds
+            for _ in range(max(1, warmup)):             # the cached grid features and operand tables: at least one pass)
+                ns2d_rollout_errors(model, *self.static_in, T_f, return_pred=return_pred)
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph), torch.no_grad():
+            self._record, self._pred = _rollout_native(model, *self.static_in, T_f, return_pred)
+
+    def _replay(self, xx, yy):
+        for dst, src in zip(self.static_in, (xx, yy)):
+            if dst.shape != src.shape:
+                raise RuntimeError(f"GraphedRollout: captured for {tuple(dst.shape)}, got {tuple(src.shape)}")
+            if src.data_ptr() != dst.data_ptr():        # (a batch loaded straight into gr.static_in needs no copy)
+                dst.copy_(src, non_blocking=True)
+        self.graph.replay()
+
+    def errors(self, xx, yy) -> RolloutErrors:
+        """-> RolloutErrors of this batch; clones (one of the record of the five quantities, one of the prediction): the graph-owned
+        tensors are overwritten by the next replay"""
+        self._replay(xx, yy)
+        return _rollout_result(self._record.clone(), self._pred.clone() if self._pred is not None else None, xx.shape[0], self.T_f)
+
+    def evaluate(self, batches):
+        """as ns2d_evaluate: -> (sum of the per-step errors, sum of the whole-trajectory errors) over the batches"""
+        total = None
+        for xx, yy in batches:
+            self._replay(xx, yy)
+            totals = self._record[-2:]
+            total = totals.clone() if total is None else total + totals
+        return total[0], total[1]
 
 
 class DarcyTrainer:
