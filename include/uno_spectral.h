@@ -352,6 +352,46 @@ int uno_rollout_advance(float* window, const float* frame, const float* target, 
                         int T, int t, int shift, void* stream);
 int uno_rollout_finish(const void* ws, float* sums, float* rel, float* totals, int B, long long P, int T, void* stream);
 
+/* The NS-2D TRAINING roll-out without a window tensor (additive: the ABI version stays 14).  The reference's training loop
+ * (ns_train_2d.py:46-68) runs the model T_f times, concatenates each prediction into the input window (`xx = torch.cat((xx[..., step:],
+ * im), dim=-1)`), sums `myloss(im, y)` over the steps and runs ONE backward through the unrolled chain: per step a `cat`, six launches
+ * of LpLoss, and in the backward pass a zero-fill and a copy per slice of every `cat` plus the additions that merge a window's
+ * gradients.  The window of step t is T_in consecutive frames of the sequence "the T_in given frames, then the predictions", and the
+ * only layer that reads it is the first lift `fc`, a point-wise map of C = T_in + F channels to Cm.  Dense float32:
+ *   given  (B, T_in, P)    the input frames, channels-first
+ *   pred, target, gpred (B, T, P)   time-major, as uno_rollout_advance writes pred (shift = 0) and reads target
+ *   feat   (F, P)          the model's positional features: ONE table for all batch entries (may be NULL when F = 0)
+ *   w (Cm, C), bias (Cm) or NULL   columns in the order [frames, features]
+ *   frame j of the sequence = given[:, j] for j < T_in, otherwise pred[:, j - T_in]
+ * uno_rollout_lift, window t:  h[b][m][p] = bias[m] + sum_{k<T_in} w[m][k] frame_{t+k}[b][p] + sum_{f<F} w[m][T_in+f] feat[f][p],
+ *   summed in ascending column order; reads pred[:, 0 ... t - 1] (pred may be NULL for t = 0).
+ * uno_rollout_lift_backward, window t, given gh (B, Cm, P) - ONE launch:
+ *   parts: the workgroup of (b, chunk) writes block [t][b][chunk] of (Cm, C + 1) floats, gw[m][c] = sum gh x over its pixels with the
+ *     bias sums in column C - the layout uno_channel_wgrad_finish sums.  parts holds uno_rollout_lift_bwd_ws_bytes() bytes = the blocks
+ *     of all T windows back to back: after the T calls ONE uno_channel_wgrad_finish(parts, gw, gb, C, Cm, bytes / (4 Cm (C + 1)), ...)
+ *     gives the layer's weight and bias gradient of the whole roll-out;
+ *   gpred[b][q][p] += sum_m w[m][k] gh[b][m][p] for every predicted frame q = t + k - T_in >= 0 of the window but the newest (the caller
+ *     clears gpred before the first call of a backward pass; a thread owns its pixel: no atomics);
+ *   for t >= 1, gframe (B, P) = the COMPLETE gradient of the newest frame q = t - 1, the model's output of step t - 1:
+ *     gpred[b][q][p] + sum_m w[m][T_in-1] gh[b][m][p] + gL[0] (pred - target)[b][q][p] / (sqrt(num[b][q]) sqrt(den[b][q]))
+ *     - complete when the windows are walked in DESCENDING t, as a backward pass walks them: every later window has added its share.
+ *     num / den are the `sums` (B, T, 2) of uno_rollout_finish, gL (1 float on the device) the gradient at the loss: no host
+ *     synchronisation.  Where num == 0 the loss term is 0 (the backward of torch.linalg.vector_norm); a zero den gives inf / NaN.
+ *     For t = 0 nothing but parts is written (target, sums, gL, gpred, gframe and pred may be NULL).
+ * uno_rollout_loss_seed: gframe[b][p] = gL[0] (pred - target)[b][T-1][p] / (sqrt(num[b][T-1]) sqrt(den[b][T-1])), the gradient of the
+ *   last frame (no lift follows it).
+ * 1 <= T_in, 0 <= F, T_in + F <= 32, 1 <= Cm <= 64, 1 <= T <= 256, 0 <= t < T, P >= 1; B == 0 returns 0 without touching the device.
+ * The chunk decomposition is uno_rollout_advance's (a function of P alone) and every sum runs in a fixed order: two calls, a call under
+ * uno_reserve_cus and a graph replay give the same bits.  The training loss itself is totals[0] of uno_rollout_finish. */
+int uno_rollout_lift(const float* given, const float* pred, const float* feat, const float* w, const float* bias, float* h, int B, int T_in,
+                     int F, int Cm, long long P, int T, int t, void* stream);
+long long uno_rollout_lift_bwd_ws_bytes(int B, int T_in, int F, int Cm, long long P, int T);
+int uno_rollout_lift_backward(const float* gh, const float* given, const float* pred, const float* target, const float* feat, const float* w,
+                              const float* sums, const float* gL, float* gpred, float* gframe, void* parts, int B, int T_in, int F, int Cm,
+                              long long P, int T, int t, void* stream);
+int uno_rollout_loss_seed(const float* pred, const float* target, const float* sums, const float* gL, float* gframe, int B, long long P, int T,
+                          void* stream);
+
 /* The same three calls on a WINDOW of a wider plane (ABI 10).  The reference crops the domain padding before its last two layers
  * (darcy_flow_uno2d.py:125-131: `x_c5[..., :-padding, :-padding]`, then fc1 - GELU - fc2 on S x S points); here those layers read
  * the padded (S + pad)^2 tensors in place and touch the domain only: the pixel axis of the call is rows x cols logical pixels,

@@ -92,6 +92,10 @@ _SIGNATURES = {
     "uno_rollout_ws_bytes": (C.c_longlong, [_i, C.c_longlong, _i]),
     "uno_rollout_advance": (C.c_int, [_fp] * 5 + [_i, _i, _i, C.c_longlong, _i, _i, _i, _fp]),
     "uno_rollout_finish": (C.c_int, [_fp] * 4 + [_i, C.c_longlong, _i, _fp]),
+    "uno_rollout_lift": (C.c_int, [_fp] * 6 + [_i, _i, _i, _i, C.c_longlong, _i, _i, _fp]),
+    "uno_rollout_lift_bwd_ws_bytes": (C.c_longlong, [_i, _i, _i, _i, C.c_longlong, _i]),
+    "uno_rollout_lift_backward": (C.c_int, [_fp] * 11 + [_i, _i, _i, _i, C.c_longlong, _i, _i, _fp]),
+    "uno_rollout_loss_seed": (C.c_int, [_fp] * 5 + [_i, C.c_longlong, _i, _fp]),
     "uno_gelu_pad": (C.c_int, [_fp, _fp, _fp] + [_i] * 6 + [_fp]),
     "uno_transpose_batched": (C.c_int, [_fp, _fp, _i, C.c_longlong, _i] + [C.c_longlong] * 4 + [_fp]),
     "uno_instnorm_forward": (C.c_int, [_fp] * 6 + [C.c_longlong, _i, C.c_longlong, C.c_float, _i, _fp]),
@@ -1137,6 +1141,113 @@ def rollout_finish(ws, B, P, T, record=None):
         rc = L.uno_rollout_finish(_ptr(ws), _ptr(sums), _ptr(rel), _ptr(totals), B, P, T, _stream(ws))
     _check(rc, "uno_rollout_finish")
     return sums, rel, totals
+
+
+def _rollout_lift_operands(given, pred, feat, w, target=None):
+    """shape / dtype / device / density checks shared by the training roll-out's calls -> (B, T_in, F, Cm, P, T)"""
+    named = [(given, "given"), (pred, "pred"), (w, "weight")] + ([(feat, "feat")] if feat is not None else []) \
+        + ([(target, "target")] if target is not None else [])
+    for x, name in named:
+        _require(x, torch.float32, name)
+        if x.device != given.device:
+            raise RuntimeError(f"uno_amd: {name} lives on {x.device}, the given frames on {given.device}")
+    if given.dim() < 3 or pred.dim() < 3 or w.dim() != 2:
+        raise RuntimeError(f"uno_amd: the roll-out lift takes (batch, T_in, ...) given frames, a (batch, time, ...) prediction and a (Cm, C) "
+                           f"weight (got {tuple(given.shape)}, {tuple(pred.shape)} and {tuple(w.shape)})")
+    B, T_in = given.shape[0], given.shape[1]
+    P = _count(given.shape[2:])
+    T = pred.shape[1]
+    if pred.shape[0] != B or _count(pred.shape[2:]) != P:
+        raise RuntimeError(f"uno_amd: pred {tuple(pred.shape)} does not match the given frames {tuple(given.shape)}")
+    if target is not None and target.shape != pred.shape:
+        raise RuntimeError(f"uno_amd: pred {tuple(pred.shape)} and target {tuple(target.shape)} differ")
+    F = 0
+    if feat is not None:
+        if feat.dim() < 2 or _count(feat.shape[1:]) != P:
+            raise RuntimeError(f"uno_amd: feat {tuple(feat.shape)} is not a (features, ...) table over the {P} pixels of a frame")
+        F = feat.shape[0]
+    Cm = w.shape[0]
+    if w.shape[1] != T_in + F:
+        raise RuntimeError(f"uno_amd: weight {tuple(w.shape)} does not have {T_in} + {F} columns")
+    return B, T_in, F, Cm, P, T
+
+
+def rollout_lift(given, pred, feat, w, bias, t, out=None):
+    """The first lift of window t of the NS-2D training roll-out (uno_rollout_lift, K19), all dense f32 on one device: given (B, T_in, ...),
+    pred (B, T, ...) time-major with steps 0 ... t - 1 recorded, feat (F, ...) or None, w (Cm, T_in + F), bias (Cm,) or None
+    -> h (B, Cm, ...) (written into `out` when given).  Launches on the current stream."""
+    B, T_in, F, Cm, P, T = _rollout_lift_operands(given, pred, feat, w)
+    if bias is not None:
+        _require(bias, torch.float32, "bias")
+        if bias.device != given.device or bias.numel() != Cm:
+            raise RuntimeError(f"uno_amd: bias {tuple(bias.shape)} on {bias.device} does not go with the weight {tuple(w.shape)}")
+    with torch.cuda.device(given.device):
+        if out is None:
+            out = torch.empty((B, Cm, *given.shape[2:]), dtype=torch.float32, device=given.device)
+        else:
+            _require(out, torch.float32, "out")
+            if out.device != given.device or out.numel() != B * Cm * P:
+                raise RuntimeError(f"uno_amd: out {tuple(out.shape)} on {out.device} does not hold ({B}, {Cm}, {P}) values")
+        rc = lib().uno_rollout_lift(_ptr(given), _ptr(pred), _opt(feat), _ptr(w), _opt(bias), _ptr(out), B, T_in, F, Cm, P, T, int(t),
+                                    _stream(given))
+    _check(rc, "uno_rollout_lift")
+    return out
+
+
+def rollout_lift_bwd_ws(B, T_in, F, Cm, P, T, device):
+    """The weight-sum workspace of one training roll-out (uno_rollout_lift_bwd_ws_bytes): a float32 tensor holding the (Cm, C + 1) blocks
+    of all T windows back to back - rollout_lift_backward fills window t's, ONE channel_wgrad_finish(ws, C, Cm, ...) sums them all."""
+    n = lib().uno_rollout_lift_bwd_ws_bytes(int(B), int(T_in), int(F), int(Cm), int(P), int(T)) // 4
+    if n <= 0 and B > 0:
+        raise RuntimeError(f"uno_amd: the roll-out lift takes T_in + F <= 32 input channels, Cm <= 64 lifted channels and T <= 256 steps "
+                           f"(got T_in = {T_in}, F = {F}, Cm = {Cm}, T = {T}, P = {P})")
+    return torch.empty((max(1, n),), dtype=torch.float32, device=device)
+
+
+def rollout_lift_backward(gh, given, pred, target, feat, w, sums, gL, gpred, gframe, parts, t):
+    """The backward of rollout_lift for window t in ONE launch (uno_rollout_lift_backward, K19-B), all dense f32 on one device: gh
+    (B, Cm, ...); sums (B, T, 2) of rollout_finish; gL one float on the device; gpred like pred (+= for the window's older predicted
+    frames); gframe B x P values (written for t >= 1: the complete gradient of the model's output of step t - 1 - the windows must be
+    walked in descending t); parts from rollout_lift_bwd_ws (block t written).  Launches on the current stream."""
+    B, T_in, F, Cm, P, T = _rollout_lift_operands(given, pred, feat, w, target)
+    for x, name in ((gh, "grad_output"), (sums, "sums"), (gL, "gL"), (gpred, "gpred"), (gframe, "gframe"), (parts, "parts")):
+        _require(x, torch.float32, name)
+        if x.device != given.device:
+            raise RuntimeError(f"uno_amd: {name} lives on {x.device}, the given frames on {given.device}")
+    if gh.dim() < 3 or gh.shape[0] != B or gh.shape[1] != Cm or gh.numel() != B * Cm * P:
+        raise RuntimeError(f"uno_amd: grad_output {tuple(gh.shape)} is not ({B}, {Cm}, {P} pixels)")
+    if gpred.shape != pred.shape:
+        raise RuntimeError(f"uno_amd: gpred {tuple(gpred.shape)} and pred {tuple(pred.shape)} differ")
+    if gframe.numel() != B * P or sums.numel() != 2 * B * T or gL.numel() != 1:
+        raise RuntimeError(f"uno_amd: gframe {tuple(gframe.shape)}, sums {tuple(sums.shape)} or gL {tuple(gL.shape)} do not go with "
+                           f"({B}, {T}, {P} pixels)")
+    L = lib()
+    need = L.uno_rollout_lift_bwd_ws_bytes(B, T_in, F, Cm, P, T)
+    if parts.numel() * 4 < need:
+        raise RuntimeError(f"uno_amd: the weight-sum workspace holds {parts.numel() * 4} bytes, {need} are needed (rollout_lift_bwd_ws)")
+    with torch.cuda.device(given.device):
+        rc = L.uno_rollout_lift_backward(_ptr(gh), _ptr(given), _ptr(pred), _ptr(target), _opt(feat), _ptr(w), _ptr(sums), _ptr(gL),
+                                         _ptr(gpred), _ptr(gframe), _ptr(parts), B, T_in, F, Cm, P, T, int(t), _stream(given))
+    _check(rc, "uno_rollout_lift_backward")
+
+
+def rollout_loss_seed(pred, target, sums, gL, gframe):
+    """gframe (B x P values) = the gradient of sum_b ||pred - target|| / ||target|| of the LAST step at pred[:, T - 1], times gL
+    (uno_rollout_loss_seed); pred, target (B, T, ...) time-major, sums (B, T, 2) of rollout_finish, gL one float on the device."""
+    for x, name in ((pred, "pred"), (target, "target"), (sums, "sums"), (gL, "gL"), (gframe, "gframe")):
+        _require(x, torch.float32, name)
+        if x.device != pred.device:
+            raise RuntimeError(f"uno_amd: {name} lives on {x.device}, pred on {pred.device}")
+    if pred.dim() < 3 or target.shape != pred.shape:
+        raise RuntimeError(f"uno_amd: pred {tuple(pred.shape)} and target {tuple(target.shape)} are not one (batch, time, ...) shape")
+    B, T = pred.shape[0], pred.shape[1]
+    P = _count(pred.shape[2:])
+    if gframe.numel() != B * P or sums.numel() != 2 * B * T or gL.numel() != 1:
+        raise RuntimeError(f"uno_amd: gframe {tuple(gframe.shape)}, sums {tuple(sums.shape)} or gL {tuple(gL.shape)} do not go with "
+                           f"({B}, {T}, {P} pixels)")
+    with torch.cuda.device(pred.device):
+        rc = lib().uno_rollout_loss_seed(_ptr(pred), _ptr(target), _ptr(sums), _ptr(gL), _ptr(gframe), B, P, T, _stream(pred))
+    _check(rc, "uno_rollout_loss_seed")
 
 
 class _DeviceView:

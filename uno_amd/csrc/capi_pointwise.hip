@@ -572,6 +572,53 @@ int uno_rollout_finish(const void* ws, float* sums, float* rel, float* totals, i
     return launch_rel_l2_steps_finish((const float*)ws, sums, rel, totals, B, T, rollout_chunks(P, nullptr), (hipStream_t)stream);
 }
 
+// K19 / K19-B: the first lift of the NS-2D training roll-out and its backward (rollout_train.hip), dense float32
+static bool rollout_lift_sizes(const char* who, int B, int T_in, int F, int Cm, long long P, int T) {
+    if (!rollout_sizes(who, B, P, T)) return false;
+    if (T_in < 1 || F < 0 || Cm < 1) { set_error("%s: bad sizes T_in=%d F=%d Cm=%d", who, T_in, F, Cm); return false; }
+    if (T_in > 32 || F > 32 || T_in + F > 32 || Cm > 64) {
+        set_error("%s: C = T_in + F = %d + %d input channels (at most 32), Cm = %d lifted channels (at most 64)", who, T_in, F, Cm);
+        return false;
+    }
+    return true;
+}
+
+int uno_rollout_lift(const float* given, const float* pred, const float* feat, const float* w, const float* bias, float* h, int B, int T_in,
+                     int F, int Cm, long long P, int T, int t, void* stream) {
+    if (!rollout_lift_sizes("uno_rollout_lift", B, T_in, F, Cm, P, T)) return -1;
+    if (t < 0 || t >= T) { set_error("uno_rollout_lift: bad sizes t=%d (0 ... T - 1 = %d)", t, T - 1); return -1; }
+    if (B == 0) return 0;
+    if (!given || (t > 0 && !pred) || (F > 0 && !feat) || !w || !h) { set_error("uno_rollout_lift: null pointer"); return -1; }
+    return launch_rollout_lift(given, pred, feat, w, bias, h, B, T_in, F, Cm, P, T, t, (hipStream_t)stream);
+}
+
+long long uno_rollout_lift_bwd_ws_bytes(int B, int T_in, int F, int Cm, long long P, int T) {
+    if (B < 1 || P < 1 || T < 1 || T > 256 || T_in < 1 || F < 0 || T_in > 32 || F > 32 || T_in + F > 32 || Cm < 1 || Cm > 64) return 0;
+    return 4LL * rollout_lift_bwd_ws_floats(B, T_in + F, Cm, P, T);
+}
+
+int uno_rollout_lift_backward(const float* gh, const float* given, const float* pred, const float* target, const float* feat, const float* w,
+                              const float* sums, const float* gL, float* gpred, float* gframe, void* parts, int B, int T_in, int F, int Cm,
+                              long long P, int T, int t, void* stream) {
+    if (!rollout_lift_sizes("uno_rollout_lift_backward", B, T_in, F, Cm, P, T)) return -1;
+    if (t < 0 || t >= T) { set_error("uno_rollout_lift_backward: bad sizes t=%d (0 ... T - 1 = %d)", t, T - 1); return -1; }
+    if (B == 0) return 0;
+    if (!gh || !given || (F > 0 && !feat) || !w || !parts || (t > 0 && (!pred || !target || !sums || !gL || !gpred || !gframe))) {
+        set_error("uno_rollout_lift_backward: null pointer");
+        return -1;
+    }
+    return launch_rollout_lift_backward(gh, given, pred, target, feat, w, sums, gL, gpred, gframe, (float*)parts, B, T_in, F, Cm, P, T, t,
+                                        (hipStream_t)stream);
+}
+
+int uno_rollout_loss_seed(const float* pred, const float* target, const float* sums, const float* gL, float* gframe, int B, long long P, int T,
+                          void* stream) {
+    if (!rollout_sizes("uno_rollout_loss_seed", B, P, T)) return -1;
+    if (B == 0) return 0;
+    if (!pred || !target || !sums || !gL || !gframe) { set_error("uno_rollout_loss_seed: null pointer"); return -1; }
+    return launch_rollout_loss_seed(pred, target, sums, gL, gframe, B, P, T, (hipStream_t)stream);
+}
+
 static int gelu_pad_impl(const void* s, const void* gy, void* out, int n_img, int H, int W, int Hp, int Wp, int backward, int bf16, void* stream) {
     if (n_img < 0 || H < 1 || W < 1 || Hp < H || Wp < W) { set_error("uno_gelu_pad: bad sizes (%d, %d) -> (%d, %d)", H, W, Hp, Wp); return -1; }
     if (n_img == 0) return 0;

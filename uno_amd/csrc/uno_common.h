@@ -396,5 +396,16 @@ long long rollout_chunks(long long P, long long* chunk_pixels);       // chunk c
 long long rollout_ws_floats(int B, long long P, int T);
 int launch_rollout_advance(float* window, const float* frame, const float* target, float* pred, float* ws, int B, int C, int T_in, long long P,
                            int T, int t, int shift, hipStream_t s);
+// rollout_train.hip (K19 / K19-B): the first lift of the NS-2D TRAINING roll-out read from the frames where they lie (given frames and
+// K18's time-major pred), its backward with per-chunk (Cm, C + 1) weight-sum blocks for launch_channel_wgrad_finish, and the last
+// frame's loss gradient; chunks = rollout_chunks(P)
+long long rollout_lift_bwd_ws_floats(int B, int C, int Cm, long long P, int T);
+int launch_rollout_lift(const float* given, const float* pred, const float* feat, const float* w, const float* bias, float* h, int B, int T_in,
+                        int F, int Cm, long long P, int T, int t, hipStream_t s);
+int launch_rollout_lift_backward(const float* gh, const float* given, const float* pred, const float* target, const float* feat, const float* w,
+                                 const float* sums, const float* gL, float* gpred, float* gframe, float* parts, int B, int T_in, int F, int Cm,
+                                 long long P, int T, int t, hipStream_t s);
+int launch_rollout_loss_seed(const float* pred, const float* target, const float* sums, const float* gL, float* gframe, int B, long long P, int T,
+                             hipStream_t s);
 
 }  // namespace uno

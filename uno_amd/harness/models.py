@@ -159,7 +159,12 @@ class UNO(nn.Module):
     def forward_cf(self, x):
         """(B, T_in + 4, S, S) channels-first window + positional features -> (B, 1, S, S).  The roll-out keeps its window in this
         layout (harness.ns2d_rollout_loss): one concatenation per step instead of one for the window and one for the layout."""
-        h = channel_mix(x, self.fc.weight, self.fc.bias)            # kept PRE-activation: fc0 (and a two-source fc2) apply the GELU as they read it
+        return self.body_cf(channel_mix(x, self.fc.weight, self.fc.bias))
+
+    def body_cf(self, h):
+        """Everything after the first lift: h = fc(x), (B, lift width, S, S) channels-first and kept PRE-activation (fc0 and a two-source
+        fc2 apply the GELU as they read it) -> (B, 1, S, S).  The native training roll-out (harness.ns2d_rollout_loss(native=True))
+        forms h from the frames where they lie and calls this."""
         lifted = F.gelu(gelu_channel_mix(h, self.fc0.weight, self.fc0.bias))
         p = self.padding
         if p != 0:              # (F.pad with zero widths still copies the tensor: 40 copies per roll-out)

@@ -15,6 +15,7 @@ import time
 
 import torch
 import torch.distributed as dist
+from torch.autograd.function import once_differentiable
 
 from .losses import NATIVE_STEP_ERRORS_MAX_T, RolloutErrors, StepErrors, _step_errors_stock, lp_loss_rel_sum, step_errors
 from .optim import ComplexAdam
@@ -194,10 +195,16 @@ class FlatGradients:
             dist.all_reduce(self.flat, op=dist.ReduceOp.SUM, group=group)
 
 
-def ns2d_rollout_loss(model, xx, yy, T_f, step=1):
+def ns2d_rollout_loss(model, xx, yy, T_f, step=1, native=False):
     """Autoregressive loss of the NS-2D training step (reference ns_train_2d.py:46-62): the model predicts
     `step` frames from the last T_in, the prediction is appended to the input window, the per-step relative
-    L2 losses are summed; ONE backward runs through the whole unrolled chain."""
+    L2 losses are summed; ONE backward runs through the whole unrolled chain.
+
+    native=True (opt-in): the same loss and gradients without a window tensor - the first lift reads the frames where they lie and
+    the loss comes from the roll-out's own sums (_rollout_loss_native).  It needs step == 1, a model with fc / body_cf / get_grid,
+    T_in + features <= 32, a first lift of at most 64 channels and T_f <= 256, and raises where that does not hold."""
+    if native:
+        return _rollout_loss_native(model, xx, yy, T_f, step)
     loss = 0
     B = yy.shape[0]
     if step == 1 and hasattr(model, "forward_cf") and hasattr(model, "get_grid"):
@@ -216,6 +223,203 @@ def ns2d_rollout_loss(model, xx, yy, T_f, step=1):
         loss = loss + lp_loss_rel_sum(im.reshape(B, -1), yy[..., t:t + step].reshape(B, -1))
         xx = torch.cat((xx[..., step:], im), dim=-1)
     return loss
+
+
+# Limits of the native training roll-out (uno_rollout_lift / uno_rollout_lift_backward): input channels of the first lift, its width, steps
+NATIVE_ROLLOUT_MAX_C, NATIVE_ROLLOUT_MAX_CM, NATIVE_ROLLOUT_MAX_T = 32, 64, 256
+
+
+class _RolloutTrain:
+    """State of ONE native training roll-out (reference ns_train_2d.py:46-68), shared by the three autograd Functions below.
+
+    The window of step t is T_in consecutive frames of the sequence "the T_in given frames, then the predictions":
+        given (B, T_in, S, S)        channels-first copy of the input frames
+        pred, target, gpred (B, T, S, S)   time-major; pred[:, t] is recorded as step t's output arrives
+        feat (F, S, S)               the model's positional features, one table for all batch entries (get_grid expands it)
+    so no window is ever built: the first lift reads the frames where they lie (K19), its backward adds each predicted frame's
+    gradient into gpred (K19-B) and leaves its weight sums as blocks in `parts` - one channel_wgrad_finish per training step.  The loss
+    is totals[0] of rollout_finish over the chunk sums that recording the frames left in `ws`.
+
+    Every kernel call has a stock-op restatement for CPU tensors and other dtypes (as channel_mix has): the same three Functions then
+    run without a device, `parts` holding one summed (Cm, C + 1) block per step."""
+
+    def __init__(self, model, xx, yy, T_f):
+        B, S1, S2, T_in = xx.shape
+        w = model.fc.weight
+        grid = model.get_grid(xx.shape, xx.device)                                  # (B, S, S, F), the same table for every b
+        self.B, self.T_in, self.F, self.T, self.P, self.Cm = B, T_in, grid.shape[-1], T_f, S1 * S2, w.shape[0]
+        self.C = T_in + self.F
+        self.native = xx.is_cuda and xx.dtype == torch.float32 and w.dtype == torch.float32
+        self.given = xx.permute(0, 3, 1, 2).contiguous()
+        self.feat = grid[0].permute(2, 0, 1).to(xx.dtype).contiguous() if self.F else None
+        self.target = yy[..., :T_f].permute(0, 3, 1, 2).contiguous()
+        self.pred = torch.empty_like(self.target)
+        self.gpred = self.gL = self.sums = None
+        if self.native:
+            from .. import _native
+            self.ws = _native.rollout_ws(B, self.P, T_f, xx.device)
+            self.record = _native.rollout_record(B, T_f, xx.device)
+            self.parts = _native.rollout_lift_bwd_ws(B, T_in, self.F, self.Cm, self.P, T_f, xx.device)
+        else:
+            self.parts = xx.new_zeros((T_f, self.Cm, self.C + 1))
+
+    def _window(self, t):
+        """stock: the T_in frames of window t, (B, T_in, S, S)"""
+        lo = max(0, self.T_in - t)                              # that many of them are given frames
+        return torch.cat((self.given[:, self.T_in - lo:], self.pred[:, t - (self.T_in - lo):t]), dim=1) if lo < self.T_in else self.given
+
+    def lift(self, w, bias, t):
+        """h_t = fc(window t, features), (B, Cm, S, S)"""
+        if self.native:
+            from .. import _native
+            return _native.rollout_lift(self.given, self.pred, self.feat, w, bias, t)
+        h = torch.einsum("mk,bkxy->bmxy", w[:, :self.T_in], self._window(t)) + bias.view(1, -1, 1, 1)
+        if self.F:
+            h = h + torch.einsum("mf,fxy->mxy", w[:, self.T_in:], self.feat)
+        return h
+
+    def record_frame(self, im, t):
+        """pred[:, t] = the model's output of step t (and, on the device, the step's chunk sums of the loss)"""
+        if self.native:
+            from .. import _native
+            _native.rollout_advance(self.given, im.contiguous(), self.target, self.pred, self.ws, self.T_in, t, False)
+        else:
+            self.pred[:, t] = im.reshape(self.B, *self.pred.shape[2:])
+
+    def finish(self):
+        """-> the loss sum_t sum_b ||pred - target|| / ||target||; keeps the sums (B, T, 2) the backward pass needs"""
+        if self.native:
+            from .. import _native
+            self.sums, _, totals = _native.rollout_finish(self.ws, self.B, self.P, self.T, record=self.record)
+            return totals[0].clone()
+        d = self.pred - self.target
+        self.sums = torch.stack(((d * d).sum((2, 3)), (self.target * self.target).sum((2, 3))), dim=-1)
+        return (self.sums[..., 0].sqrt() / self.sums[..., 1].sqrt()).sum()
+
+    def _loss_term(self, q):
+        """stock: gL d / (||d|| ||y||) of step q, 0 where ||d|| = 0 (the backward of torch.linalg.vector_norm)"""
+        num, den = self.sums[:, q, 0], self.sums[:, q, 1]
+        scale = torch.where(num == 0, torch.zeros_like(num), self.gL / (num.sqrt() * den.sqrt()))
+        return scale.view(-1, 1, 1) * (self.pred[:, q] - self.target[:, q])
+
+    def seed(self, gL):
+        """Start of the backward pass: keep gL, clear gpred -> the gradient of the LAST frame (its loss term: no lift follows it)"""
+        self.gL = gL.detach().reshape(1).to(self.pred.dtype).clone()
+        self.gpred = torch.zeros_like(self.pred)
+        if self.native:
+            from .. import _native
+            gframe = torch.empty((self.B, 1, *self.pred.shape[2:]), dtype=self.pred.dtype, device=self.pred.device)
+            _native.rollout_loss_seed(self.pred, self.target, self.sums, self.gL, gframe)
+            return gframe
+        return self._loss_term(self.T - 1).unsqueeze(1)
+
+    def lift_backward(self, gh, w, t):
+        """Backward of lift(t): window t's weight sums into `parts`, the older predicted frames' gradients into gpred -> the COMPLETE
+        gradient of step t - 1's output (None for t = 0).  Must be called in DESCENDING t after seed()."""
+        if self.gpred is None:
+            raise RuntimeError("ns2d_rollout_loss(native=True): the roll-out's backward pass must start at its loss")
+        if self.native:
+            from .. import _native
+            gframe = torch.empty((self.B, 1, *self.pred.shape[2:]), dtype=self.pred.dtype, device=self.pred.device)
+            _native.rollout_lift_backward(gh.contiguous(), self.given, self.pred, self.target, self.feat, w, self.sums, self.gL, self.gpred,
+                                          gframe, self.parts, t)
+            return gframe if t >= 1 else None
+        T_in = self.T_in
+        self.parts[t, :, :T_in] = torch.einsum("bmxy,bkxy->mk", gh, self._window(t))
+        if self.F:
+            self.parts[t, :, T_in:self.C] = torch.einsum("bmxy,fxy->mf", gh, self.feat)
+        self.parts[t, :, self.C] = gh.sum((0, 2, 3))
+        if t == 0:
+            return None
+        gx = torch.einsum("mk,bmxy->bkxy", w[:, :T_in], gh)
+        for k in range(max(0, T_in - t), T_in - 1):
+            self.gpred[:, t + k - T_in] += gx[:, k]
+        return ((self.gpred[:, t - 1] + gx[:, T_in - 1]) + self._loss_term(t - 1)).unsqueeze(1)
+
+    def wgrad_finish(self):
+        """-> gw (Cm, C), gb (Cm): the sum of every window's blocks, ONE launch on the device"""
+        if self.native:
+            from .. import _native
+            return _native.channel_wgrad_finish(self.parts, self.C, self.Cm, True)
+        total = self.parts.sum(0)
+        return total[:, :self.C].contiguous(), total[:, self.C].contiguous()
+
+
+# The chain h_t -> body -> im_t -> h_{t+1} makes autograd run the three Functions in REVERSE step order: _RolloutLastFn first, then
+# _RolloutStepFn of step T - 2 ... 0, then _RolloutFirstFn (h_0 has no other producer, and every later node hangs on it through im_0).
+# That order is what the accumulation relies on: when step t's node runs, every later window has added its share to gpred[:, t].
+class _RolloutFirstFn(torch.autograd.Function):
+    """(w, b) -> h_0.  backward: window 0's weight sums, then the ONE finish over all windows' blocks -> gw, gb."""
+
+    @staticmethod
+    def forward(ctx, w, bias, state):
+        ctx.state = state
+        ctx.save_for_backward(w)
+        return state.lift(w, bias, 0)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gh):
+        (w,) = ctx.saved_tensors
+        ctx.state.lift_backward(gh, w, 0)
+        gw, gb = ctx.state.wgrad_finish()
+        return gw, gb, None
+
+
+class _RolloutStepFn(torch.autograd.Function):
+    """(im_t, w, b) -> h_{t+1}: record the frame, lift the next window.  backward: K19-B -> the gradient of im_t; None for w / b, whose
+    blocks wait in the workspace for _RolloutFirstFn."""
+
+    @staticmethod
+    def forward(ctx, im, w, bias, state, t):
+        ctx.state, ctx.t = state, t
+        ctx.save_for_backward(w)
+        state.record_frame(im, t)
+        return state.lift(w, bias, t + 1)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gh):
+        (w,) = ctx.saved_tensors
+        return ctx.state.lift_backward(gh, w, ctx.t + 1), None, None, None, None
+
+
+class _RolloutLastFn(torch.autograd.Function):
+    """im_{T-1} -> loss: record the frame, finish the sums.  backward: store gL, clear gpred -> the last frame's loss gradient."""
+
+    @staticmethod
+    def forward(ctx, im, state):
+        ctx.state = state
+        state.record_frame(im, state.T - 1)
+        return state.finish()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gL):
+        return ctx.state.seed(gL), None
+
+
+def _rollout_loss_native(model, xx, yy, T_f, step):
+    """ns2d_rollout_loss(native=True): no silent fallback - whatever the native path does not cover raises."""
+    limits = (f"step == 1, a model with fc / body_cf / get_grid, (B, S, S, T) tensors of one dtype and device, T_in + features <= "
+              f"{NATIVE_ROLLOUT_MAX_C}, a first lift of at most {NATIVE_ROLLOUT_MAX_CM} channels, 1 <= T_f <= {NATIVE_ROLLOUT_MAX_T} within yy")
+    ok = (step == 1 and all(hasattr(model, a) for a in ("fc", "body_cf", "get_grid")) and xx.dim() == 4 and yy.dim() == 4
+          and xx.dtype == yy.dtype and xx.device == yy.device and xx.dtype.is_floating_point and xx.numel() > 0
+          and 1 <= T_f <= min(NATIVE_ROLLOUT_MAX_T, yy.shape[-1]) and getattr(model.fc, "bias", None) is not None)
+    if ok:
+        F = model.get_grid(xx.shape, xx.device).shape[-1]
+        w = model.fc.weight
+        ok = w.dim() == 2 and w.shape[1] == xx.shape[-1] + F and w.shape[1] <= NATIVE_ROLLOUT_MAX_C and w.shape[0] <= NATIVE_ROLLOUT_MAX_CM \
+            and w.dtype == xx.dtype and w.device == xx.device
+    if not ok:
+        raise RuntimeError(f"ns2d_rollout_loss(native=True) needs {limits} (got step = {step}, T_f = {T_f}, {type(model).__name__}, "
+                           f"xx {tuple(xx.shape)} {xx.dtype}, yy {tuple(yy.shape)} {yy.dtype})")
+    state = _RolloutTrain(model, xx.detach(), yy.detach(), T_f)
+    w, bias = model.fc.weight, model.fc.bias
+    h = _RolloutFirstFn.apply(w, bias, state)
+    for t in range(T_f - 1):
+        h = _RolloutStepFn.apply(model.body_cf(h), w, bias, state, t)
+    return _RolloutLastFn.apply(model.body_cf(h), state)
 
 
 def _rollout_native_applies(model, xx, yy, T_f, step):
