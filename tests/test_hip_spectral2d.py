@@ -35,6 +35,9 @@ DFT_SHAPES = [
     (3, 16, 16, 4, 5), (2, 21, 18, 4, 5), (2, 23, 23, 11, 12), (1, 40, 44, 17, 20), (2, 85, 85, 12, 12),
     (1, 90, 90, 18, 18), (2, 111, 111, 8, 8), (1, 223, 223, 8, 8), (1, 64, 66, 32, 33), (2, 10, 14, 7, 5),
     (1, 7, 130, 3, 40), (1, 130, 6, 40, 4), (1, 1, 2, 1, 2), (1, 421, 421, 20, 20),
+    # the two tile forms of K1 with H != W and a ragged last row tile: full tile <1, 1, R4 = 0> with several waves per image (the
+    # cross-wave reduction) and <2, 2, 1> (4x4x1 regroup, two corner tiles); half tile <2, 1, 1> and <2, 3, 1> (paired column stage)
+    (5, 37, 91, 6, 9), (3, 50, 133, 12, 20), (3, 40, 203, 5, 20), (2, 45, 227, 20, 20),
     # many small images: the plane-batched kernels K1p / K3p (n_img >= 128, H*W <= 2048, W <= 64, 2 m1 <= 48, 2 m2 <= 32)
     (130, 16, 16, 6, 6), (200, 64, 20, 16, 8), (129, 64, 13, 22, 5), (128, 48, 26, 14, 8), (160, 32, 32, 14, 14),
     (128, 21, 18, 4, 5), (131, 23, 23, 11, 12), (128, 16, 15, 8, 8), (1100, 10, 14, 5, 5), (150, 4, 4, 2, 3),

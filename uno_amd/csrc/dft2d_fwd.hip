@@ -1,5 +1,7 @@
-// K1 dispatcher + the 16x16x4-only instantiations; the kernel lives in dft2d_fwd_kernel.h
+// K1 dispatcher + the 16x16x4-only instantiations; the three forms of the kernel live in the headers below
 #include "dft2d_fwd_kernel.h"
+#include "dft2d_fwd_ft_kernel.h"
+#include "dft2d_fwd_ht_kernel.h"
 
 namespace uno {
 

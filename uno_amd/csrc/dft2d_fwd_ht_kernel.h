@@ -17,10 +17,7 @@
 // with ONE 14 KB buffer, so both waits are exposed to the wave - and hidden by the other wave of the SIMD, which is in its
 // compute phases then.  Twiddles come from the operand-layout table in LDS shared by the workgroup's 8 waves.
 #pragma once
-#include "uno_common.h"
-#include "dft2d_fwd_ft_kernel.h"
-#include <algorithm>
-#include <cstdio>
+#include "dft2d_fwd_common.h"
 
 namespace uno {
 
@@ -34,7 +31,7 @@ struct HtSplit { int cs, QL, QR, len_in, seg, s0, off0; };
 // off0 on; slot k >= 1 (seg floats, at s0 + (k - 1) seg) holds run k = [right part of row k-1 | left part of row k].  The inner
 // half reuses the slots, one row each.  seg = 4 (mod 8) floats keeps the 16 rows of an operand read off each other's banks.
 __host__ __device__ inline HtSplit ht_split(int W) {
-    const int P = (W - 1) >> 1, nfull = P >> 4;
+    const int nfull = fwd_columns(W).nfull;
     HtSplit s;
     int cs = (W - 2 + 32) / 64;
     cs = cs < 1 ? 1 : cs;
@@ -67,14 +64,9 @@ __global__ __launch_bounds__(64 * HT_WAVES) void dft2d_fwd_ht_kernel(Dft2dParams
     const int r16 = lane & 15;
     const int kk = lane >> 4;
     const unsigned H8 = 8u * H;
-
-    const int P = (W - 1) >> 1;
-    const int nfull = P >> 4;
-    const int prem = P - (nfull << 4);
-    const int ntail = prem + 1 + ((W & 1) ? 0 : 1);
-    const int tailsteps = (ntail + 3) >> 2;
+    UNO_FWD_COLUMN_PAIRS(W);
     const int nk = 4 * nfull + tailsteps;
-    const int nka = 4 * nfull + FT_TAILMAX;
+    const int nka = UNO_FWD_TABLE_STEPS(nfull);
     const HtSplit sp = ht_split(W);
     const int cs = sp.cs, QL = sp.QL, QR = sp.QR, LEN_IN = sp.len_in, SEG = sp.seg, S0 = sp.s0, OFF0 = sp.off0;
     auto slot_base = [&](int k) { return k == 0 ? 0 : S0 + (k - 1) * SEG; };
@@ -91,14 +83,8 @@ __global__ __launch_bounds__(64 * HT_WAVES) void dft2d_fwd_ht_kernel(Dft2dParams
     const int nrt = (H + 15) >> 4;
     float* buf = sBuf + (size_t)wave * buf_stride;
 
-    // buffer resource = [128-byte aligned start of the image, end of the tensor): offsets are non-negative, reads past the
-    // tensor return zero
-    const float* timg = p.in + (size_t)(active ? image : 0) * H * W;
-    const uintptr_t ibase = reinterpret_cast<uintptr_t>(timg) & ~uintptr_t(127);
-    const int a0 = (int)((reinterpret_cast<uintptr_t>(timg) - ibase) >> 2);
-    const unsigned long long span = reinterpret_cast<uintptr_t>(p.in + (size_t)p.n_img * H * W) - ibase;
-    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        reinterpret_cast<void*>(ibase), 0, (int)(unsigned)std::min<unsigned long long>(span, 0xffffffffull), 0x00020000);
+    int a0;
+    const __amdgpu_buffer_rsrc_t rsrc = image_rsrc(p.in, p.n_img, H, W, active ? image : 0, &a0);
     // one run: floats [m, m + len) from the aligned base -> LDS floats [dst + (m & 3), ...): the fetch starts at the 16-byte
     // boundary below m, so element e of the run lands at dst + (m & 3) + e
     auto fetch_run = [&](int m, int len, float* dst) {
@@ -135,28 +121,7 @@ __global__ __launch_bounds__(64 * HT_WAVES) void dft2d_fwd_ht_kernel(Dft2dParams
 
     // ---- tables (built while the first half tile is on its way)
     for (int n = tid; n < H; n += nthreads) sTwH[n] = p.twH[n];
-    for (int e = tid; e < nk * 64; e += nthreads) {
-        const int ln = e & 63, q = e >> 6, ks = ln >> 4;
-        unsigned w;
-        if (q < 4 * nfull) {
-            w = 1u + 16u * (q >> 2) + 4u * ks + (q & 3);
-        } else {
-            const int qt = 4 * (q - 4 * nfull) + ks;
-            w = qt < prem ? 1u + 16u * nfull + qt : ((qt == prem + 1 && !(W & 1)) ? (unsigned)(W >> 1) : 0u);
-        }
-#pragma unroll
-        for (int t = 0; t < NTF; ++t) {
-            const unsigned l = (unsigned)min(16 * t + (ln & 15), m2 - 1);
-            sTabF[((size_t)q * NTF + t) * 64 + ln] = p.twW[(w * l) % (unsigned)W];
-        }
-        if ((ln & 12) == 0) {
-#pragma unroll
-            for (int g = 0; g < R4; ++g) {
-                const unsigned l = (unsigned)min(16 * NTF + 4 * g + (ln & 3), m2 - 1);
-                sTab4[((size_t)q * R4 + g) * 16 + 4 * ks + (ln & 3)] = p.twW[(w * l) % (unsigned)W];
-            }
-        }
-    }
+    UNO_FWD_BUILD_OPERAND_TABLES();
     __syncthreads();
 
     // Column stage in +-k PAIRED form where that saves row tiles (MT >= 3): the kept rows are the frequencies +k (lo corner row k,
@@ -167,29 +132,7 @@ __global__ __launch_bounds__(64 * HT_WAVES) void dft2d_fwd_ht_kernel(Dft2dParams
     // this kernel's MFMA cycles), 12 against 16 at modes1 = 32.  K3 has used the same pairing since round 1.
     constexpr bool PAIR = MT >= 3 && NT * MT < 12;      // (NT, MT) = (3, 4), (3, 5): the four accumulator sets no longer fit 256 VGPRs
     constexpr int MP = PAIR ? MT / 2 + 1 : MT;          // >= ceil((m1 + 1) / 16) for every m1 <= 8 MT
-    int Kj[MP];
-    bool jvalid[MP];
-#pragma unroll
-    for (int mt = 0; mt < MP; ++mt) {
-        const int j = 16 * mt + r16;
-        if constexpr (PAIR) {
-            jvalid[mt] = j <= m1;                       // k = j: 0 .. m1
-            Kj[mt] = jvalid[mt] ? j : 0;
-        } else {
-            jvalid[mt] = j < 2 * m1;
-            Kj[mt] = jvalid[mt] ? corner_freq(j, m1, H) : 0;
-        }
-    }
-    // !PAIR: Xr / Xi = Re / Im of the spectrum rows, Yr / Yi unused.  PAIR: Xr = Re C, Xi = Re S, Yr = -Im C, Yi = -Im S
-    // (the row stage hands over Tn = -Im T)
-    f32x4 Xr[MP][NT], Xi[MP][NT], Yr[PAIR ? MP : 1][NT], Yi[PAIR ? MP : 1][NT];
-#pragma unroll
-    for (int mt = 0; mt < MP; ++mt)
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            Xr[mt][t] = f32x4{0, 0, 0, 0}; Xi[mt][t] = f32x4{0, 0, 0, 0};
-            if (PAIR || mt == 0) { Yr[PAIR ? mt : 0][t] = f32x4{0, 0, 0, 0}; Yi[PAIR ? mt : 0][t] = f32x4{0, 0, 0, 0}; }
-        }
+    UNO_FWD_ACCUMULATORS(PAIR, MP);             // Xr, Xi (PAIR: and Yr, Yi): this wave's partial spectrum; Kj, jvalid: its rows / its k
 
     const float2* tabF = sTabF + lane;
     const float2* tab4 = sTab4 + 4 * kk + (lane & 3);
@@ -221,8 +164,8 @@ __global__ __launch_bounds__(64 * HT_WAVES) void dft2d_fwd_ht_kernel(Dft2dParams
             Tn[t] = mfma16((D_), (TWF_)[t].y, Tn[t]);                                     \
         }                                                                                 \
         _Pragma("unroll") for (int g = 0; g < R4; ++g) {                                  \
-            Qr[g] = ft_mfma4((E_), (TW4_)[g].x, Qr[g]);                                   \
-            Qn[g] = ft_mfma4((D_), (TW4_)[g].y, Qn[g]);                                   \
+            Qr[g] = mfma4((E_), (TW4_)[g].x, Qr[g]);                                   \
+            Qn[g] = mfma4((D_), (TW4_)[g].y, Qn[g]);                                   \
         }                                                                                 \
     } while (0)
             // chunks [c_lo, c_hi) of the row stage: lane (row r16, k-slot kk) owns column pairs w = 1 + 16 c + 4 kk + s; pl / pr
@@ -279,7 +222,7 @@ __global__ __launch_bounds__(64 * HT_WAVES) void dft2d_fwd_ht_kernel(Dft2dParams
                 const float2* tf = tabF + (size_t)(4 * nfull) * (NTF * 64);
                 const float2* t4 = tab4 + (size_t)(4 * nfull) * (R4 * 16);
 #pragma unroll
-                for (int s = 0; s < FT_TAILMAX; ++s) {
+                for (int s = 0; s < FWD_TAILMAX; ++s) {
                     if (s < tailsteps) {
                         const int q = 4 * s + kk;
                         const bool pair = q < prem;
@@ -307,159 +250,35 @@ __global__ __launch_bounds__(64 * HT_WAVES) void dft2d_fwd_ht_kernel(Dft2dParams
                 request_outer(rt + NW);
             }
 
-            if constexpr (R4 > 0) {
-                // 4x4x1 result: lane 16 ws + 4 rg + j, reg i = partial T[row 4 rg + i][mode 16 NTF + 4 g + j] of k-slot ws.
-                // Sum over the four k-slots, then move to the 16x16x4 accumulator layout stage B consumes
-                // (lane (kk, n), reg s = T[row 4 kk + s][mode n]); columns n >= 4 R4 of the last tile are zero.
-                f32x4 lastR = f32x4{0, 0, 0, 0}, lastN = f32x4{0, 0, 0, 0};
-                const int src = 20 * kk + (r16 & 3);
-#pragma unroll
-                for (int g = 0; g < R4; ++g)
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        float vr = Qr[g][i], vn = Qn[g][i];
-                        vr += __shfl_xor(vr, 16); vn += __shfl_xor(vn, 16);
-                        vr += __shfl_xor(vr, 32); vn += __shfl_xor(vn, 32);
-                        const float gr = __shfl(vr, src), gn = __shfl(vn, src);
-                        if ((r16 >> 2) == g) { lastR[i] = gr; lastN[i] = gn; }
-                    }
-                Tr[NT - 1] = lastR;
-                Tn[NT - 1] = lastN;
-            }
-
-            // ---- stage B: X[j][l] += exp(-i theta(j,h)) * T[h][l], h = 16 rt + 4 kk + s
-            unsigned idxB[MP];
-            float2 twB[MP];
-#pragma unroll
-            for (int mt = 0; mt < MP; ++mt) {
-                const unsigned i0 = 8u * (((unsigned)Kj[mt] * (unsigned)(16 * rt + 4 * kk)) % (unsigned)H);
-                twB[mt] = lds_tw(sTwH, i0);
-                idxB[mt] = wrap_add(i0, 8u * (unsigned)Kj[mt], H8);
-            }
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                const bool hvalid = (16 * rt + 4 * kk + s) < H;
-                float2 twBn[MP];
-#pragma unroll
-                for (int mt = 0; mt < MP; ++mt) {
-                    twBn[mt] = lds_tw(sTwH, idxB[mt]);
-                    idxB[mt] = wrap_add(idxB[mt], 8u * (unsigned)Kj[mt], H8);
-                }
-#pragma unroll
-                for (int mt = 0; mt < MP; ++mt) {
-                    const bool v = hvalid && jvalid[mt];
-                    const float ac = v ? twB[mt].x : 0.f;
-                    if constexpr (PAIR) {
-                        const float as = v ? twB[mt].y : 0.f;
-#pragma unroll
-                        for (int t = 0; t < NT; ++t) {
-                            Xr[mt][t] = mfma16(ac, Tr[t][s], Xr[mt][t]);         // Re C
-                            Yr[mt][t] = mfma16(ac, Tn[t][s], Yr[mt][t]);         // -Im C
-                            Xi[mt][t] = mfma16(as, Tr[t][s], Xi[mt][t]);         // Re S
-                            Yi[mt][t] = mfma16(as, Tn[t][s], Yi[mt][t]);         // -Im S
-                        }
-                    } else {
-                        const float ans = v ? -twB[mt].y : 0.f;
-                        const float anc = -ac;
-#pragma unroll
-                        for (int t = 0; t < NT; ++t) {
-                            Xr[mt][t] = mfma16(ac, Tr[t][s], Xr[mt][t]);
-                            Xi[mt][t] = mfma16(anc, Tn[t][s], Xi[mt][t]);
-                            Xr[mt][t] = mfma16(ans, Tn[t][s], Xr[mt][t]);
-                            Xi[mt][t] = mfma16(ans, Tr[t][s], Xi[mt][t]);
-                        }
-                    }
-                }
-#pragma unroll
-                for (int mt = 0; mt < MP; ++mt) twB[mt] = twBn[mt];
-            }
+            UNO_FWD_REGROUP_4X4();              // the 4-mode groups join Tr / Tn
+            UNO_FWD_STAGE_B(PAIR, MP);          // columns: X += F T, or C += cos T, S += sin T
         }
     }
 
-    // ---- several waves per image: deterministic tree reduction of the partial spectra through the (now free) buffers
+    // ---- several waves per image: the partial spectra are combined through the (now free) buffers
     if (NW > 1) __syncthreads();            // every wave of the workgroup is done with its buffer
-    // one pass per accumulator pair ((Xr, Xi), and in the paired form (Yr, Yi)): MP * NT * 8 * 64 floats fit a wave's buffer
+    // one pass per accumulator pair ((Xr, Xi), and in the paired form (Yr, Yi))
     auto reduce_pair = [&](f32x4 (*A)[NT], f32x4 (*Bv)[NT], int stride) {
-        if (wsub >= stride && wsub < 2 * stride) {
-            float* dst = sBuf + (size_t)(wave - stride) * buf_stride;         // the partner's buffer
-#pragma unroll
-            for (int mt = 0; mt < MP; ++mt)
-#pragma unroll
-                for (int t = 0; t < NT; ++t)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        dst[((mt * NT + t) * 8 + r) * 64 + lane] = A[mt][t][r];
-                        dst[((mt * NT + t) * 8 + 4 + r) * 64 + lane] = Bv[mt][t][r];
-                    }
-        }
-        __syncthreads();
-        if (wsub < stride && wsub + stride < NW) {
-#pragma unroll
-            for (int mt = 0; mt < MP; ++mt)
-#pragma unroll
-                for (int t = 0; t < NT; ++t)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        A[mt][t][r] += buf[((mt * NT + t) * 8 + r) * 64 + lane];
-                        Bv[mt][t][r] += buf[((mt * NT + t) * 8 + 4 + r) * 64 + lane];
-                    }
-        }
-        __syncthreads();
+        UNO_FWD_REDUCE_STEP(A, Bv, MP, buf, sBuf + (size_t)(wave - stride) * buf_stride, wsub, stride);
     };
     for (int stride = 2; stride >= 1; stride >>= 1) {
         if (stride >= NW) continue;
         reduce_pair(Xr, Xi, stride);
         if constexpr (PAIR) reduce_pair(Yr, Yi, stride);
     }
-
-    if (active && wsub == 0) {
-        float2* out = reinterpret_cast<float2*>(p.out) + spectrum_index(p, image) * 2 * m1 * m2;
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            const int l = 16 * t + r16;
-            if (l >= m2) continue;
-            const float cs_ = p.scale * (p.herm ? herm_weight(l, W) : 1.0f);
-#pragma unroll
-            for (int mt = 0; mt < MP; ++mt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int j = 16 * mt + 4 * kk + r;
-                    if constexpr (PAIR) {
-                        // k = j:  X[+k] = C - i S = (Re C - (-Im S)... with Yr = -Im C, Yi = -Im S:  Re = Xr - Yi, Im = -Yr - Xi;  X[-k]: S -> -S
-                        const float cr = Xr[mt][t][r], sr = Xi[mt][t][r], cn = Yr[PAIR ? mt : 0][t][r], sn = Yi[PAIR ? mt : 0][t][r];
-                        if (j < m1) {
-                            const float f = (p.mask && !row_survives(j, m1, H)) ? 0.f : cs_;
-                            out[(size_t)j * m2 + l] = make_float2((cr - sn) * f, (-cn - sr) * f);
-                        }
-                        if (j >= 1 && j <= m1) {
-                            const int jm = 2 * m1 - j;
-                            const float f = (p.mask && !row_survives(jm, m1, H)) ? 0.f : cs_;
-                            out[(size_t)jm * m2 + l] = make_float2((cr + sn) * f, (-cn + sr) * f);
-                        }
-                    } else {
-                        if (j < 2 * m1) {
-                            const float f = (p.mask && !row_survives(j, m1, H)) ? 0.f : cs_;
-                            out[(size_t)j * m2 + l] = make_float2(Xr[mt][t][r] * f, Xi[mt][t][r] * f);
-                        }
-                    }
-                }
-        }
-    }
+    if (active && wsub == 0) UNO_FWD_STORE_SPECTRUM(PAIR, MP, image);
 }
 
 // ---- launcher side
 static size_t fwd_ht_lds_bytes(const Dft2dParams& p, int NTF, int R4, int waves) {
-    const int P = (p.W - 1) >> 1, nfull = P >> 4;
-    const size_t nka = (size_t)4 * nfull + FT_TAILMAX;
     const HtSplit sp = ht_split(p.W);
-    return (size_t)waves * (sp.s0 + 15 * sp.seg) * 4 + nka * ((size_t)NTF * 512 + (size_t)R4 * 128) + (size_t)p.H * 8;
+    return (size_t)waves * (sp.s0 + 15 * sp.seg) * 4 + fwd_table_bytes(p.W, NTF, R4) + (size_t)p.H * 8;
 }
 
-// NW in {1, 2, 4} waves per image, G = 8 / NW images per workgroup (fewer when the images do not fill the CUs)
+// HT_WAVES waves per workgroup; the point of this form is two waves per SIMD
 static bool fwd_ht_geometry(const Dft2dParams& p, int NT, int MT, int R4, FwdFtGeometry* out) {
     const int NTF = R4 > 0 ? NT - 1 : NT;
-    const int P = (p.W - 1) >> 1, nfull = P >> 4;
-    if (p.bf16 || p.rowfreq || nfull < 2 || p.W <= FT_MAXW) return false;
+    if (p.bf16 || p.rowfreq || fwd_columns(p.W).nfull < 2) return false;
     // measured (1024 images, in-block, input cold): 421^2 227 us against 257 for the register path, 446^2 218 / 230, 223^2 51 / 47:
     // short rows make short runs (a run of the inner half of a 223-wide row is 0.4 KB), the register path keeps those
     // round 3: from 200 columns.  The 51 / 47 us above were taken with inputs that a standalone loop keeps partly cache-resident;
@@ -470,40 +289,14 @@ static bool fwd_ht_geometry(const Dft2dParams& p, int NT, int MT, int R4, FwdFtG
     if (sp.QL + sp.QR + 3 > 256 || sp.len_in + 3 > 256 || sp.len_in < 8) return false;      // a run is one 64-lane x 16-byte fetch
     const int MPh = (MT >= 3 && NT * MT < 12) ? MT / 2 + 1 : MT;                          // row tiles of the (paired) column stage
     if ((size_t)MPh * NT * 8 * 64 > (size_t)(sp.s0 + 15 * sp.seg)) return false;         // reduction slots must fit a buffer
-    const int nrt = (p.H + 15) / 16, cus = ft_device_cu_count();
-    long long best_cost = -1;
-    for (int nw = 1; nw <= 4 && nw <= nrt; nw *= 2) {
-        int g = HT_WAVES / nw;
-        while (g > 1 && (long long)(p.n_img + g - 1) / g < cus) --g;
-        while (g > 1 && fwd_ht_lds_bytes(p, NTF, R4, nw * g) > HT_LDS_LIMIT) --g;
-        const size_t lds = fwd_ht_lds_bytes(p, NTF, R4, nw * g);
-        if (lds > HT_LDS_LIMIT) continue;
-        const long long per_cu = std::max<long long>(1, std::min<long long>((long long)(HT_LDS_LIMIT / lds), 16 / (nw * g)));
-        if (per_cu * nw * g < 6 && (long long)p.n_img * nw >= 8LL * cus) continue;      // the point of this form is two waves per SIMD
-        const long long groups = (p.n_img + g - 1) / g;
-        const long long rounds = (groups + cus * per_cu - 1) / (cus * per_cu);
-        const long long cost = rounds * ((nrt + nw - 1) / nw);
-        if (best_cost < 0 || cost < best_cost) { best_cost = cost; *out = FwdFtGeometry{nw, g, lds}; }
-    }
-    return best_cost >= 0;
+    return fwd_tile_geometry(p, NTF, R4, FwdTileForm{HT_WAVES, HT_LDS_LIMIT, 6, fwd_ht_lds_bytes}, out);
 }
 
 template <int NT, int MT, int R4>
-static int launch_fwd_ht(Dft2dParams p, const FwdFtGeometry& g, hipStream_t s) {
-    auto k = dft2d_fwd_ht_kernel<NT, MT, R4>;
-    static int lds_slot[64];
-    if (!ensure_dynamic_lds(reinterpret_cast<const void*>(k), g.lds, lds_slot)) { set_error("dft2d_fwd: cannot raise dynamic LDS to %zu", g.lds); return -4; }
-    p.nw = g.nw;
-    p.rev = next_sweep_reversed(SWEEP_K1);
+static int launch_fwd_ht(const Dft2dParams& p, const FwdFtGeometry& g, hipStream_t s) {
     char name[64];
     snprintf(name, sizeof(name), "uno::dft2d_fwd_ht_kernel<%d, %d, %d>", NT, MT, R4);
-    {
-        ProfScope prof(name, (double)p.n_img * ((double)p.H * p.W * 4.0 + 2.0 * p.m1 * p.m2 * 8.0), s);
-        hipLaunchKernelGGL(k, dim3((p.n_img + g.g - 1) / g.g), dim3(64 * g.nw * g.g), g.lds, s, p);
-    }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("dft2d_fwd launch: %s", hipGetErrorString(e)); return -5; }
-    return 0;
+    return launch_fwd_tile<dft2d_fwd_ht_kernel<NT, MT, R4>>(name, p, g, next_sweep_reversed(SWEEP_K1), s);
 }
 
 }  // namespace uno

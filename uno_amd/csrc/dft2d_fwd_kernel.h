@@ -18,20 +18,9 @@
 // Each wave keeps a partial X for its tiles; a tree reduction through LDS (fixed order: deterministic)
 // combines them and wave 0 writes the 2*m1*m2 complex results.
 #pragma once
-#include "uno_common.h"
-#include "dft2d_fwd_ft_kernel.h"
-#include "dft2d_fwd_ht_kernel.h"
-#include <cstdio>
+#include "dft2d_fwd_common.h"
 
 namespace uno {
-
-constexpr int TAILMAX = 5;      // tail <= 15 pairs + w=0 + Nyquist column = 17 elements = 5 k-steps
-
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
-    // v_mfma_f32_4x4x1_16b_f32: 16 independent 4x4 outer products, block = lane / 4 (probed on gfx950:
-    // tools/probes/mfma4x4_probe.hip): A[i] = lane 4*block + i, B[j] = lane 4*block + j, D[i][j] = lane 4*block + j, reg i
-    return __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, c, 0, 0, 0);
-}
 
 // waves per SIMD the register allocator is asked to fit (accumulators: 8 NT MT for X + 8 NT for T)
 template <int NT, int MT>
@@ -56,9 +45,9 @@ __global__ __launch_bounds__(256, (fwd_waves_per_simd<NT, MT>())) void dft2d_fwd
     const int H = p.H, W = p.W, m1 = p.m1, m2 = p.m2;
     float2* sTwW = reinterpret_cast<float2*>(smem);
     float2* sTwH = sTwW + W;
-    int* sTailW = reinterpret_cast<int*>(sTwH + H);                  // [TAILMAX][2][64]: left / right column of a tail element (-1 = none)
-    unsigned* sTailI = reinterpret_cast<unsigned*>(sTailW + TAILMAX * 2 * 64);   // [TAILMAX][NS][64]: its twiddle offset per stage-A stream
-    float* sRed = reinterpret_cast<float*>(sTailI + TAILMAX * NS * 64);
+    int* sTailW = reinterpret_cast<int*>(sTwH + H);                  // [FWD_TAILMAX][2][64]: left / right column of a tail element (-1 = none)
+    unsigned* sTailI = reinterpret_cast<unsigned*>(sTailW + FWD_TAILMAX * 2 * 64);   // [FWD_TAILMAX][NS][64]: its twiddle offset per stage-A stream
+    float* sRed = reinterpret_cast<float*>(sTailI + FWD_TAILMAX * NS * 64);
 
     const int tid = threadIdx.x;
     const int nthreads = blockDim.x;
@@ -68,25 +57,13 @@ __global__ __launch_bounds__(256, (fwd_waves_per_simd<NT, MT>())) void dft2d_fwd
     const int r16 = lane & 15;
     const int kk = lane >> 4;
     const unsigned W8 = 8u * W, H8 = 8u * H;
-
-    // column-pair bookkeeping: pairs (w, W-w), w = 1..P; singles w = 0 and (W even) w = W/2
-    const int P = (W - 1) >> 1;
-    const int nfull = P >> 4;                   // chunks of 16 pairs handled by the vector path
-    const int prem = P - (nfull << 4);
-    const int ntail = prem + 1 + ((W & 1) ? 0 : 1);
-    const int tailsteps = (ntail + 3) >> 2;
+    UNO_FWD_COLUMN_PAIRS(W);                    // nfull: the chunks handled by the vector path
 
     for (int n = tid; n < W; n += nthreads) sTwW[n] = p.twW[n];
     for (int n = tid; n < H; n += nthreads) sTwH[n] = p.twH[n];
     // tail element of k-step s, k-slot (lane >> 4): pairs beyond the last full chunk, then w = 0, then the Nyquist column
-    for (int e = tid; e < TAILMAX * 64; e += nthreads) {
-        const int ln = e & 63, sq = e >> 6;
-        const int q = 4 * sq + (ln >> 4);
-        const bool pair = q < prem;
-        const bool nyq = (q == prem + 1) && !(W & 1);
-        const int w = pair ? 1 + 16 * nfull + q : (nyq ? (W >> 1) : 0);
-        sTailW[(sq * 2 + 0) * 64 + ln] = (pair || q == prem || nyq) ? w : -1;
-        sTailW[(sq * 2 + 1) * 64 + ln] = pair ? W - w : -1;
+    for (int e = tid; e < FWD_TAILMAX * 64; e += nthreads) {
+        UNO_FWD_PUT_TAIL_COLUMNS(e);
         for (int t = 0; t < NS; ++t) {
             const int lm = t < NTF ? 16 * t + (ln & 15) : 16 * NTF + 4 * (t - NTF) + (ln & 3);
             const unsigned l = (unsigned)min(lm, m2 - 1);
@@ -106,21 +83,7 @@ __global__ __launch_bounds__(256, (fwd_waves_per_simd<NT, MT>())) void dft2d_fwd
         stepL[t] = 8u * l;
         jump[t] = 8u * ((13u * l) % (unsigned)W);      // step from the last column pair of a chunk to the first of the next
     }
-    // stage-B A operand rows (corner rows) owned by this lane
-    int Kj[MT];
-    bool jvalid[MT];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-        const int j = 16 * mt + r16;
-        jvalid[mt] = j < 2 * m1;
-        Kj[mt] = jvalid[mt] ? corner_freq(j, m1, H) : 0;
-    }
-
-    f32x4 Xr[MT][NT], Xi[MT][NT];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int t = 0; t < NT; ++t) { Xr[mt][t] = f32x4{0, 0, 0, 0}; Xi[mt][t] = f32x4{0, 0, 0, 0}; }
+    UNO_FWD_ACCUMULATORS(false, MT);            // Xr, Xi: this wave's partial spectrum; Kj, jvalid: the corner rows this lane owns
 
     const in_t* img = reinterpret_cast<const in_t*>(p.in) + (size_t)blockIdx.x * H * W;
     const int nrt = (H + 15) >> 4;
@@ -151,9 +114,9 @@ __global__ __launch_bounds__(256, (fwd_waves_per_simd<NT, MT>())) void dft2d_fwd
     for (; rt < nrt; rt += NW) {
         const in_t* xr = row_ptr(rt);
         asm volatile("" ::: "memory");          // keep the (loop-invariant) LDS table reads inside the loop: registers are scarcer
-        float TL[TAILMAX], TR[TAILMAX];
+        float TL[FWD_TAILMAX], TR[FWD_TAILMAX];
 #pragma unroll
-        for (int s = 0; s < TAILMAX; ++s) {
+        for (int s = 0; s < FWD_TAILMAX; ++s) {
             const int wl = sTailW[(s * 2 + 0) * 64 + lane], wr = sTailW[(s * 2 + 1) * 64 + lane];
             const float vl = io_widen(xr[max(wl, 0)]);    // unconditional (clamped) loads, masked by select
             const float vr = io_widen(xr[max(wr, 0)]);
@@ -226,10 +189,10 @@ __global__ __launch_bounds__(256, (fwd_waves_per_simd<NT, MT>())) void dft2d_fwd
 #pragma unroll
             for (int t = 0; t < NS; ++t) twt[t] = lds_tw(sTwW, sTailI[t * 64 + lane]);
 #pragma unroll
-            for (int s = 0; s < TAILMAX; ++s) {
+            for (int s = 0; s < FWD_TAILMAX; ++s) {
                 float2 twn[NS];
 #pragma unroll
-                for (int t = 0; t < NS; ++t) twn[t] = lds_tw(sTwW, sTailI[((s + 1 < TAILMAX ? s + 1 : s) * NS + t) * 64 + lane]);
+                for (int t = 0; t < NS; ++t) twn[t] = lds_tw(sTwW, sTailI[((s + 1 < FWD_TAILMAX ? s + 1 : s) * NS + t) * 64 + lane]);
                 if (s < tailsteps) {
                     const float E = TL[s] + TR[s];
                     const float D = TL[s] - TR[s];
@@ -247,117 +210,20 @@ __global__ __launch_bounds__(256, (fwd_waves_per_simd<NT, MT>())) void dft2d_fwd
             UNO_LOAD_CHUNK(2, xn, 2);
         }
 
-        if constexpr (R4 > 0) {
-            // 4x4x1 result: lane 16 ws + 4 rg + j, reg i = partial T[row 4 rg + i][mode 16 NTF + 4 g + j] of k-slot ws.
-            // Sum over the four k-slots, then move to the 16x16x4 accumulator layout stage B consumes
-            // (lane (kk, n), reg s = T[row 4 kk + s][mode n]); columns n >= 4 R4 of the last tile are zero.
-            f32x4 lastR = f32x4{0, 0, 0, 0}, lastN = f32x4{0, 0, 0, 0};
-            const int src = 20 * kk + (r16 & 3);
-#pragma unroll
-            for (int g = 0; g < R4; ++g)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    float vr = Qr[g][i], vn = Qn[g][i];
-                    vr += __shfl_xor(vr, 16); vn += __shfl_xor(vn, 16);
-                    vr += __shfl_xor(vr, 32); vn += __shfl_xor(vn, 32);
-                    const float gr = __shfl(vr, src), gn = __shfl(vn, src);
-                    if ((r16 >> 2) == g) { lastR[i] = gr; lastN[i] = gn; }
-                }
-            Tr[NT - 1] = lastR;
-            Tn[NT - 1] = lastN;
-        }
-
-        // stage B: X[j][l] += exp(-i theta(j,h)) * T[h][l], h = 16 rt + 4 kk + s
-        unsigned idxB[MT];
-        float2 twB[MT];
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-            const unsigned i0 = 8u * (((unsigned)Kj[mt] * (unsigned)(16 * rt + 4 * kk)) % (unsigned)H);
-            twB[mt] = lds_tw(sTwH, i0);
-            idxB[mt] = wrap_add(i0, 8u * (unsigned)Kj[mt], H8);
-        }
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const bool hvalid = (16 * rt + 4 * kk + s) < H;
-            float2 twBn[MT];
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) {
-                twBn[mt] = lds_tw(sTwH, idxB[mt]);
-                idxB[mt] = wrap_add(idxB[mt], 8u * (unsigned)Kj[mt], H8);
-            }
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) {
-                const bool v = hvalid && jvalid[mt];
-                const float ac = v ? twB[mt].x : 0.f;
-                const float ans = v ? -twB[mt].y : 0.f;
-                const float anc = -ac;
-#pragma unroll
-                for (int t = 0; t < NT; ++t) {
-                    Xr[mt][t] = mfma16(ac, Tr[t][s], Xr[mt][t]);
-                    Xi[mt][t] = mfma16(anc, Tn[t][s], Xi[mt][t]);
-                    Xr[mt][t] = mfma16(ans, Tn[t][s], Xr[mt][t]);
-                    Xi[mt][t] = mfma16(ans, Tr[t][s], Xi[mt][t]);
-                }
-            }
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) twB[mt] = twBn[mt];
-        }
+        UNO_FWD_REGROUP_4X4();                  // the 4-mode groups join Tr / Tn
+        UNO_FWD_STAGE_B(false, MT);             // columns: X += F T, the stage-A accumulators are the B operand
     }
 #undef UNO_LOAD_CHUNK
 #undef UNO_COMPUTE_CHUNK
 #undef UNO_STAGE_A_MFMA
 
-    // deterministic tree reduction of the per-wave partial spectra through LDS
+    // deterministic tree reduction of the per-wave partial spectra through LDS, then wave 0 writes the image's spectrum
     constexpr int NACC = MT * NT * 8;
     for (int stride = 2; stride >= 1; stride >>= 1) {
         if (stride >= NW) continue;
-        if (wave >= stride && wave < 2 * stride) {
-            float* slot = sRed + (size_t)(wave - stride) * NACC * 64;
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                for (int t = 0; t < NT; ++t)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        slot[((mt * NT + t) * 8 + r) * 64 + lane] = Xr[mt][t][r];
-                        slot[((mt * NT + t) * 8 + 4 + r) * 64 + lane] = Xi[mt][t][r];
-                    }
-        }
-        __syncthreads();
-        if (wave < stride && wave + stride < NW) {
-            const float* slot = sRed + (size_t)wave * NACC * 64;
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                for (int t = 0; t < NT; ++t)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        Xr[mt][t][r] += slot[((mt * NT + t) * 8 + r) * 64 + lane];
-                        Xi[mt][t][r] += slot[((mt * NT + t) * 8 + 4 + r) * 64 + lane];
-                    }
-        }
-        __syncthreads();
+        UNO_FWD_REDUCE_STEP(Xr, Xi, MT, sRed + (size_t)wave * NACC * 64, sRed + (size_t)(wave - stride) * NACC * 64, wave, stride);
     }
-
-    if (wave == 0) {
-        float2* out = reinterpret_cast<float2*>(p.out) + spectrum_index(p, blockIdx.x) * 2 * m1 * m2;
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            const int l = 16 * t + r16;
-            if (l >= m2) continue;
-            const float cs = p.scale * (p.herm ? herm_weight(l, W) : 1.0f);
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int j = 16 * mt + 4 * kk + r;
-                    if (j < 2 * m1) {
-                        const float f = (p.mask && !row_survives(j, m1, H)) ? 0.f : cs;
-                        out[(size_t)j * m2 + l] = make_float2(Xr[mt][t][r] * f, Xi[mt][t][r] * f);
-                    }
-                }
-        }
-    }
+    if (wave == 0) UNO_FWD_STORE_SPECTRUM(false, MT, blockIdx.x);
 }
 
 template <int NT, int MT, bool VEC, int R4, bool BF16>
@@ -366,7 +232,7 @@ static int launch_fwd_b(const Dft2dParams& p, hipStream_t s) {
     const int nrt = (p.H + 15) / 16;
     const int NW = (long long)p.H * p.W < 4096 ? 1 : pick_waves_per_image(nrt);     // small images (3-D planes): one wave each, more images in flight per CU
     const size_t red = (size_t)(NW / 2) * MT * NT * 8 * 64 * sizeof(float);
-    const size_t lds = (size_t)(p.W + p.H) * sizeof(float2) + (size_t)TAILMAX * (2 + NS) * 64 * 4 + red;
+    const size_t lds = (size_t)(p.W + p.H) * sizeof(float2) + (size_t)FWD_TAILMAX * (2 + NS) * 64 * 4 + red;
     if (lds > 160 * 1024) { set_error("dft2d_fwd: grid %dx%d needs %zu B of LDS", p.H, p.W, lds); return -3; }
     auto k = dft2d_fwd_kernel<NT, MT, VEC, R4, BF16>;
     static int lds_slot[64];
@@ -381,6 +247,13 @@ static int launch_fwd_b(const Dft2dParams& p, hipStream_t s) {
     if (e != hipSuccess) { set_error("dft2d_fwd launch: %s", hipGetErrorString(e)); return -5; }
     return 0;
 }
+
+// Form of one launch.  The two tile forms (dft2d_fwd_ft_kernel.h, dft2d_fwd_ht_kernel.h) keep their admission rules; a translation
+// unit that dispatches through launch_fwd_t includes them as well.
+static bool fwd_ft_geometry(const Dft2dParams& p, int NT, int MT, int R4, FwdFtGeometry* out);
+static bool fwd_ht_geometry(const Dft2dParams& p, int NT, int MT, int R4, FwdFtGeometry* out);
+template <int NT, int MT, int R4> static int launch_fwd_ft(const Dft2dParams& p, const FwdFtGeometry& g, hipStream_t s);
+template <int NT, int MT, int R4> static int launch_fwd_ht(const Dft2dParams& p, const FwdFtGeometry& g, hipStream_t s);
 
 template <int NT, int MT, bool VEC, int R4>
 static int launch_fwd_t(const Dft2dParams& p, hipStream_t s) {

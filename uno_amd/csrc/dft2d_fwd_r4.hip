@@ -1,5 +1,7 @@
 // K1 instantiations whose last mode tile runs on 4x4x1 MFMAs (R4 = 1 or 2 groups of four modes)
 #include "dft2d_fwd_kernel.h"
+#include "dft2d_fwd_ft_kernel.h"
+#include "dft2d_fwd_ht_kernel.h"
 
 namespace uno {
 
