@@ -690,13 +690,17 @@ __global__ __launch_bounds__(64 * VI_WAVES) void dft3d_inv_volume_kernel(Vol3dPa
     __syncthreads();
     VOL_STAMP_NOWAIT(4);
 
-    // ---- phase 2: planes.  LDS offsets of this lane's +kappa / -kappa values per k-step (rows past m2: clamped, their twiddles are zero)
+    // ---- phase 2: planes.  LDS offsets of this lane's +kappa / -kappa values per k-step (rows past m2: clamped, their twiddles are zero).
+    // Lanes past the 2 m3 floats of a spectrum row re-read its last float: what they compute meets zero T-axis weights, so it must be
+    // FINITE - at n16 itself the -kappa row of kappa index 0 ran into the row's pad floats (C2 = 32 NT and m3 < 8), which nobody writes:
+    // a NaN left there by an earlier kernel turned the whole plane into NaN
     int zlo[NK2], zhi[NK2];
+    const int nz = min(n16, 2 * m3 - 1);
 #pragma unroll
     for (int ks = 0; ks < NK2; ++ks) {
         const int mk = min(4 * ks + gq, m2 - 1);
-        zlo[ks] = mk * 2 * m3 + n16;
-        zhi[ks] = (2 * m2 - 1 - mk) * 2 * m3 + n16;
+        zlo[ks] = mk * 2 * m3 + nz;
+        zhi[ks] = (2 * m2 - 1 - mk) * 2 * m3 + nz;
     }
     // store plan: byte offsets (inside a plane) of this lane's 4-column pieces of rows P / Q of tile pair u; absent rows / columns -> OOB
     constexpr unsigned OOB = 0xC0000000u;
