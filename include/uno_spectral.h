@@ -184,6 +184,26 @@ int uno_dft2d_inverse_add(const float* spec, float* images, int n_img, int H, in
                           int mask_overlap, const float* addend, int Hs, int Ws, const int* tile_p0, const float* row_op,
                           const int* col_v0, const float* col_op, void* stream);
 
+/* (added under ABI 14: new entry points only, nothing existing changes)  Pruned forward DFT PLUS the down-sampled image from one read of the images:
+ *   spec as uno_dft2d_forward_grouped writes it (group <= 0: the plain layout), and
+ *   resampled[i][j] = sum_{h,w} A[i][h] B[j][w] images[h][w]      (n_img, Ho, Wo) f32
+ * = the truncated input spectrum and the bicubic / align_corners / antialias interpolation (reference integral_operators.py:240-242) of
+ * a down-sampling operator block's input, which uno_resample2d followed by uno_dft2d_forward read twice - and, with the transposed
+ * operators, the gradient spectrum and the point-wise gradient of an up-sampling block.  B (Wo x W) is uno_resample2d's band table of
+ * the columns: col_start [Wo] first source column, col_wt [Wo][KW] taps (zero past the row's end).  A (Ho x H) is given per 16-row
+ * tile of the IMAGE (the kernel carries the output rows a tile contributes to in registers, 13 at most; uno_amd/resample.py
+ * fused_resample_tables builds the tables once per size pair):
+ *   row_tiles [ceil(H/16)][4]       first carried output row i0, output rows complete after this tile (stored, then dropped from the
+ *                                   carried set), bits 0..31 and 32..51 of the mask whose bit 4 c + q is set where
+ *                                   row_op[tile][c][4 q .. 4 q + 3] holds a non-zero weight
+ *   row_op    [ceil(H/16)][13][16]  entry (tile, c, r) = A[i0 + c][16 tile + r], zero outside the matrix
+ * uno_dft2d_forward_resample_applies: 1 where the fused kernel exists (float32, rows of 416..447 elements, Wo <= 256, KW <= 9,
+ * (modes1, modes2) in 17..24 x 17..20 or 1..8 x 1..8, the tiles fit the LDS), else 0 - the caller then runs the two calls. */
+int uno_dft2d_forward_resample_applies(int n_img, int H, int W, int m1, int m2, int Ho, int Wo, int KW);
+int uno_dft2d_forward_resample(const float* images, float* spec, int n_img, int H, int W, int m1, int m2, float scale, int hermitian_cols,
+                               int mask_overlap, int group, int stride, int offset, float* resampled, int Ho, int Wo, const int* col_start,
+                               const float* col_wt, int KW, const int* row_tiles, const float* row_op, void* stream);
+
 /* The two transforms with bfloat16 images (the stages of uno_spectral_conv2d_*_bf16); spectra are c64 as above. */
 int uno_dft2d_forward_bf16(const void* images, float* spec, int n_img, int H, int W, int m1, int m2,
                            float scale, int hermitian_cols, int mask_overlap, void* stream);

@@ -45,6 +45,8 @@ _SIGNATURES = {
     "uno_reserve_cus": (C.c_int, [_i]),
     "uno_sweep_alternation": (C.c_int, [_i]),
     "uno_dft2d_inverse_add_applies": (C.c_int, [_i] * 7),
+    "uno_dft2d_forward_resample_applies": (C.c_int, [_i] * 8),
+    "uno_dft2d_forward_resample": (C.c_int, [_fp, _fp] + [_i] * 5 + [C.c_float] + [_i] * 5 + [_fp, _i, _i, _fp, _fp, _i, _fp, _fp, _fp]),
     "uno_dft2d_inverse_add": (C.c_int, [_fp, _fp] + [_i] * 5 + [C.c_float, _i, _i, _fp, _i, _i, _fp, _fp, _fp, _fp, _fp]),
     "uno_dft2d_forward_grouped": (C.c_int, [_fp, _fp] + [_i] * 5 + [C.c_float] + [_i] * 5 + [_fp]),
     "uno_dft2d_inverse_grouped": (C.c_int, [_fp, _fp] + [_i] * 5 + [C.c_float] + [_i] * 5 + [_fp]),
@@ -426,6 +428,37 @@ def sweep_direction(mode: str, mask: int = 255) -> int:
 def dft2d_inverse_add_applies(n_img, H, W, m1, m2, Hs, Ws) -> bool:
     """True where dft2d_inverse(..., addend=) runs the fused kernel (K3 + up-sampled addend, csrc/dft2d_inv_add_kernel.h)."""
     return bool(lib().uno_dft2d_inverse_add_applies(int(n_img), int(H), int(W), int(m1), int(m2), int(Hs), int(Ws)))
+
+
+def dft2d_forward_resample_applies(n_img, H, W, m1, m2, Ho, Wo, KW) -> bool:
+    """True where dft2d_forward_resample runs (K1 + down-sampled image, csrc/dft2d_fwd_fd_kernel.h)."""
+    return bool(lib().uno_dft2d_forward_resample_applies(int(n_img), int(H), int(W), int(m1), int(m2), int(Ho), int(Wo), int(KW)))
+
+
+def dft2d_forward_resample(images, m1, m2, Ho, Wo, tables, scale=1.0, hermitian_cols=False, mask_overlap=False, out=None, channel_offset=0):
+    """dft2d_forward of float32 images (..., H, W) and, from the same read, their banded resampling to (..., Ho, Wo)
+    (uno_dft2d_forward_resample; the caller checked dft2d_forward_resample_applies).  tables = (col_start, col_wt, row_tiles, row_op) of
+    resample.fused_resample_tables; `out` / channel_offset: dft2d_forward's.  -> (spectra, resampled)."""
+    _require(images, torch.float32, "images")
+    col_start, col_wt, row_tiles, row_op = tables
+    *lead, H, W = images.shape
+    n = _count(lead)
+    group = stride = 0
+    if out is None:
+        spec = torch.empty((*lead, 2 * m1, m2), dtype=torch.complex64, device=images.device)
+    else:
+        _require(out, torch.complex64, "out")
+        if images.dim() != 4 or out.dim() != 4 or out.shape[0] != images.shape[0] or tuple(out.shape[2:]) != (2 * m1, m2) \
+                or channel_offset < 0 or channel_offset + images.shape[1] > out.shape[1]:
+            raise RuntimeError("uno_amd: out must be (B, Ctot, 2*m1, m2) with room for the image channels at channel_offset")
+        spec, group, stride = out, images.shape[1], out.shape[1]
+    res = torch.empty((*lead, Ho, Wo), dtype=torch.float32, device=images.device)
+    with torch.cuda.device(images.device):
+        rc = lib().uno_dft2d_forward_resample(_ptr(images), _ptr(spec), n, H, W, m1, m2, float(scale), int(hermitian_cols), int(mask_overlap),
+                                              int(group), int(stride), int(channel_offset), _ptr(res), int(Ho), int(Wo), _ptr(col_start),
+                                              _ptr(col_wt), int(col_wt.shape[1]), _ptr(row_tiles), _ptr(row_op), _stream(images))
+    _check(rc, "uno_dft2d_forward_resample")
+    return spec, res
 
 
 def dft2d_inverse(spec, H, W, scale=1.0, hermitian_cols=True, mask_overlap=True, channels=None, channel_offset=0,

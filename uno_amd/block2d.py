@@ -7,7 +7,7 @@ from torch.autograd.function import once_differentiable
 from . import _native
 from ._param_grads import _grad_targets, _note_use, _stack_arrived, _stack_grad_slot, _stack_take, _stack_wanted
 from .pointwise import _mix2_forward, _mix2_input_grads, _plain, _wgrad_into
-from .resample import resample_adjoint, resample_forward, upsample_add_tables
+from .resample import fused_resample_tables, resample_adjoint, resample_forward, upsample_add_tables
 
 
 def _half_weights(w1, w2):
@@ -131,6 +131,27 @@ def _fused_addend(t, H, W, m1, m2, adjoint):
     return None if tabs is None else (t, tabs)
 
 
+# Down-sampling blocks (and the backward pass of up-sampling blocks): the forward transform of the full-resolution tensor also writes its
+# resampling to the coarse grid (uno_dft2d_forward_resample), instead of K7 and K1 reading that tensor one after the other.  False: the
+# two kernels (A/B).
+FUSE_FORWARD_RESAMPLE = True
+
+
+def _fused_resample(x, m1, m2, Ho, Wo, adjoint):
+    """Tables for _native.dft2d_forward_resample of x (B, C, H, W) -> its spectrum and its resampling to (Ho, Wo) - resample_forward, or
+    resample_adjoint for an (Ho, Wo) input grid when `adjoint` - or None where the fused kernel does not apply (the caller runs the two)."""
+    if not FUSE_FORWARD_RESAMPLE or x.dtype != torch.float32 or x.dim() != 4 or not x.is_cuda:
+        return None
+    H, W = x.shape[-2], x.shape[-1]
+    n = x.shape[0] * x.shape[1]
+    if Ho * Wo >= H * W or not _native.dft2d_forward_resample_applies(n, H, W, m1, m2, Ho, Wo, 1):
+        return None
+    tabs = fused_resample_tables(H, W, Ho, Wo, str(x.device), bool(adjoint))
+    if tabs is None or not _native.dft2d_forward_resample_applies(n, H, W, m1, m2, Ho, Wo, tabs[1].shape[1]):
+        return None
+    return tabs
+
+
 def _stage_wgrad(stack, gslot, xt, gO, w1, w2, leaves, both_gw, need_gx):
     """Weight gradient of a spectral layer in the stage-by-stage backward pass, from the truncated spectra xt (input) and gO (output
     gradient; in `gslot` of the layer's stack when that took it).  -> (gX or None, gw1, gw2 as autograd should receive them): the
@@ -151,18 +172,19 @@ def _stage_wgrad(stack, gslot, xt, gO, w1, w2, leaves, both_gw, need_gx):
     return gX, gw1, gw2
 
 
-def _spectral_backward(gs, xt, w1, w2, H, W, need_gx, need_gw, both_gw, leaves, stack, join=None, addend=None):
+def _spectral_backward(gs, xt, w1, w2, H, W, need_gx, need_gw, both_gw, leaves, stack, join=None, addend=None, k1=None):
     """Backward of the spectral branch: -> (gx or None, gw1, gw2 as autograd should receive them, whether the layer's stack took the call).
     leaves = (weights1, weights2) as the caller passed them (in-place gradient targets); stack = the forward pass's _StackSlot
     or None; join: GradJoin whose deferred spectra are merged into this layer's before the inverse transform; addend: _fused_addend(...)
-    of the point-wise branch's contribution to gx (float32 only) - the call then runs stage by stage."""
+    of the point-wise branch's contribution to gx (float32 only) - the call then runs stage by stage; k1(out): the caller's form of the
+    forward transform of gs (the one that also resamples gs), which also makes the call run stage by stage."""
     B, Co = gs.shape[:2]
     Ci, _, m1, m2 = w1.shape[:4]
     gslot = _stack_grad_slot(stack, Co) if (stack is not None and need_gw) else None
     merging = join is not None and need_gx and bool(join.spectra)
     if addend is not None and not need_gx:
         raise RuntimeError("uno_amd: an addend for the input gradient needs the input gradient")
-    if gslot is None and not merging and addend is None and not (need_gx and need_gw and w1.dtype == torch.complex64):
+    if gslot is None and not merging and addend is None and k1 is None and not (need_gx and need_gw and w1.dtype == torch.complex64):
         tg = _grad_targets(leaves) if (need_gw and both_gw) else None
         if need_gw:
             _note_use(leaves[0])
@@ -173,7 +195,7 @@ def _spectral_backward(gs, xt, w1, w2, H, W, need_gx, need_gw, both_gw, leaves, 
         return gx, gw1, gw2, False
     # stage by stage: the gradient spectrum goes to its slot of the layer's stack and / or the deferred gradient spectra of x's
     # other consumer are added to this layer's before ONE inverse transform
-    gO = _native.dft2d_forward(gs, m1, m2, 1.0, True, True, out=gslot)
+    gO = _native.dft2d_forward(gs, m1, m2, 1.0, True, True, out=gslot) if k1 is None else k1(gslot)
     gX, gw1, gw2 = _stage_wgrad(stack, gslot, xt, gO, w1, w2, leaves, both_gw, need_gx) if need_gw else (None, None, None)
     gx = None
     if need_gx:
@@ -225,11 +247,19 @@ class _OperatorBlock2dFn(torch.autograd.Function):
             _native.dft2d_forward(x, m1, m2, 1.0 / (H * W), out=xt, channel_offset=0)
             O = _native.mode_mix(xt.view(B, Ci, 2, m1 * m2), [w1, w2], 0)
             s = _native.dft2d_inverse(O.view(B, Co, 2 * m1, m2), Ho, Wo, 1.0, True, True, addend=fused)
+        elif mix_last and not same and not half_weights and (rs := _fused_resample(x, w1.shape[2], w1.shape[3], Ho, Wo, False)) is not None:
+            # down-sampling block: the forward transform writes the resampled input of the 1x1 convolution from the same read of x
+            m1, m2 = w1.shape[2], w1.shape[3]
+            xt = _xt_dest(ctx.stack, B, Ci, m1, m2, x.device)
+            _, pre_act = _native.dft2d_forward_resample(x, m1, m2, Ho, Wo, rs, 1.0 / (H * W), out=xt, channel_offset=0)
+            O = _native.mode_mix(xt.view(B, Ci, 2, m1 * m2), [w1, w2], 0)
+            s = _native.dft2d_inverse(O.view(B, Co, 2 * m1, m2), Ho, Wo, 1.0, True, True)
         else:
             pre_act = None
             if mix_last and not same:
-                # the resampling kernel (K7) runs right BEFORE the forward transform (K1) that reads the same tensor: the two walk the
-                # images in opposite order (launch alternation), so what K7 read last is still cached when K1 starts
+                # (where the fused transform above does not apply) the resampling kernel (K7) runs right BEFORE the forward transform (K1)
+                # that reads the same tensor: the two walk the images in opposite order (launch alternation), so what K7 read last is
+                # still cached when K1 starts
                 pre_act = resample_forward(x, Ho, Wo)
             s, xt = _native.spectral_conv2d_forward(x, w1, w2, Ho, Wo, xt_out=_xt_slot(ctx.stack))
         out = s
@@ -282,14 +312,25 @@ class _OperatorBlock2dFn(torch.autograd.Function):
         lw1, lw2, lcw, lcb = ctx.leaves
         # down-sampling block (forward: act = R x; s += Wm act): the point-wise part of gx is the ADJOINT resampling of Wm^T gs, an
         # up-sampling - it joins the spectral part inside the inverse transform (one pass over gx) where the fused kernel applies
-        g_act = addend = g_t = None
+        g_act = addend = g_t = k1 = None
         if not mix_last:
-            g_t = resample_adjoint(gs, H, W).view(B, Co, -1)        # right before the K1 that reads gs as well (see forward)
+            rs = _fused_resample(gs, w1.shape[2], w1.shape[3], H, W, True) if w1.dtype == torch.complex64 else None
+            if rs is None:
+                g_t = resample_adjoint(gs, H, W).view(B, Co, -1)        # right before the K1 that reads gs as well (see forward)
+            else:
+                # up-sampling block: the transform of gs writes its adjoint resampling from the same read (g_t: taken from `both` below)
+                both = []
+
+                def k1(out):
+                    both.extend(_native.dft2d_forward_resample(gs, w1.shape[2], w1.shape[3], H, W, rs, 1.0, True, True, out=out))
+                    return both[0]
         if mix_last and not same and need_gx and gs.dtype == torch.float32:
             g_act = _native.channel_mix(gs.view(B, Co, -1), cwm, None, transpose_w=True).view(B, Ci, Ho, Wo)
             addend = _fused_addend(g_act, H, W, w1.shape[2], w1.shape[3], True)
         gx, gw1, gw2, stacked = _spectral_backward(gs, xt, w1, w2, H, W, need_gx, need_gw, ctx.needs_input_grad[1] and ctx.needs_input_grad[2],
-                                                   (lw1, lw2), ctx.stack, join, addend)
+                                                   (lw1, lw2), ctx.stack, join, addend, k1)
+        if k1 is not None:
+            g_t = both[1].view(B, Co, -1)
         pstack = ctx.stack if stacked else None         # the 1x1 convolution's weight gradient follows the spectral layer's stack
         gcw = gcb = None
         # x is the activation of a fused-GELU block (join.pre): the gradient this block returns must be multiplied by gelu'(pre).
@@ -380,9 +421,15 @@ class _OperatorBlock2dCatFn(torch.autograd.Function):
         lw1, lw2, lcw, lcb = ctx.leaves
         both_gw = ctx.needs_input_grad[2] and ctx.needs_input_grad[3]
         gslot = _stack_grad_slot(ctx.stack, Co) if (ctx.stack is not None and need_gw) else None
-        # gradient at the 1x1 convolution's output; the resampling runs right before the K1 that reads gs as well (_OperatorBlock2dFn.forward)
-        g_src = gs.view(B, Co, -1) if mix_last else resample_adjoint(gs, H, W).view(B, Co, -1)
-        gO = _native.dft2d_forward(gs, m1, m2, 1.0, True, True, out=gslot)             # c (.) keep (.) DFT_trunc(gs)
+        # gradient at the 1x1 convolution's output and the gradient spectrum: from one read of gs where the fused transform applies, else K7
+        # right before the K1 that reads gs as well (_OperatorBlock2dFn.forward)
+        rs = _fused_resample(gs, m1, m2, H, W, True) if (not mix_last and w1.dtype == torch.complex64) else None
+        if rs is not None:
+            gO, g_src = _native.dft2d_forward_resample(gs, m1, m2, H, W, rs, 1.0, True, True, out=gslot)      # c (.) keep (.) DFT_trunc(gs), R^T gs
+            g_src = g_src.view(B, Co, -1)
+        else:
+            g_src = gs.view(B, Co, -1) if mix_last else resample_adjoint(gs, H, W).view(B, Co, -1)
+            gO = _native.dft2d_forward(gs, m1, m2, 1.0, True, True, out=gslot)             # c (.) keep (.) DFT_trunc(gs)
         gXp, gw1, gw2 = _stage_wgrad(ctx.stack, gslot, xt, gO, w1, w2, (lw1, lw2), both_gw, need1 or need2) if need_gw else (None, None, None)
         gx1 = gx2 = None
         defer = ctx.defer if (need2 and ctx.defer is not None and ctx.defer.owner) else None    # owner's backward still to come

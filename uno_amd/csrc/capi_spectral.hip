@@ -217,6 +217,49 @@ int uno_dft2d_inverse_add(const float* spec, float* images, int n_img, int H, in
     return launch_dft2d_inv_add(p, (hipStream_t)stream);
 }
 
+// K1 + down-sampled image (dft2d_fwd_fd_kernel.h): where the form applies
+static void fwd_resample_shape(Dft2dParams& p, int n_img, int H, int W, int m1, int m2, int Ho, int Wo, int KW) {
+    p.n_img = n_img; p.H = H; p.W = W; p.m1 = m1; p.m2 = m2;
+    p.fd_Ho = Ho; p.fd_Wo = Wo; p.fd_KW = KW;
+}
+
+int uno_dft2d_forward_resample_applies(int n_img, int H, int W, int m1, int m2, int Ho, int Wo, int KW) {
+    if (n_img < 1 || H < 1 || W < 1 || m1 < 1 || m2 < 1 || Ho < 1 || Wo < 1 || KW < 1 || m1 > H || m2 > W / 2 + 1 || m1 > 40 || m2 > 48) return 0;
+    Dft2dParams p;
+    fwd_resample_shape(p, n_img, H, W, m1, m2, Ho, Wo, KW);
+    return dft2d_fwd_fd_applies(p) ? 1 : 0;
+}
+
+int uno_dft2d_forward_resample(const float* images, float* spec, int n_img, int H, int W, int m1, int m2, float scale, int hermitian_cols,
+                               int mask_overlap, int group, int stride, int offset, float* resampled, int Ho, int Wo, const int* col_start,
+                               const float* col_wt, int KW, const int* row_tiles, const float* row_op, void* stream) {
+    const char* who = "uno_dft2d_forward_resample";
+    if (n_img < 0) { set_error("%s: negative image count", who); return -1; }
+    if (n_img > 0 && (!images || !spec || !resampled || !col_start || !col_wt || !row_tiles || !row_op)) { set_error("%s: null pointer", who); return -1; }
+    if (int rc = check_modes2d(who, H, W, H, W, m1, m2)) return rc;
+    if (Ho < 1 || Wo < 1 || KW < 1) { set_error("%s: bad output grid %dx%d or band (%d taps)", who, Ho, Wo, KW); return -1; }
+    if (n_img == 0) return 0;
+    if (group <= 0) { group = n_img; stride = 0; offset = 0; }          // plain layout: spectrum i of image i
+    else if (offset < 0 || stride < offset + group || n_img % group) {
+        set_error("%s: bad spectrum grouping (group %d, stride %d, offset %d, images %d)", who, group, stride, offset, n_img);
+        return -1;
+    }
+    if (!uno_dft2d_forward_resample_applies(n_img, H, W, m1, m2, Ho, Wo, KW)) {
+        set_error("%s: the fused form does not apply to %d images of %dx%d -> %dx%d, modes (%d, %d), %d taps (query uno_dft2d_forward_resample_applies)",
+                  who, n_img, H, W, Ho, Wo, m1, m2, KW);
+        return -3;
+    }
+    Dft2dParams p;
+    fwd_resample_shape(p, n_img, H, W, m1, m2, Ho, Wo, KW);
+    p.in = images; p.out = spec; p.scale = scale; p.herm = hermitian_cols ? 1 : 0; p.mask = mask_overlap ? 1 : 0;
+    p.sp_group = group; p.sp_stride = stride; p.sp_offset = offset;
+    p.twH = twiddle_table(H);
+    p.twW = twiddle_table(W);
+    if (!p.twH || !p.twW) return -6;
+    p.fd_out = resampled; p.fd_startW = col_start; p.fd_wtW = col_wt; p.fd_tiles = row_tiles; p.fd_rowop = row_op;
+    return launch_dft2d_fwd_fd(p, (hipStream_t)stream);
+}
+
 int uno_dft2d_forward_bf16(const void* images, float* spec, int n_img, int H, int W, int m1, int m2, float scale,
                            int hermitian_cols, int mask_overlap, void* stream) {
     return dft2d(false, static_cast<const float*>(images), spec, n_img, H, W, m1, m2, scale, hermitian_cols, mask_overlap,

@@ -223,11 +223,14 @@ static bool fwd_ft_geometry(const Dft2dParams& p, int NT, int MT, int R4, FwdFtG
     return fwd_tile_geometry(p, NTF, R4, FwdTileForm{4, FT_LDS_BUDGET, 3, fwd_ft_lds_bytes}, out);
 }
 
+// the sweep direction of one launch of a full-tile form (this kernel and dft2d_fwd_fd_kernel.h, which shares its stage A and its counter)
+static int fwd_ft_sweep() { return next_sweep_reversed(SWEEP_K1); }
+
 template <int NT, int MT, int R4>
 static int launch_fwd_ft(const Dft2dParams& p, const FwdFtGeometry& g, hipStream_t s) {
     char name[64];
     snprintf(name, sizeof(name), "uno::dft2d_fwd_ft_kernel<%d, %d, %d>", NT, MT, R4);
-    return launch_fwd_tile<dft2d_fwd_ft_kernel<NT, MT, R4>>(name, p, g, next_sweep_reversed(SWEEP_K1), s);
+    return launch_fwd_tile<dft2d_fwd_ft_kernel<NT, MT, R4>>(name, p, g, fwd_ft_sweep(), s);
 }
 
 }  // namespace uno

@@ -197,6 +197,16 @@ struct Dft2dParams {
     const float* add_rowop = nullptr;
     const int* add_v0 = nullptr;
     const float* add_colop = nullptr;
+    // K1-FD (dft2d_fwd_fd_kernel.h): the forward transform also writes fd_out (n_img, fd_Ho, fd_Wo) = A . image . B^T.  B: K7's band table
+    // (first source column and fd_KW taps per output column); A: host-built per 16-row tile of the IMAGE (uno_amd/resample.py
+    // fused_resample_tables): fd_tiles [tile][4] = first carried output row, rows the tile completes, 52-bit mask of the non-zero 4-row
+    // pieces; fd_rowop [tile][13][16] dense weights of the carried rows
+    float* fd_out = nullptr;
+    int fd_Ho = 0, fd_Wo = 0, fd_KW = 0;
+    const int* fd_startW = nullptr;
+    const float* fd_wtW = nullptr;
+    const int* fd_tiles = nullptr;
+    const float* fd_rowop = nullptr;
 };
 
 __device__ __forceinline__ size_t spectrum_index(const Dft2dParams& p, int img) {
@@ -296,6 +306,8 @@ int launch_dft2d_fwd(const Dft2dParams& p, hipStream_t s);
 int launch_dft2d_inv(const Dft2dParams& p, hipStream_t s);
 bool dft2d_inv_add_applies(const Dft2dParams& p);       // dft2d_inv_add.hip: K3 + up-sampled addend (p.add_* set)
 int launch_dft2d_inv_add(const Dft2dParams& p, hipStream_t s);
+bool dft2d_fwd_fd_applies(const Dft2dParams& p);        // dft2d_fwd_fd.hip: K1 + down-sampled image (p.fd_Ho, fd_Wo, fd_KW set)
+int launch_dft2d_fwd_fd(const Dft2dParams& p, hipStream_t s);
 bool dft2d_fwd_plane_applies(const Dft2dParams& p);      // dft2d_plane.hip: many small images
 bool dft2d_inv_plane_applies(const Dft2dParams& p);
 bool dft2d_b16_applies(const Dft2dParams& p);           // dft2d_b16.hip: bfloat16 images, row stage on the bf16 MFMA

@@ -160,6 +160,57 @@ def upsample_add_tables(Hs: int, Ws: int, H: int, W: int, device_str: str, adjoi
     return tuple(_native.table_to_device(t, dev) for t in ops)
 
 
+FD_NC = 13         # output rows the fused `forward transform + resampling` kernel carries across tiles (csrc/dft2d_fwd_fd_kernel.h)
+FD_KW = 9          # ... and the widest column band it takes
+
+
+def _fd_row_tiles(A: torch.Tensor):
+    """Row operator A (Ho, H) per 16-row tile of the INPUT, for a kernel that walks the tiles in order and carries the output rows a
+    tile contributes to: (row_tiles [nrt][4] int32, row_op [nrt][FD_NC][16] float32) as include/uno_spectral.h describes them, or None
+    when more than FD_NC rows are open at once."""
+    Ho, H = A.shape
+    nrt = (H + TILE_ROWS - 1) // TILE_ROWS
+    nz = A != 0
+    last = torch.where(nz.any(1), H - 1 - nz.flip(1).float().argmax(1), torch.zeros(Ho, dtype=torch.long))
+    done = torch.cummax(last, 0).values // TILE_ROWS        # the tile after which output row i is complete (rows leave in order)
+    pad = torch.zeros(Ho + FD_NC, TILE_ROWS * nrt, dtype=torch.float32)
+    pad[:Ho, :H] = A
+    tiles = torch.zeros(nrt, 4, dtype=torch.int64)
+    op = torch.zeros(nrt, FD_NC, TILE_ROWS, dtype=torch.float32)
+    for rt in range(nrt):
+        i0 = int((done < rt).sum())
+        cols = slice(TILE_ROWS * rt, TILE_ROWS * (rt + 1))
+        if bool((pad[i0 + FD_NC:, cols] != 0).any()):
+            return None
+        op[rt] = pad[i0:i0 + FD_NC, cols]
+        ncomp = int((done == rt).sum()) if rt < nrt - 1 else Ho - i0
+        if ncomp > FD_NC:
+            return None
+        pieces = (op[rt].view(FD_NC, 4, 4) != 0).any(2).flatten()
+        mask = sum(1 << b for b in range(4 * FD_NC) if bool(pieces[b]))
+        lo, hi = mask & 0xffffffff, mask >> 32
+        tiles[rt] = torch.tensor([i0, ncomp, lo - (1 << 32) if lo >= 1 << 31 else lo, hi])
+    return tiles.to(torch.int32).contiguous(), op.contiguous()
+
+
+@functools.lru_cache(maxsize=None)
+def fused_resample_tables(H: int, W: int, Ho: int, Wo: int, device_str: str, adjoint: bool = False, mode: str = "bicubic_aa"):
+    """Device tables (col_start, col_wt, row_tiles, row_op) of _native.dft2d_forward_resample for an (H, W) image resampled to (Ho, Wo), or
+    None where the kernel's limits do not hold.  adjoint=False: resample_forward (H, W) -> (Ho, Wo); adjoint=True: resample_adjoint of an
+    (H, W) gradient for an (Ho, Wo) INPUT grid (the operators are the transposes of the (Ho, Wo) -> (H, W) matrices)."""
+    if adjoint:
+        A, (bw, _) = _matrix(Ho, H, mode).t().contiguous(), _tables(Wo, W, device_str, mode)[1]
+    else:
+        A, (bw, _) = _matrix(H, Ho, mode), _tables(W, Wo, device_str, mode)[0]
+    if bw[1].shape[1] > FD_KW:
+        return None
+    rows = _fd_row_tiles(A)
+    if rows is None:
+        return None
+    dev = torch.device(device_str)
+    return (bw[0], bw[1], *(_native.table_to_device(t, dev) for t in rows))
+
+
 def resample_forward(x: torch.Tensor, Ho: int, Wo: int, out: torch.Tensor | None = None) -> torch.Tensor:
     """R_h x R_w^T on the device (no autograd); with `out`, accumulates into it."""
     H, W = x.shape[-2:]
