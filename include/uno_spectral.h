@@ -197,12 +197,21 @@ int uno_dft2d_inverse_add(const float* spec, float* images, int n_img, int H, in
  *                                   carried set), bits 0..31 and 32..51 of the mask whose bit 4 c + q is set where
  *                                   row_op[tile][c][4 q .. 4 q + 3] holds a non-zero weight
  *   row_op    [ceil(H/16)][13][16]  entry (tile, c, r) = A[i0 + c][16 tile + r], zero outside the matrix
- * uno_dft2d_forward_resample_applies: 1 where the fused kernel exists (float32, rows of 416..447 elements, Wo <= 256, KW <= 9,
- * (modes1, modes2) in 17..24 x 17..20 or 1..8 x 1..8, the tiles fit the LDS), else 0 - the caller then runs the two calls. */
+ * uno_dft2d_forward_resample_applies: 1 where the fused kernel exists (float32; rows of 416..447 elements with Wo <= 256, or rows of
+ * 192..223 elements with Wo <= 128; KW <= 9, (modes1, modes2) in 17..24 x 17..20 or 1..8 x 1..8, the tiles fit the LDS), else 0 - the
+ * caller then runs the two calls. */
 int uno_dft2d_forward_resample_applies(int n_img, int H, int W, int m1, int m2, int Ho, int Wo, int KW);
 int uno_dft2d_forward_resample(const float* images, float* spec, int n_img, int H, int W, int m1, int m2, float scale, int hermitian_cols,
                                int mask_overlap, int group, int stride, int offset, float* resampled, int Ho, int Wo, const int* col_start,
                                const float* col_wt, int KW, const int* row_tiles, const float* row_op, void* stream);
+
+/* (added under ABI 14: a new entry point only)  The truncation to (m1, m2) modes of spectra truncated to (M1, M2) modes, m1 <= M1 and
+ * m2 <= M2: dst rows 0 .. m1 - 1 = src rows 0 .. m1 - 1 (lo corner), dst rows m1 .. 2 m1 - 1 = the LAST m1 rows of src (hi corner),
+ * columns 0 .. m2 - 1.  A tensor that two spectral layers transform on one grid with the same scale and flags (reference
+ * darcy_flow_uno2d.py:110 and :121 both take x_c0) is transformed once at the larger mode counts; the other layer's spectrum is this
+ * copy.  src (.., 2 M1, M2) and dst (.., 2 m1, m2) c64 in uno_dft2d_forward_grouped's layout each (group <= 0: plain); dst != src. */
+int uno_spectrum_crop(const float* src, float* dst, int n_img, int M1, int M2, int m1, int m2, int src_group, int src_stride, int src_offset,
+                      int dst_group, int dst_stride, int dst_offset, void* stream);
 
 /* The two transforms with bfloat16 images (the stages of uno_spectral_conv2d_*_bf16); spectra are c64 as above. */
 int uno_dft2d_forward_bf16(const void* images, float* spec, int n_img, int H, int W, int m1, int m2,

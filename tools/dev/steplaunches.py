@@ -1,11 +1,17 @@
 """Every library launch of ONE Darcy training step in issue order: kernel, us, algorithmic MB, GB/s (library event pairs; averaged
-over a few steps).  python tools/dev/steplaunches.py [lib.so|-]"""
+over a few steps).  python tools/dev/steplaunches.py [lib.so|-] [switch=0|1 ...]   (switch: a module-level A/B switch of uno_amd.block2d,
+e.g. SHARE_FORWARD_SPECTRUM=0 FUSE_FORWARD_RESAMPLE=0)"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
 from uno_amd import _native
 if len(sys.argv) > 1 and sys.argv[1] != "-":
     _native.LIB_PATH = os.path.abspath(sys.argv[1])
+from uno_amd import block2d
+for arg in sys.argv[2:]:
+    name, value = arg.split("=")
+    assert hasattr(block2d, name), name
+    setattr(block2d, name, bool(int(value)))
 from uno_amd.harness import DarcyTrainer, UNO_9, synthetic_darcy_batch
 dev = torch.device("cuda:0")
 torch.manual_seed(0)

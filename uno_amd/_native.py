@@ -50,6 +50,7 @@ _SIGNATURES = {
     "uno_dft2d_inverse_add": (C.c_int, [_fp, _fp] + [_i] * 5 + [C.c_float, _i, _i, _fp, _i, _i, _fp, _fp, _fp, _fp, _fp]),
     "uno_dft2d_forward_grouped": (C.c_int, [_fp, _fp] + [_i] * 5 + [C.c_float] + [_i] * 5 + [_fp]),
     "uno_dft2d_inverse_grouped": (C.c_int, [_fp, _fp] + [_i] * 5 + [C.c_float] + [_i] * 5 + [_fp]),
+    "uno_spectrum_crop": (C.c_int, [_fp, _fp] + [_i] * 11 + [_fp]),
     "uno_mode_mix": (C.c_int, [_fp, C.POINTER(_fp), _fp] + [_i] * 6 + [_fp]),
     "uno_mode_wgrad": (C.c_int, [_fp, _fp, C.POINTER(_fp)] + [_i] * 5 + [_fp]),
     "uno_mode_backward": (C.c_int, [_fp, _fp, C.POINTER(_fp), _fp, C.POINTER(_fp)] + [_i] * 6 + [_fp]),
@@ -399,6 +400,39 @@ def dft2d_forward(images, m1, m2, scale=1.0, hermitian_cols=False, mask_overlap=
             rc = fn(_ptr(images), _ptr(out), n, H, W, m1, m2, float(scale), int(hermitian_cols),
                     int(mask_overlap), images.shape[1], out.shape[1], int(channel_offset), _stream(images))
     _check(rc, "uno_dft2d_forward_grouped")
+    return out
+
+
+def spectrum_crop(src, m1, m2, out=None, channels=None, channel_offset=0, out_channel_offset=0):
+    """The truncation to (m1, m2) modes of spectra (..., 2*M1, M2) c64 truncated to (M1, M2) >= (m1, m2): a copy of the corner blocks
+    (uno_spectrum_crop) -> (..., 2*m1, m2).  With `channels` = C1 and src (B, Ctot, 2*M1, M2) only the channels
+    [channel_offset, channel_offset + C1) are taken -> (B, C1, 2*m1, m2); with `out` (B, Cout, 2*m1, m2) they go to its channels
+    [out_channel_offset, out_channel_offset + C1)."""
+    _require(src, torch.complex64, "src")
+    *lead, R2, M2 = src.shape
+    M1 = R2 // 2
+    if R2 != 2 * M1 or not (1 <= m1 <= M1 and 1 <= m2 <= M2):
+        raise RuntimeError(f"uno_amd: spectrum_crop of {tuple(src.shape)} to modes ({m1}, {m2}): need an even row count and 1 <= modes <= the source's")
+    sg = ss = so = dg = ds = do = 0
+    if channels is not None or out is not None:
+        if src.dim() != 4:
+            raise RuntimeError("uno_amd: spectrum_crop of a channel range needs src (B, Ctot, 2*M1, M2)")
+        C1 = src.shape[1] - channel_offset if channels is None else int(channels)
+        if channel_offset < 0 or C1 < 1 or channel_offset + C1 > src.shape[1]:
+            raise RuntimeError("uno_amd: src must hold the requested channel range")
+        lead = [src.shape[0], C1]
+        sg, ss, so = C1, src.shape[1], int(channel_offset)
+    if out is None:
+        out = torch.empty((*lead, 2 * m1, m2), dtype=torch.complex64, device=src.device)
+    else:
+        _require(out, torch.complex64, "out")
+        if out.dim() != 4 or out.shape[0] != lead[0] or tuple(out.shape[2:]) != (2 * m1, m2) or out_channel_offset < 0 \
+                or out_channel_offset + lead[1] > out.shape[1] or out.device != src.device:
+            raise RuntimeError("uno_amd: out must be (B, Cout, 2*m1, m2) with room for the channels at out_channel_offset")
+        dg, ds, do = lead[1], out.shape[1], int(out_channel_offset)
+    with torch.cuda.device(src.device):
+        rc = lib().uno_spectrum_crop(_ptr(src), _ptr(out), _count(lead), M1, M2, int(m1), int(m2), sg, ss, so, dg, ds, do, _stream(src))
+    _check(rc, "uno_spectrum_crop")
     return out
 
 

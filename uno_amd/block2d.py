@@ -152,6 +152,78 @@ def _fused_resample(x, m1, m2, Ho, Wo, adjoint):
     return tabs
 
 
+# A tensor that TWO spectral layers transform on the same grid (the Darcy model's c0: conv1 at modes 8, then conv5 at modes 18 as the second
+# source of its two-source form): the corner blocks of the smaller truncation are a subset of the larger one's, so the first consumer
+# transforms the tensor ONCE at the larger mode counts, straight into the later consumer's spectrum, and copies its own corner blocks out of
+# it (uno_spectrum_crop); the later consumer skips its transform of that source (SpectrumShare).  False: each layer transforms for itself (A/B).
+SHARE_FORWARD_SPECTRUM = True
+
+
+class SpectrumShare:
+    """One forward transform for a tensor with TWO spectral consumers on the same grid - the forward-pass counterpart of GradJoin, which
+    transforms the sum of the two gradient spectra once.
+
+    Made per forward pass for the LATER consumer - a two-source block that takes the tensor as its second source at channel
+    `channel_offset` of its `channels` input channels, with `modes` = (m1, m2) - and handed to both: the FIRST consumer
+    (`OperatorBlock_2D(x, share=)`) transforms x at the larger modes into a fresh (B, channels, 2 m1, m2) tensor - the later consumer's
+    truncated input spectrum - and crops its own spectrum from it; the later one (`forward_cat(share=)`) takes that tensor, transforms
+    its first source into the other channels and skips the second.  Each layer keeps its own spectrum for its backward pass.
+    Applies to float32 device tensors and complex64 weights, where the later consumer's modes are no fewer than the first one's in both
+    axes and fit the grid; anywhere else - and with SHARE_FORWARD_SPECTRUM off - nothing is left here and both layers run as before."""
+
+    def __init__(self, modes, channels, channel_offset):
+        self.modes = (int(modes[0]), int(modes[1]))
+        self.channels, self.offset = int(channels), int(channel_offset)
+        self.spec = self.src = None
+
+    @classmethod
+    def for_block(cls, block, channel_offset):
+        """for the two-source OperatorBlock_2D `block` whose second source starts at input channel `channel_offset`"""
+        return cls((block.conv.modes1, block.conv.modes2), block.conv.in_channels, channel_offset)
+
+    def reset(self):
+        self.spec = self.src = None
+
+    def dest(self, x, m1, m2):
+        """First consumer, x (B, C, H, W) plain: (spectrum tensor, M1, M2, channel offset) to transform x into, or None"""
+        self.reset()
+        M1, M2 = self.modes
+        H, W = x.shape[-2], x.shape[-1]
+        if not SHARE_FORWARD_SPECTRUM or x.dtype != torch.float32 or x.dim() != 4 or not x.is_cuda or m1 > M1 or m2 > M2 \
+                or M1 > H or M2 > W // 2 + 1 or self.offset < 0 or self.offset + x.shape[1] != self.channels:
+            return None
+        self.spec = torch.empty((x.shape[0], self.channels, 2 * M1, M2), dtype=torch.complex64, device=x.device)
+        self.src = (x, x._version)              # (holding x keeps its storage from being handed to another tensor meanwhile)
+        return self.spec, M1, M2, self.offset
+
+    def take(self, x2, C1, Ci, m1, m2):
+        """Later consumer: its (B, Ci, 2 m1, m2) spectrum with x2's part at channels [C1, Ci) in place, or None (it transforms x2 itself)"""
+        spec, src = self.spec, self.src
+        self.reset()
+        if spec is None or (m1, m2) != self.modes or Ci != self.channels or C1 != self.offset:
+            return None
+        x, version = src
+        if x2.data_ptr() != x.data_ptr() or x2.shape != x.shape or x2.stride() != x.stride() or x2.dtype != x.dtype or x2._version != version:
+            return None
+        return spec
+
+
+def _source_spectrum(x, xt, m1, m2, dest, rs=None, Ho=0, Wo=0):
+    """K1 of a block's plain source x (B, Ci, H, W) into xt (B, Ci, 2 m1, m2), rfft2(norm="forward") truncated; rs (_fused_resample's
+    tables): the form that also resamples x to (Ho, Wo) -> that tensor.  dest = SpectrumShare.dest(...): x is transformed at the later
+    consumer's modes into its spectrum, and xt is the crop of that (rs then belongs to those modes)."""
+    H, W = x.shape[-2], x.shape[-1]
+    tgt, k1, k2, off = (xt, m1, m2, 0) if dest is None else dest
+    res = None
+    if rs is None:
+        _native.dft2d_forward(x, k1, k2, 1.0 / (H * W), out=tgt, channel_offset=off)
+    else:
+        _, res = _native.dft2d_forward_resample(x, k1, k2, Ho, Wo, rs, 1.0 / (H * W), out=tgt, channel_offset=off)
+    if dest is not None:
+        _native.spectrum_crop(tgt, m1, m2, out=xt, channels=x.shape[1], channel_offset=off)
+    return res
+
+
 def _stage_wgrad(stack, gslot, xt, gO, w1, w2, leaves, both_gw, need_gx):
     """Weight gradient of a spectral layer in the stage-by-stage backward pass, from the truncated spectra xt (input) and gO (output
     gradient; in `gslot` of the layer's stack when that took it).  -> (gX or None, gw1, gw2 as autograd should receive them): the
@@ -218,13 +290,14 @@ class _OperatorBlock2dFn(torch.autograd.Function):
     separate element-wise pass."""
 
     @staticmethod
-    def forward(ctx, x, w1, w2, cw, cb, Ho, Wo, half_weights=False, fuse_gelu=False, join=None, out_join=None):
+    def forward(ctx, x, w1, w2, cw, cb, Ho, Wo, half_weights=False, fuse_gelu=False, join=None, out_join=None, share=None):
         """fuse_gelu (blocks with Non_Lin and no normalisation, reference integral_operators.py:282-283): returns gelu(s); where the
         channel mix is the kernel that completes s (no up-sampling) it writes the activation in the same pass.
         join: GradJoin of x - this block is x's FIRST consumer and returns x's complete gradient (see GradJoin).
         out_join (with fuse_gelu): the GradJoin of this block's OUTPUT; the block leaves its pre-activation sum there, and the
         consumer that completes the output's gradient multiplies it by gelu'(pre) in its last accumulating kernel - this block's
-        backward then receives the gradient at the pre-activation sum and runs no GELU-backward pass."""
+        backward then receives the gradient at the pre-activation sum and runs no GELU-backward pass.
+        share: SpectrumShare of x - this block is x's FIRST spectral consumer and transforms x for the later one as well."""
         ctx.leaves = (w1, w2, cw, cb)
         ctx.join = None
         if join is not None:
@@ -236,22 +309,24 @@ class _OperatorBlock2dFn(torch.autograd.Function):
         B, Ci, H, W = x.shape
         Co = cw.shape[0]
         w1, w2, cwm, cb, same, mix_last = _block_prologue(ctx, 1, x, Ci, w1, w2, cw, cb, Ho, Wo, half_weights)
+        m1, m2 = w1.shape[2], w1.shape[3]
+        # x has a later spectral consumer with at least as many modes: K1 runs at ITS modes into its spectrum, xt is cropped from that
+        dest = share.dest(x, m1, m2) if (share is not None and not half_weights and w1.dtype == torch.complex64) else None
+        k1m = (m1, m2) if dest is None else dest[1:3]
         t = fused = None
         if not mix_last and not half_weights and x.dtype == torch.float32:
             # up-sampling block: the 1x1 convolution first, its result joins the inverse transform's (one pass over the output)
             t = _native.channel_mix(x.view(B, Ci, -1), cwm, cb).view(B, Co, H, W)
-            fused = _fused_addend(t, Ho, Wo, w1.shape[2], w1.shape[3], False)
+            fused = _fused_addend(t, Ho, Wo, m1, m2, False)
         if fused is not None:
-            m1, m2 = w1.shape[2], w1.shape[3]
             xt = _xt_dest(ctx.stack, B, Ci, m1, m2, x.device)
-            _native.dft2d_forward(x, m1, m2, 1.0 / (H * W), out=xt, channel_offset=0)
+            _source_spectrum(x, xt, m1, m2, dest)
             O = _native.mode_mix(xt.view(B, Ci, 2, m1 * m2), [w1, w2], 0)
             s = _native.dft2d_inverse(O.view(B, Co, 2 * m1, m2), Ho, Wo, 1.0, True, True, addend=fused)
-        elif mix_last and not same and not half_weights and (rs := _fused_resample(x, w1.shape[2], w1.shape[3], Ho, Wo, False)) is not None:
+        elif mix_last and not same and not half_weights and (rs := _fused_resample(x, *k1m, Ho, Wo, False)) is not None:
             # down-sampling block: the forward transform writes the resampled input of the 1x1 convolution from the same read of x
-            m1, m2 = w1.shape[2], w1.shape[3]
             xt = _xt_dest(ctx.stack, B, Ci, m1, m2, x.device)
-            _, pre_act = _native.dft2d_forward_resample(x, m1, m2, Ho, Wo, rs, 1.0 / (H * W), out=xt, channel_offset=0)
+            pre_act = _source_spectrum(x, xt, m1, m2, dest, rs, Ho, Wo)
             O = _native.mode_mix(xt.view(B, Ci, 2, m1 * m2), [w1, w2], 0)
             s = _native.dft2d_inverse(O.view(B, Co, 2 * m1, m2), Ho, Wo, 1.0, True, True)
         else:
@@ -261,7 +336,13 @@ class _OperatorBlock2dFn(torch.autograd.Function):
                 # that reads the same tensor: the two walk the images in opposite order (launch alternation), so what K7 read last is
                 # still cached when K1 starts
                 pre_act = resample_forward(x, Ho, Wo)
-            s, xt = _native.spectral_conv2d_forward(x, w1, w2, Ho, Wo, xt_out=_xt_slot(ctx.stack))
+            if dest is None:
+                s, xt = _native.spectral_conv2d_forward(x, w1, w2, Ho, Wo, xt_out=_xt_slot(ctx.stack))
+            else:           # the composite's three stages, with the shared transform as the first
+                xt = _xt_dest(ctx.stack, B, Ci, m1, m2, x.device)
+                _source_spectrum(x, xt, m1, m2, dest)
+                O = _native.mode_mix(xt.view(B, Ci, 2, m1 * m2), [w1, w2], 0)
+                s = _native.dft2d_inverse(O.view(B, Co, 2 * m1, m2), Ho, Wo, 1.0, True, True)
         out = s
         if fused is not None:
             act = x
@@ -360,7 +441,7 @@ class _OperatorBlock2dFn(torch.autograd.Function):
                         gx = torch.ops.aten.gelu_backward(gx, xpre)
                     join.dgelu_applied = True
             join.reset()
-        return gx, gw1, gw2, gcw, gcb, None, None, None, None, None, None
+        return gx, gw1, gw2, gcw, gcb, None, None, None, None, None, None, None
 
 
 class _OperatorBlock2dCatFn(torch.autograd.Function):
@@ -371,7 +452,7 @@ class _OperatorBlock2dCatFn(torch.autograd.Function):
     of a joint gradient to copy or accumulate)."""
 
     @staticmethod
-    def forward(ctx, x1, x2, w1, w2, cw, cb, Ho, Wo, half_weights=False, defer=None):
+    def forward(ctx, x1, x2, w1, w2, cw, cb, Ho, Wo, half_weights=False, defer=None, share=None):
         ctx.leaves = (w1, w2, cw, cb)
         ctx.defer = defer if (defer is not None and defer.owner and ctx.needs_input_grad[1]) else None
         x1, x2 = _plain(x1), _plain(x2)
@@ -380,9 +461,15 @@ class _OperatorBlock2dCatFn(torch.autograd.Function):
         Ci, Co, m1, m2 = w1.shape
         w1, w2, cwm, cb, same, mix_last = _block_prologue(ctx, 2, x1, Ci, w1, w2, cw, cb, Ho, Wo, half_weights)
         # spectral branch, stage by stage (the composite entry point takes a single source)
-        xt = _xt_dest(ctx.stack, B, Ci, m1, m2, x1.device)
+        # x2's first consumer may have left this layer's spectrum with x2's channels in place (SpectrumShare): x2 is not transformed again
+        shared = share.take(x2, C1, Ci, m1, m2) if (share is not None and not half_weights and x2.dtype == torch.float32
+                                                    and w1.dtype == torch.complex64) else None
+        xt = shared if (shared is not None and ctx.stack is None) else _xt_dest(ctx.stack, B, Ci, m1, m2, x1.device)
         _native.dft2d_forward(x1, m1, m2, 1.0 / (H * W), out=xt, channel_offset=0)
-        _native.dft2d_forward(x2, m1, m2, 1.0 / (H * W), out=xt, channel_offset=C1)
+        if shared is None:
+            _native.dft2d_forward(x2, m1, m2, 1.0 / (H * W), out=xt, channel_offset=C1)
+        elif shared is not xt:      # the layer's stack keeps its uses' spectra in one tensor: a copy of the truncated spectrum into the slot
+            xt[:, C1:].copy_(shared[:, C1:])
         O = _native.mode_mix(xt.view(B, Ci, 2, m1 * m2), [w1, w2], 0)
         t = fused = None
         if not mix_last and not half_weights and x1.dtype == torch.float32:
@@ -462,7 +549,7 @@ class _OperatorBlock2dCatFn(torch.autograd.Function):
             gcw = None if gcw is None else gcw.view(cw_shape)
         if ctx.defer is not None and gx2 is not None:       # the owner's backward came first after all
             gx2 = ctx.defer.late(gx2)
-        return gx1, gx2, gw1, gw2, gcw, gcb, None, None, None, None
+        return gx1, gx2, gw1, gw2, gcw, gcb, None, None, None, None, None
 
 
 def spectral_conv2d(x, weights1, weights2, dim1, dim2):

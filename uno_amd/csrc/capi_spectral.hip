@@ -260,6 +260,32 @@ int uno_dft2d_forward_resample(const float* images, float* spec, int n_img, int 
     return launch_dft2d_fwd_fd(p, (hipStream_t)stream);
 }
 
+// the truncation to (m1, m2) modes of spectra truncated to (M1, M2): a copy of the corner blocks (spectrum_crop.hip)
+int uno_spectrum_crop(const float* src, float* dst, int n_img, int M1, int M2, int m1, int m2, int src_group, int src_stride, int src_offset,
+                      int dst_group, int dst_stride, int dst_offset, void* stream) {
+    const char* who = "uno_spectrum_crop";
+    if (n_img < 0) { set_error("%s: negative image count", who); return -1; }
+    if (m1 < 1 || m2 < 1 || m1 > M1 || m2 > M2 || (long long)M1 * M2 > 0x7fffffffLL / 4) {
+        set_error("%s: bad mode counts (%d, %d) -> (%d, %d) (need 1 <= m1 <= M1, 1 <= m2 <= M2)", who, M1, M2, m1, m2);
+        return -1;
+    }
+    if (n_img == 0) return 0;
+    if (!src || !dst) { set_error("%s: null pointer", who); return -1; }
+    if (src == dst) { set_error("%s: dst must not alias src", who); return -1; }
+    if (src_group <= 0) { src_group = n_img; src_stride = 0; src_offset = 0; }          // plain layout: spectrum i of image i
+    else if (src_offset < 0 || src_stride < src_offset + src_group || n_img % src_group) {
+        set_error("%s: bad source grouping (group %d, stride %d, offset %d, images %d)", who, src_group, src_stride, src_offset, n_img);
+        return -1;
+    }
+    if (dst_group <= 0) { dst_group = n_img; dst_stride = 0; dst_offset = 0; }
+    else if (dst_offset < 0 || dst_stride < dst_offset + dst_group || n_img % dst_group) {
+        set_error("%s: bad destination grouping (group %d, stride %d, offset %d, images %d)", who, dst_group, dst_stride, dst_offset, n_img);
+        return -1;
+    }
+    return launch_spectrum_crop(src, dst, n_img, M1, M2, m1, m2, src_group, src_stride, src_offset, dst_group, dst_stride, dst_offset,
+                                (hipStream_t)stream);
+}
+
 int uno_dft2d_forward_bf16(const void* images, float* spec, int n_img, int H, int W, int m1, int m2, float scale,
                            int hermitian_cols, int mask_overlap, void* stream) {
     return dft2d(false, static_cast<const float*>(images), spec, n_img, H, W, m1, m2, scale, hermitian_cols, mask_overlap,

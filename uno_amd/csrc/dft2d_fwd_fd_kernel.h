@@ -4,7 +4,7 @@
 // other; the input gradient of an up-sampling block has the same shape.  Here the wave that holds a 16 x W
 // tile of the image in LDS for the row stage of the transform (dft2d_fwd_ft_kernel.h: stage A is that kernel's, expanded in place)
 // applies the separable banded operator of K7 to it before the tile buffer is handed to the next tile's loads:
-//   * column operator, VALU, from the tile in LDS: lane -> output columns 64 e + lane (e < FD_CE), Y[r][e] = sum_t wtW[j][t] x[r][start_j + t]
+//   * column operator, VALU, from the tile in LDS: lane -> output columns 64 e + lane (e < CE, the instantiation's FD_CE or FD_CE2), Y[r][e] = sum_t wtW[j][t] x[r][start_j + t]
 //     for the 16 tile rows (taps in ascending order, as K7's column sweep).  The upper half wave reads one column EARLIER, with its taps
 //     moved up by one register: at 2:1 the start columns of neighbouring outputs are two floats apart, so the two half waves would hit
 //     the same 32 LDS banks - shifted, they take the even and the odd banks.
@@ -25,7 +25,8 @@ namespace uno {
 
 constexpr int FD_NC = 13;               // carried output rows (12 are open at once at 446 -> 223 and its adjoint twin)
 constexpr int FD_KT = 10;               // compiled taps of the column operator, one of them the half-wave shift: KW <= 9
-constexpr int FD_CE = 4;                // output columns per lane: Wo <= 256
+constexpr int FD_CE = 4;                // output columns per lane at the 446^2 level: Wo <= 256
+constexpr int FD_CE2 = 2;               // ... and at the 223^2 level: Wo <= 128, the carried rows, the column sums and the taps take half the registers
 constexpr int FD_WR = (FD_NC * 16 + 63) / 64;   // registers per lane that hold a tile's [FD_NC][16] piece of the row operator
 // development builds (tools/dev/mkvariant.py ... -DUNO_FD_KO=mask): knock-outs for timing - 1: no column operator, 2: no row operator,
 // 4: no stores of the resampled rows; 0 in production
@@ -33,9 +34,18 @@ constexpr int FD_WR = (FD_NC * 16 + 63) / 64;   // registers per lane that hold 
 #define UNO_FD_KO 0
 #endif
 constexpr int FD_MINW = 416, FD_MAXW = 447;     // admitted row lengths (the 446^2 level; four 16 x W tiles + the tables fill the LDS)
+// ... and the second window, the 223^2 level (CE = FD_CE2): a workgroup's four 16 x W tiles (14.4 KB each at W = 223) and its table set
+// (18.6 KB for <2, 3, 1>) take 80.5 KB at 223 x 223, so TWO workgroups share a CU's 160 KB - two waves per SIMD, which is what lets one
+// wave's column operator run under the other's MFMA stages.  The upper end is where that stops: at 225 the twiddle tables grow by a
+// seventh 16-pair chunk (21.1 KB) and two workgroups of four no longer fit (224 itself puts the 16 rows of an operand read on four LDS
+// banks).  The lower end is the one of K3-A's window at this level (dft2d_inv_add_kernel.h); the tail tables (FWD_TAILMAX k-steps: at most
+// 15 pairs + w = 0 + the Nyquist column) hold for every row length.
+constexpr int FD_MINW2 = 192, FD_MAXW2 = 223;
+constexpr size_t FD_LDS_HALF = (160 * 1024) / 2 - 1024;     // per workgroup where two share a CU
 
-template <int NT, int MT, int R4>
-__global__ __launch_bounds__(256) void dft2d_fwd_fd_kernel(Dft2dParams p) {
+// CE: output columns per lane (FD_CE | FD_CE2); the FD_CE2 instantiations are compiled for two waves per SIMD (<= 256 registers)
+template <int NT, int MT, int R4, int CE = FD_CE>
+__global__ __launch_bounds__(256, CE == FD_CE2 ? 2 : 1) void dft2d_fwd_fd_kernel(Dft2dParams p) {
     constexpr int NTF = R4 > 0 ? NT - 1 : NT;       // full 16-mode streams
     constexpr int NQ = R4 > 0 ? R4 : 1;
     constexpr int NTFA = NTF > 0 ? NTF : 1;
@@ -88,14 +98,14 @@ __global__ __launch_bounds__(256) void dft2d_fwd_fd_kernel(Dft2dParams p) {
     for (int e = tid; e < FWD_TAILMAX * 64; e += nthreads) { UNO_FWD_PUT_TAIL_COLUMNS(e); }
     UNO_FWD_BUILD_OPERAND_TABLES();
 
-    // ---- column operator of this lane's FD_CE output columns: first source column sc (moved so that all FD_KT reads stay inside the
+    // ---- column operator of this lane's CE output columns: first source column sc (moved so that all FD_KT reads stay inside the
     // row, and one to the left in the upper half wave) and the taps, moved up by as much; everything outside the band is an exact zero
-    int sc[FD_CE];
-    float wc[FD_CE][FD_KT];
+    int sc[CE];
+    float wc[CE][FD_KT];
     {
         const int KW = p.fd_KW;
 #pragma unroll
-        for (int e = 0; e < FD_CE; ++e) {
+        for (int e = 0; e < CE; ++e) {
             const int j = min(64 * e + lane, Wo - 1);
             const int s = p.fd_startW[j];
             sc[e] = max(min(s - (lane >> 5), W - FD_KT), 0);
@@ -116,11 +126,11 @@ __global__ __launch_bounds__(256) void dft2d_fwd_fd_kernel(Dft2dParams p) {
     const float2* tabF = sTabF + lane;
     const float2* tab4 = sTab4 + 4 * kk + (lane & 3);
 
-    float C[FD_NC][FD_CE];                      // carried output rows ibase(tile) + c, columns 64 e + lane
+    float C[FD_NC][CE];                      // carried output rows ibase(tile) + c, columns 64 e + lane
 #pragma unroll
     for (int c = 0; c < FD_NC; ++c)
 #pragma unroll
-        for (int e = 0; e < FD_CE; ++e) C[c][e] = 0.f;
+        for (int e = 0; e < CE; ++e) C[c][e] = 0.f;
 
     if (active) {
         float* const oimg = p.fd_out + (size_t)image * Ho * Wo;
@@ -134,7 +144,7 @@ __global__ __launch_bounds__(256) void dft2d_fwd_fd_kernel(Dft2dParams p) {
                 if (c < pend_ncomp && (unsigned)(pend_ibase + c) < (unsigned)Ho && !(UNO_FD_KO & 4)) {
                     float* orow = oimg + (size_t)(pend_ibase + c) * Wo;
 #pragma unroll
-                    for (int e = 0; e < FD_CE; ++e)
+                    for (int e = 0; e < CE; ++e)
                         if (64 * e + lane < Wo) orow[64 * e + lane] = C[c][e];
                 }
             }
@@ -144,7 +154,7 @@ __global__ __launch_bounds__(256) void dft2d_fwd_fd_kernel(Dft2dParams p) {
 #pragma unroll
                     for (int c = 0; c < FD_NC; ++c)
 #pragma unroll
-                        for (int e = 0; e < FD_CE; ++e) C[c][e] = (c + n < FD_NC) ? C[(c + n < FD_NC) ? c + n : 0][e] : 0.f;
+                        for (int e = 0; e < CE; ++e) C[c][e] = (c + n < FD_NC) ? C[(c + n < FD_NC) ? c + n : 0][e] : 0.f;
                 }
             }
         };
@@ -255,15 +265,15 @@ __global__ __launch_bounds__(256) void dft2d_fwd_fd_kernel(Dft2dParams p) {
 #undef UNO_FD_MFMA
 
             // ---- column operator on the 16 tile rows, from LDS (rows past the image are zero)
-            float Y[16][FD_CE];
+            float Y[16][CE];
             {
                 // the reads of row r + 1 are issued before the products of row r (two operand sets in ping-pong; sched_barrier keeps the
                 // compiler from hoisting all 640 reads of the tile to the front, which spilled)
                 const float* trow = buf + phase;
-                float xv[2][FD_CE][FD_KT];
-                auto read_row = [&](float (&x)[FD_CE][FD_KT], int r) {
+                float xv[2][CE][FD_KT];
+                auto read_row = [&](float (&x)[CE][FD_KT], int r) {
 #pragma unroll
-                    for (int e = 0; e < FD_CE; ++e) {
+                    for (int e = 0; e < CE; ++e) {
                         const float* q = trow + r * W + sc[e];
 #pragma unroll
                         for (int t = 0; t < FD_KT; ++t) x[e][t] = q[t];
@@ -272,11 +282,11 @@ __global__ __launch_bounds__(256) void dft2d_fwd_fd_kernel(Dft2dParams p) {
                 if (!(UNO_FD_KO & 1)) read_row(xv[0], 0);
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    if (UNO_FD_KO & 1) { for (int e = 0; e < FD_CE; ++e) Y[r][e] = 0.f; continue; }
+                    if (UNO_FD_KO & 1) { for (int e = 0; e < CE; ++e) Y[r][e] = 0.f; continue; }
                     if (r + 1 < 16) read_row(xv[(r + 1) & 1], r + 1);
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                    for (int e = 0; e < FD_CE; ++e) {
+                    for (int e = 0; e < CE; ++e) {
                         float acc = 0.f;
 #pragma unroll
                         for (int t = 0; t < FD_KT; ++t) acc = fmaf(wc[e][t], xv[r & 1][e][t], acc);
@@ -311,7 +321,7 @@ __global__ __launch_bounds__(256) void dft2d_fwd_fd_kernel(Dft2dParams p) {
                         for (int r = 4 * q4; r < 4 * q4 + 4; ++r) {
                             const float w = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wv[(c * 16 + r) >> 6]), (c * 16 + r) & 63));
 #pragma unroll
-                            for (int e = 0; e < FD_CE; ++e) C[c][e] = fmaf(w, Y[r][e], C[c][e]);
+                            for (int e = 0; e < CE; ++e) C[c][e] = fmaf(w, Y[r][e], C[c][e]);
                         }
                     }
                 }
@@ -331,29 +341,39 @@ __global__ __launch_bounds__(256) void dft2d_fwd_fd_kernel(Dft2dParams p) {
 
 // ---- launcher side
 // one wave per image whatever the image count (fwd_tile_geometry would give a lone image several waves): up to four images per workgroup
+// output columns per lane of the window W belongs to; 0: outside both
+static int fwd_fd_columns_per_lane(int W) {
+    return (W >= FD_MINW && W <= FD_MAXW) ? FD_CE : ((W >= FD_MINW2 && W <= FD_MAXW2) ? FD_CE2 : 0);
+}
+
 static bool fwd_fd_geometry(const Dft2dParams& p, int NT, int MT, int R4, FwdFtGeometry* out) {
     (void)MT;
     const int NTF = R4 > 0 ? NT - 1 : NT;
-    if (p.bf16 || p.rowfreq || p.W < FD_MINW || p.W > FD_MAXW) return false;
-    if (p.fd_Ho < 1 || p.fd_Wo < 1 || p.fd_Wo > 64 * FD_CE || p.fd_KW < 1 || p.fd_KW > FD_KT - 1) return false;
+    const int ce = fwd_fd_columns_per_lane(p.W);
+    if (p.bf16 || p.rowfreq || ce == 0) return false;
+    if (p.fd_Ho < 1 || p.fd_Wo < 1 || p.fd_Wo > 64 * ce || p.fd_KW < 1 || p.fd_KW > FD_KT - 1) return false;
     if ((long long)p.fd_Ho * p.fd_Wo > 0x7fffffffLL / 4) return false;
     const int cus = ft_device_cu_count();
+    // 223^2 level: up to four images per workgroup and two workgroups per CU (the LDS of each within half a CU's); where four tiles and
+    // the tables do not fit that, fewer images per workgroup
+    const size_t budget = ce == FD_CE2 ? FD_LDS_HALF : FT_LDS_BUDGET;
     int g = 4;
     while (g > 1 && (long long)(p.n_img + g - 1) / g < cus) --g;
-    while (g > 1 && fwd_ft_lds_bytes(p, NTF, R4, g) > FT_LDS_BUDGET) --g;
+    while (g > 1 && fwd_ft_lds_bytes(p, NTF, R4, g) > budget) --g;
     const size_t lds = fwd_ft_lds_bytes(p, NTF, R4, g);
-    if (lds > FT_LDS_BUDGET) return false;
+    if (lds > budget) return false;
     *out = FwdFtGeometry{1, g, lds};
     return true;
 }
 
-template <int NT, int MT, int R4>
+template <int NT, int MT, int R4, int CE = FD_CE>
 static int launch_fwd_fd(Dft2dParams p, const FwdFtGeometry& g, hipStream_t s) {
-    auto K = dft2d_fwd_fd_kernel<NT, MT, R4>;
+    auto K = dft2d_fwd_fd_kernel<NT, MT, R4, CE>;
     static int lds_slot[64];
     if (!ensure_dynamic_lds(reinterpret_cast<const void*>(K), g.lds, lds_slot)) { set_error("dft2d_fwd_fd: cannot raise dynamic LDS to %zu", g.lds); return -4; }
     char name[64];
-    snprintf(name, sizeof(name), "uno::dft2d_fwd_fd_kernel<%d, %d, %d>", NT, MT, R4);
+    if constexpr (CE == FD_CE) snprintf(name, sizeof(name), "uno::dft2d_fwd_fd_kernel<%d, %d, %d>", NT, MT, R4);
+    else snprintf(name, sizeof(name), "uno::dft2d_fwd_fd_kernel<%d, %d, %d, %d>", NT, MT, R4, CE);
     p.nw = 1;
     p.rev = fwd_ft_sweep();             // once per launch, the K1 family's counter
     {

@@ -308,6 +308,9 @@ bool dft2d_inv_add_applies(const Dft2dParams& p);       // dft2d_inv_add.hip: K3
 int launch_dft2d_inv_add(const Dft2dParams& p, hipStream_t s);
 bool dft2d_fwd_fd_applies(const Dft2dParams& p);        // dft2d_fwd_fd.hip: K1 + down-sampled image (p.fd_Ho, fd_Wo, fd_KW set)
 int launch_dft2d_fwd_fd(const Dft2dParams& p, hipStream_t s);
+// spectrum_crop.hip: the (2 m1, m2) corner blocks of (2 M1, M2) truncated spectra; both sides in the grouped layout (arguments validated by the caller)
+int launch_spectrum_crop(const float* src, float* dst, int n_img, int M1, int M2, int m1, int m2, int s_group, int s_stride, int s_offset,
+                         int d_group, int d_stride, int d_offset, hipStream_t s);
 bool dft2d_fwd_plane_applies(const Dft2dParams& p);      // dft2d_plane.hip: many small images
 bool dft2d_inv_plane_applies(const Dft2dParams& p);
 bool dft2d_b16_applies(const Dft2dParams& p);           // dft2d_b16.hip: bfloat16 images, row stage on the bf16 MFMA

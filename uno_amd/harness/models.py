@@ -15,7 +15,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ..integral_operators import (GradJoin, OperatorBlock_2D, OperatorBlock_3D, channel_mix, channel_mix_cat, channel_mix_cat_project,
+from ..integral_operators import (GradJoin, SpectrumShare, OperatorBlock_2D, OperatorBlock_3D, channel_mix, channel_mix_cat, channel_mix_cat_project,
                                   enable_native_resample3d_any, enable_one_buffer_any_grid, gelu_channel_mix, gelu_channel_mix_pad, gelu_pad2d, gelu_project, gelu_project2,
                                   lift_gelu_pad)
 
@@ -87,7 +87,10 @@ class UNO_9(nn.Module):
             # join of c0; conv4, c2's only consumer) applies gelu'(pre) in its last accumulating kernel (`out_join`)
             jc, j2 = GradJoin(), GradJoin()
             c0 = self.conv0(lifted, d1 // 2, d2 // 2, join=jl, out_join=jc)
-            c1 = self.conv1(c0, d1 // 4, d2 // 4, join=jc)
+            # ... and c0's forward TRANSFORM is shared: conv1 transforms it once at conv5's mode counts, into conv5's spectrum, and crops
+            # its own (fewer) modes from that; conv5 skips its transform of c0 (SpectrumShare)
+            sc = SpectrumShare.for_block(self.conv5, self.conv4.conv.out_channels)
+            c1 = self.conv1(c0, d1 // 4, d2 // 4, join=jc, share=sc)
             c2 = self.conv2(c1, d1 // 4, d2 // 4, out_join=j2)
             # skip connections: conv5 consumes cat([conv4 output, c0]) and fc1 cat([conv5 output, lifted]) from their two
             # sources; the concatenations are never built.  conv5's GELU is deferred to its only consumer: fc1 applies it while
@@ -95,7 +98,7 @@ class UNO_9(nn.Module):
             skip5 = [self.conv4(c2, d1 // 2, d2 // 2, join=j2), c0]
             # fc2(gelu(fc1(cat([gelu(conv5 pre), lifted])))): one forward kernel (the fc1 pass also reduces its 64 channels to the output)
             # ... on the S1 x S2 domain only (the padding is cropped from the result: its points are never computed)
-            out = channel_mix_cat_project([self.conv5.forward_cat(skip5, d1, d2, defer_gelu=True, defer_grad=jc), lifted], self.fc1.weight,
+            out = channel_mix_cat_project([self.conv5.forward_cat(skip5, d1, d2, defer_gelu=True, defer_grad=jc, share=sc), lifted], self.fc1.weight,
                                           self.fc1.bias, self.fc2.weight, self.fc2.bias, gelu_first=True, defer_grad=jl, crop=(S1, S2))
             return out[:, :, :S1, :S2].permute(0, 2, 3, 1).contiguous()
         else:

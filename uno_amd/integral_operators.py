@@ -28,14 +28,14 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ._param_grads import release_pass_state
-from .block2d import _OperatorBlock2dCatFn, _OperatorBlock2dFn, _SpectralConv2dFn, spectral_conv2d, spectral_conv2d_mixed
+from .block2d import SpectrumShare, _OperatorBlock2dCatFn, _OperatorBlock2dFn, _SpectralConv2dFn, spectral_conv2d, spectral_conv2d_mixed
 from .pointwise import (GradJoin, _dev_act, channel_mix, channel_mix_cat, channel_mix_cat_project, gelu_channel_mix, gelu_channel_mix_pad,
                         gelu_pad2d, gelu_project, gelu_project2, instance_norm_gelu, lift_gelu_pad)
 from .resample import resample2d_bicubic_aa
 from .spectral3d import (_FftResample3dAnyFn, _FftResample3dFn, _OperatorBlock3dFn, _resample3d_plan, _resample3d_plan_any, spectral_conv3d)
 
 __all__ = [
-    "enable_mixed_precision", "enable_native_resample3d_any", "enable_one_buffer_any_grid", "GradJoin", "channel_mix_cat_project", "release_pass_state",
+    "enable_mixed_precision", "enable_native_resample3d_any", "enable_one_buffer_any_grid", "GradJoin", "SpectrumShare", "channel_mix_cat_project", "release_pass_state",
     "SpectralConv1d_Uno", "pointwise_op_1D", "OperatorBlock_1D",
     "SpectralConv2d_Uno", "pointwise_op_2D", "OperatorBlock_2D",
     "SpectralConv3d_Uno", "pointwise_op_3D", "OperatorBlock_3D",
@@ -144,22 +144,23 @@ class OperatorBlock_2D(nn.Module):
         if Normalize:
             self.normalize_layer = nn.InstanceNorm2d(int(out_codim), affine=True)
 
-    def forward(self, x, dim1=None, dim2=None, *, join=None, out_join=None):
+    def forward(self, x, dim1=None, dim2=None, *, join=None, out_join=None, share=None):
         """join / out_join (optional, beyond the reference signature): GradJoin objects of the input / of this block's output - see
-        GradJoin and _OperatorBlock2dFn."""
+        GradJoin and _OperatorBlock2dFn.  share: SpectrumShare of the input, this block being its first spectral consumer."""
         if self.non_lin and not self.normalize:
-            return self._branches(x, dim1, dim2, gelu=True, join=join, out_join=out_join)
+            return self._branches(x, dim1, dim2, gelu=True, join=join, out_join=out_join, share=share)
         if out_join is not None:            # no GELU straight after the sum: this block leaves no pre-activation tensor to a join
             out_join.void()
-        out = self._branches(x, dim1, dim2, join=join)
+        out = self._branches(x, dim1, dim2, join=join, share=share)
         if self.normalize:
             return instance_norm_gelu(out, self.normalize_layer, self.non_lin)
         return out
 
-    def forward_cat(self, xs, dim1=None, dim2=None, defer_gelu=False, defer_grad=None):
+    def forward_cat(self, xs, dim1=None, dim2=None, defer_gelu=False, defer_grad=None, share=None):
         """self(torch.cat(xs, dim=1), dim1, dim2) for a skip connection (reference darcy_flow_uno2d.py:117-125) - two
         float32 device tensors are consumed in place, the concatenation is never built.  defer_gelu (blocks without
-        normalisation only): return the PRE-activation sum; the caller's consumer applies the GELU as it reads it."""
+        normalisation only): return the PRE-activation sum; the caller's consumer applies the GELU as it reads it.  share: SpectrumShare of
+        xs[1], whose first spectral consumer has transformed it for this block as well (the stock-op path ignores it)."""
         if defer_gelu and (self.normalize or not self.non_lin):
             raise ValueError("defer_gelu needs a block with Non_Lin=True and Normalize=False")
         xs = list(xs)
@@ -179,14 +180,14 @@ class OperatorBlock_2D(nn.Module):
         if dim1 is not None:
             conv.dim1, conv.dim2 = dim1, dim2
         out = _OperatorBlock2dCatFn.apply(xs[0], xs[1], conv.weights1, conv.weights2, w.conv.weight, w.conv.bias, int(d1), int(d2),
-                                          xs[0].dtype == torch.bfloat16, defer_grad)
+                                          xs[0].dtype == torch.bfloat16, defer_grad, share)
         if defer_gelu:
             return out
         if self.normalize:
             return instance_norm_gelu(out, self.normalize_layer, self.non_lin)
         return F.gelu(out) if self.non_lin else out
 
-    def _branches(self, x, dim1, dim2, gelu=False, join=None, out_join=None):
+    def _branches(self, x, dim1, dim2, gelu=False, join=None, out_join=None, share=None):
         """conv(x) + w(x) [then GELU when `gelu`: written by the kernel that completes the sum where the fused path runs]"""
         conv, w = self.conv, self.w
         if dim1 is not None:        # the spectral layer keeps a call-time override, the point-wise one does not (:182-184, :236-238)
@@ -203,7 +204,7 @@ class OperatorBlock_2D(nn.Module):
             out = conv(x) + w(x, d1, d2)
             return F.gelu(out) if gelu else out
         return _OperatorBlock2dFn.apply(x, conv.weights1, conv.weights2, w.conv.weight, w.conv.bias, int(d1), int(d2),
-                                        x.dtype == torch.bfloat16, bool(gelu), join, out_join)
+                                        x.dtype == torch.bfloat16, bool(gelu), join, out_join, share)
 
     def _takes(self, x):
         """4-D device tensor the fused block kernels take: float32, or bfloat16 once the spectral layer is in mixed-precision mode."""
