@@ -1,8 +1,10 @@
 """Every spectral kernel that a bench table names is reached by an oracle comparison AT THE BENCH SHAPE.  pytest -m gpu
 
 The kernels of the spectral path are picked per shape (register / full-tile / half-tile transforms, plane-batched or one workgroup
-per volume, 4x4x1 or LDS-staged per-mode GEMM, 8- or 16-mode variants).  The shape-class tests elsewhere cover every variant, but a
-variant can still be wrong only at the geometry a benchmark dispatches it with.  Here the layers of the four workloads bench.py
+per volume, 4x4x1 or LDS-staged per-mode GEMM, 8- or 16-mode variants).  test_hip_dft2d_instances.py covers every variant of the 2-D
+transforms K1 / K3 (each compiled instantiation at a shape that dispatches to it; test_dft2d_instances_cpu.py checks that none is left
+out), the shape-class tests elsewhere a part of the other families' variants - but a variant can still be wrong only at the geometry
+a benchmark dispatches it with.  Here the layers of the four workloads bench.py
 times (BASELINE.json configs[1..4]) run at their full sizes - batch, channels, grid, modes - against the reference's op sequence
 (rfft -> corner einsum -> irfft, oracle/spectral_oracle.py, pinned by the goldens) on the host, with the library's per-kernel
 records on: the names that ran are collected, and the last test asserts that every spectral kernel named in the committed bench
