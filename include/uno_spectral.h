@@ -357,6 +357,30 @@ long long uno_rel_l2_steps_ws_bytes(int B, long long P, int T);
 int uno_rel_l2_steps(const float* pred, const float* target, float* sums, float* rel, float* totals, void* ws, int B, long long P, int T,
                      void* stream);
 
+/* The relative L2 TRAINING loss and its gradient (additive: the ABI version stays 14).  The reference's three training loops call
+ * `LpLoss(size_average=False)(x.view(B, -1), y.view(B, -1))` (utilities3.py:86-100; train_darcy.py:53, ns_train_2d.py:55,
+ * ns_train_3d.py:58-64) - about six small launches forward and eight backward as stock ops, 40 times per NS-2D roll-out.
+ * x, y: float32 seen as (B, N); element [b][e] of x lies x_row * b + x_elem * e ELEMENTS from x (likewise y): a time slice
+ * `out[..., t].view(B, -1)` is x_elem = T_f.  Strides are >= 0 (0: a broadcast operand).
+ * uno_rel_l2_forward - two launches (partial sums over (chunk, row), then one workgroup), written by the call:
+ *   sums  (B, 2)  [b][0] = sum_e (x - y)^2,  [b][1] = sum_e y^2
+ *   ratio (B)     sqrt(sums[b][0]) / sqrt(sums[b][1])
+ *   total (1)     sum_b ratio[b]
+ * uno_rel_l2_backward - one launch: gx (B, N) dense, gx[b][e] = g[b] * scale * (x - y)[b][e] / (sqrt(num_b) * sqrt(den_b)) with
+ *   (num_b, den_b) = sums[b] of the forward call; g lives on the device - B values (g_per_row = 1) or one (g_per_row = 0) - and is never
+ *   read by the host.  Where num_b == 0 the row's gradient is 0 (the backward of torch.linalg.vector_norm).  No gradient for y.
+ * No clamping: a zero target row gives ratio = +inf (NaN for 0 / 0) as torch.norm(.) / torch.norm(.) does.
+ * B >= 0, N >= 1, any B * N (64-bit offsets); B == 0 returns 0 without touching the device.  No atomics; the chunk decomposition is a
+ * function of N alone (4096 elements per chunk, at most 64 chunks; not of the CU count or uno_reserve_cus) and chunk partials are
+ * summed in double in ascending order and rounded once: two calls, a call under uno_reserve_cus and a graph replay give the same bits.
+ * 16-byte loads where both element strides are 1 and every row of x and y starts 16-byte aligned, 4-byte loads otherwise.
+ * ws: scratch of uno_rel_l2_ws_bytes() = 8 * B * chunks(N) bytes (0 for bad sizes; never shrinks as N grows). */
+long long uno_rel_l2_ws_bytes(int B, long long N);
+int uno_rel_l2_forward(const float* x, long long x_row, long long x_elem, const float* y, long long y_row, long long y_elem, float* sums,
+                       float* ratio, float* total, void* ws, int B, long long N, void* stream);
+int uno_rel_l2_backward(const float* x, long long x_row, long long x_elem, const float* y, long long y_row, long long y_elem,
+                        const float* sums, const float* g, int g_per_row, float scale, float* gx, int B, long long N, void* stream);
+
 /* One step of the NS-2D evaluation roll-out in one launch (additive: the ABI version stays 14).  The reference's validation and test
  * loops (ns_train_2d.py:94-107, 141-157) run the model T_f times under no_grad, feed each prediction back into the input window and
  * report the sum of the per-step relative L2 errors and the error of the whole trajectory; between two forward passes they spend a

@@ -6,6 +6,7 @@ error is raised to the caller (RuntimeError, as the reference surfaces torch Run
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 import threading
@@ -92,6 +93,9 @@ _SIGNATURES = {
     "uno_gelu_project2_backward": (C.c_int, [_fp] * 9 + [_i, _i, _i, C.c_longlong, _i, _fp]),
     "uno_rel_l2_steps_ws_bytes": (C.c_longlong, [_i, C.c_longlong, _i]),
     "uno_rel_l2_steps": (C.c_int, [_fp] * 6 + [_i, C.c_longlong, _i, _fp]),
+    "uno_rel_l2_ws_bytes": (C.c_longlong, [_i, C.c_longlong]),
+    "uno_rel_l2_forward": (C.c_int, [_fp, C.c_longlong, C.c_longlong] * 2 + [_fp] * 4 + [_i, C.c_longlong, _fp]),
+    "uno_rel_l2_backward": (C.c_int, [_fp, C.c_longlong, C.c_longlong] * 2 + [_fp, _fp, _i, C.c_float, _fp, _i, C.c_longlong, _fp]),
     "uno_rollout_ws_bytes": (C.c_longlong, [_i, C.c_longlong, _i]),
     "uno_rollout_advance": (C.c_int, [_fp] * 5 + [_i, _i, _i, C.c_longlong, _i, _i, _i, _fp]),
     "uno_rollout_finish": (C.c_int, [_fp] * 4 + [_i, C.c_longlong, _i, _fp]),
@@ -1131,6 +1135,75 @@ def rel_l2_steps(pred, target):
         rc = L.uno_rel_l2_steps(_ptr(pred), _ptr(target), _ptr(sums), _ptr(rel), _ptr(totals), _ptr(ws), B, P, T, _stream(pred))
     _check(rc, "uno_rel_l2_steps")
     return sums, rel, totals
+
+
+def _rel_l2_operands(x, y):
+    """x, y: f32 (B, N) on one device, of any two strides (a row stride and an element stride) -> (B, N)"""
+    _require(x, torch.float32, "x", dense=False)
+    _require(y, torch.float32, "y", dense=False)
+    if x.dim() != 2 or x.shape != y.shape or x.device != y.device:
+        raise RuntimeError(f"uno_amd: the relative L2 loss takes two (B, N) tensors on one device (got {tuple(x.shape)} on {x.device} "
+                           f"and {tuple(y.shape)} on {y.device})")
+    if x.shape[1] < 1:
+        raise RuntimeError(f"uno_amd: the relative L2 loss needs at least one element per row (got {tuple(x.shape)})")
+    return x.shape[0], x.shape[1]
+
+
+def _raw_stream(t):
+    """the current stream of t's device as an integer handle (torch's raw accessor where it exists: no Stream object is built)"""
+    get = getattr(torch._C, "_cuda_getCurrentRawStream", None)
+    return C.c_void_p(get(t.device.index)) if get is not None and t.device.index is not None else _stream(t)
+
+
+def _on_device(device):
+    """a context in which `device` is current - torch.cuda.device(), or nothing where it already is (the loss is called once per
+    roll-out step, and its host time is what it costs: this spares the context's two device switches)"""
+    return contextlib.nullcontext() if device.index == torch.cuda.current_device() else torch.cuda.device(device)
+
+
+def rel_l2_views(record, B):
+    """-> sums (B, 2), ratio (B,), total (1,): views of a rel_l2_forward record"""
+    return record[:2 * B].view(B, 2), record[2 * B:3 * B], record[3 * B:3 * B + 1]
+
+
+def rel_l2_forward(x, y):
+    """x, y f32 (B, N) views (row stride, element stride) -> ONE flat f32 record [sums (B, 2) | ratio (B) | total (1) | workspace]
+    (rel_l2_views): sums = [sum (x - y)^2, sum y^2], ratio = sqrt(num) / sqrt(den), total = sum of ratio (uno_rel_l2_forward, K20: two
+    launches, fixed summation order).  One allocation: the call sits between two model passes 40 times per NS-2D roll-out, and its
+    host time is what it costs there.  Launches on the current stream and allocates through torch, so it can be captured into a hipGraph."""
+    B, N = _rel_l2_operands(x, y)
+    L = lib()
+    head = (3 * B + 2) // 2 * 2                     # the workspace holds float2: an even offset
+    with _on_device(x.device):
+        record = torch.empty((head + L.uno_rel_l2_ws_bytes(B, N) // 4,), dtype=torch.float32, device=x.device)
+        if B == 0:
+            record.zero_()
+        base = record.data_ptr()
+        rc = L.uno_rel_l2_forward(_ptr(x), x.stride(0), x.stride(1), _ptr(y), y.stride(0), y.stride(1), base, base + 8 * B, base + 12 * B,
+                                  base + 4 * head, B, N, _raw_stream(x))
+    _check(rc, "uno_rel_l2_forward")
+    return record
+
+
+def rel_l2_backward(x, y, sums, g, scale=1.0):
+    """The gradient of rel_l2_forward's ratio (or total) at x, dense (B, N): g * scale * (x - y) / (sqrt(num) sqrt(den)) (uno_rel_l2_backward,
+    K20: one launch).  sums: (B, 2) from the forward call, or its whole record (which begins with them).  g: f32 on the device, (B,) -
+    one value per row - or one element, which every row takes; it is not read by the host.  Rows with num == 0 get a zero gradient."""
+    B, N = _rel_l2_operands(x, y)
+    _require(sums, torch.float32, "sums")
+    _require(g, torch.float32, "g")
+    if (sums.shape != (B, 2) and (sums.dim() != 1 or sums.numel() < 3 * B + 1)) or sums.device != x.device or g.device != x.device:
+        raise RuntimeError(f"uno_amd: sums {tuple(sums.shape)} on {sums.device} is neither the (B, 2) = ({B}, 2) sums nor the record of the "
+                           f"forward call on {x.device}")
+    if g.numel() != 1 and g.shape != (B,):
+        raise RuntimeError(f"uno_amd: g {tuple(g.shape)} holds neither one value nor one per row ({B})")
+    per_row = 0 if g.numel() == 1 else 1
+    with _on_device(x.device):
+        gx = torch.empty((B, N), dtype=torch.float32, device=x.device)
+        rc = lib().uno_rel_l2_backward(_ptr(x), x.stride(0), x.stride(1), _ptr(y), y.stride(0), y.stride(1), _ptr(sums), _ptr(g), per_row,
+                                       float(scale), _ptr(gx), B, N, _raw_stream(x))
+    _check(rc, "uno_rel_l2_backward")
+    return gx
 
 
 def rollout_ws(B, P, T, device):

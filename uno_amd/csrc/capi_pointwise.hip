@@ -541,6 +541,38 @@ int uno_rel_l2_steps(const float* pred, const float* target, float* sums, float*
     return launch_rel_l2_steps(pred, target, sums, rel, totals, (float*)ws, B, P, T, (hipStream_t)stream);
 }
 
+// K20: the relative L2 training loss and its gradient, float32 (B, N) views with a row stride and an element stride each
+static bool rel_l2_sizes(const char* who, int B, long long N, long long xrs, long long xes, long long yrs, long long yes) {
+    if (B < 0 || N < 1) { set_error("%s: bad sizes B=%d N=%lld", who, B, N); return false; }
+    if (xrs < 0 || xes < 0 || yrs < 0 || yes < 0) {
+        set_error("%s: bad strides x (%lld, %lld) y (%lld, %lld): none may be negative", who, xrs, xes, yrs, yes);
+        return false;
+    }
+    return true;
+}
+
+long long uno_rel_l2_ws_bytes(int B, long long N) {
+    if (B < 1 || N < 1) return 0;
+    return 4LL * rel_l2_ws_floats(B, N);
+}
+
+int uno_rel_l2_forward(const float* x, long long x_row, long long x_elem, const float* y, long long y_row, long long y_elem, float* sums,
+                       float* ratio, float* total, void* ws, int B, long long N, void* stream) {
+    if (!rel_l2_sizes("uno_rel_l2_forward", B, N, x_row, x_elem, y_row, y_elem)) return -1;
+    if (B == 0) return 0;
+    if (!x || !y || !sums || !ratio || !total || !ws) { set_error("uno_rel_l2_forward: null pointer"); return -1; }
+    return launch_rel_l2_forward(x, x_row, x_elem, y, y_row, y_elem, sums, ratio, total, (float*)ws, B, N, (hipStream_t)stream);
+}
+
+int uno_rel_l2_backward(const float* x, long long x_row, long long x_elem, const float* y, long long y_row, long long y_elem, const float* sums,
+                        const float* g, int g_per_row, float scale, float* gx, int B, long long N, void* stream) {
+    if (!rel_l2_sizes("uno_rel_l2_backward", B, N, x_row, x_elem, y_row, y_elem)) return -1;
+    if (g_per_row != 0 && g_per_row != 1) { set_error("uno_rel_l2_backward: g_per_row = %d, 0 (one scalar) or 1 (one per row)", g_per_row); return -1; }
+    if (B == 0) return 0;
+    if (!x || !y || !sums || !g || !gx) { set_error("uno_rel_l2_backward: null pointer"); return -1; }
+    return launch_rel_l2_backward(x, x_row, x_elem, y, y_row, y_elem, sums, g, g_per_row, scale, gx, B, N, (hipStream_t)stream);
+}
+
 // K18: one step of the NS-2D evaluation roll-out (forward only), dense float32; the finish launch is K17's
 static bool rollout_sizes(const char* who, int B, long long P, int T) {
     if (B < 0 || P < 1 || T < 1) { set_error("%s: bad sizes B=%d P=%lld T=%d", who, B, P, T); return false; }

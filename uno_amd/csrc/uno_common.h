@@ -422,5 +422,13 @@ int launch_rollout_lift_backward(const float* gh, const float* given, const floa
                                  long long P, int T, int t, hipStream_t s);
 int launch_rollout_loss_seed(const float* pred, const float* target, const float* sums, const float* gL, float* gframe, int B, long long P, int T,
                              hipStream_t s);
+// rel_l2_loss.hip (K20): the relative L2 training loss of (B, N) views with a row and an element stride each, forward (partial + finish
+// launch) and backward (one launch, gx dense); ws: rel_l2_ws_floats() floats
+long long rel_l2_chunks(long long N, long long* chunk_elems);       // chunk count: a function of N alone
+long long rel_l2_ws_floats(int B, long long N);
+int launch_rel_l2_forward(const float* x, long long xrs, long long xes, const float* y, long long yrs, long long yes, float* sums, float* ratio,
+                          float* total, float* ws, int B, long long N, hipStream_t s);
+int launch_rel_l2_backward(const float* x, long long xrs, long long xes, const float* y, long long yrs, long long yes, const float* sums,
+                           const float* g, int per_row, float scale, float* gx, int B, long long N, hipStream_t s);
 
 }  // namespace uno

@@ -11,6 +11,99 @@ def lp_loss_rel_sum(pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     return (diff / torch.linalg.vector_norm(target.reshape(n, -1), ord=2, dim=1)).sum()
 
 
+def _rows(t: torch.Tensor) -> Optional[torch.Tensor]:
+    """t seen as (B, N) without a copy - a row stride and an element stride - or None where that needs more than two strides
+    (a cropped plane) or there is nothing to sum"""
+    if t.dim() < 1 or t.shape[0] == 0 or t.numel() == 0:
+        return None
+    try:
+        return t.view(t.shape[0], -1)
+    except RuntimeError:
+        return None
+
+
+def _native_rows(x: torch.Tensor, y: torch.Tensor):
+    """(x, y) as the (B, N) views the native loss takes, or None: float32 device tensors of one shape, a target that needs no gradient"""
+    if not (x.is_cuda and y.is_cuda and x.device == y.device and x.dtype == torch.float32 and y.dtype == torch.float32
+            and x.shape == y.shape and not (y.requires_grad and torch.is_grad_enabled())):
+        return None
+    xr, yr = _rows(x), _rows(y)
+    return None if xr is None or yr is None else (xr, yr)
+
+
+class _RelL2Fn(torch.autograd.Function):
+    """(x, y) as (B, N) views -> the ratios (B,) (reduce = 0), their sum (1) or their mean (2), 0-dim: uno_rel_l2_forward /
+    uno_rel_l2_backward (K20).  The upstream gradient stays on the device; a reduced result hands the kernel ONE scalar."""
+
+    @staticmethod
+    def forward(ctx, x, y, reduce):
+        from .. import _native
+        record = _native.rel_l2_forward(x, y)           # [sums (B, 2) | ratio (B) | total (1) | workspace]
+        ctx.save_for_backward(x, y, record)
+        ctx.reduce = reduce
+        B = x.shape[0]
+        if reduce == 0:
+            return record[2 * B:3 * B]
+        return record[3 * B] if reduce == 1 else record[3 * B] / B
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        from .. import _native
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        x, y, record = ctx.saved_tensors
+        if g.dtype != torch.float32:
+            g = g.to(torch.float32)
+        if g.dim() == 1 and g.shape[0] > 1 and g.stride(0) == 0:        # the gradient of `.sum()`: one value expanded over the rows
+            g = g[:1]
+        elif not g.is_contiguous():
+            g = g.contiguous()
+        return _native.rel_l2_backward(x, y, record, g, 1.0 / x.shape[0] if ctx.reduce == 2 else 1.0), None, None
+
+
+def rel_l2(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """||x_b - y_b||_2 / ||y_b||_2 for every batch entry b, (B,), differentiable in x - `LpLoss(reduction=False)(x, y)` of the reference
+    (utilities3.py:86-100).  float32 device tensors whose (B, -1) view is a row stride plus an element stride (dense tensors, and the
+    time slices `out[..., t]` of ns_train_3d.py:58-61) with a target that needs no gradient take the native kernels (K20: two launches
+    forward, one backward, fixed summation order, no host synchronisation); everything else - CPU, other dtypes, a target that
+    requires grad, views of more than two strides - the stock ops of lp_loss_rel_sum."""
+    rows = _native_rows(x, y)
+    if rows is None:
+        n = x.shape[0]
+        diff = torch.linalg.vector_norm(x.reshape(n, -1) - y.reshape(n, -1), ord=2, dim=1)
+        return diff / torch.linalg.vector_norm(y.reshape(n, -1), ord=2, dim=1)
+    return _RelL2Fn.apply(rows[0], rows[1], 0)
+
+
+class LpLoss(object):
+    """The reference's loss object (utilities3.py:75-103) - same constructor, `rel` and `__call__` - on the native relative-L2 kernels
+    where they apply (p == 2 and the conditions of rel_l2); sum and mean are the kernel's own total, so a training step's loss costs
+    two launches forward and one backward.  Other p and everything rel_l2 leaves to stock ops run as the reference writes them."""
+
+    def __init__(self, d=2, p=2, size_average=True, reduction=True):
+        super(LpLoss, self).__init__()
+        assert d > 0 and p > 0
+        self.d = d
+        self.p = p
+        self.reduction = reduction
+        self.size_average = size_average
+
+    def rel(self, x, y):
+        rows = _native_rows(x, y) if self.p == 2 else None
+        if rows is not None:
+            return _RelL2Fn.apply(rows[0], rows[1], 0 if not self.reduction else (2 if self.size_average else 1))
+        n = x.size()[0]
+        ratio = torch.linalg.vector_norm(x.reshape(n, -1) - y.reshape(n, -1), ord=self.p, dim=1) \
+            / torch.linalg.vector_norm(y.reshape(n, -1), ord=self.p, dim=1)
+        if self.reduction:
+            return torch.mean(ratio) if self.size_average else torch.sum(ratio)
+        return ratio
+
+    def __call__(self, x, y):
+        return self.rel(x, y)
+
+
 class StepErrors(NamedTuple):
     """Relative L2 errors of a (B, ..., T) prediction per time step and for the whole trajectory (device tensors)."""
     sums: torch.Tensor          # (B, T, 2): [sum (pred - target)^2, sum target^2] of every time slice
