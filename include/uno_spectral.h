@@ -116,6 +116,23 @@ int uno_fft_resample3d_any_acc(const float* x, float* y, float* y_act, void* ws,
                                int J1, const int* f1_in, const int* f1_out, int J2, const int* f2_in, const int* f2_out, int m3,
                                float scale, int herm_in, int herm_out, void* stream);
 
+/* The same operator once more (no ABI change: new entry points only), for the grids of the reference's 256 x 256 NS-3D models
+ * (Uno3D_T20_256 / Uno3D_T10_256, navier_stokes_uno3d.py:993-1181 / :1184-1372: conv0 resamples (256,256,T) -> (64,64,T), conv8
+ * (64,64,T) -> (256,256,T); the operator itself is integral_operators.py:448-463, quirks kept).  The two leading (complex) axes of x and y
+ * in 2 ... 256, the last (real) axis in 2 ... 64, any J1, J2 in 1 ... 256, any 1 <= m3 <= D3/2 + 1 (and <= M3/2 + 1).  Tables, Hermitian
+ * weights, adjoint convention, workspace size and the _acc form (y += result; y_act = gelu(y) when y_act != NULL; y_act == y, x == y and
+ * x == y_act refused) are those of uno_fft_resample3d_any / _any_acc.  The sums along the two complex axes run on v_mfma_f32_16x16x4_f32
+ * (exact f32, fixed order: two runs are bit-identical); plane and volume offsets are 64-bit.  Outside the range the call returns an error
+ * that names the limits; a combination inside it whose kernels would need more than 160 KB of LDS (modes3 = 33 with J2 + M2 > 500) is
+ * refused with -2 before any launch. */
+long long uno_fft_resample3d_wide_ws_bytes(int n_vol, int D1, int M1, int J1, int J2, int m3);
+int uno_fft_resample3d_wide(const float* x, float* y, void* ws, int n_vol, int D1, int D2, int D3, int M1, int M2, int M3,
+                            int J1, const int* f1_in, const int* f1_out, int J2, const int* f2_in, const int* f2_out, int m3,
+                            float scale, int herm_in, int herm_out, void* stream);
+int uno_fft_resample3d_wide_acc(const float* x, float* y, float* y_act, void* ws, int n_vol, int D1, int D2, int D3, int M1, int M2, int M3,
+                                int J1, const int* f1_in, const int* f1_out, int J2, const int* f2_in, const int* f2_out, int m3,
+                                float scale, int herm_in, int herm_out, void* stream);
+
 /* SpectralConv3d_Uno.forward - reference integral_operators.py:385-427
  *   x (B, Ci, H, W, T) f32;  w[0..3] = weights1..4 (Ci, Co, m1, m2, m3) c64 in the reference's corner
  *   order (lo,lo), (hi,lo), (lo,hi), (hi,hi);  y (B, Co, Ho, Wo, To) f32 [out]

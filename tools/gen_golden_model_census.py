@@ -1,4 +1,4 @@
-"""The layer plan of the seven Navier-Stokes U-NO models, recorded from the genuine reference (navier_stokes_uno2d.py,
+"""The layer plan of the nine Navier-Stokes U-NO models, recorded from the genuine reference (navier_stokes_uno2d.py,
 navier_stokes_uno3d.py): which operator blocks each constructor builds and on which grids each forward pass calls them.
 
 Development machine only (it imports the reference checkout, which never enters this repository and never travels to the GPU box):
@@ -8,8 +8,9 @@ Development machine only (it imports the reference checkout, which never enters 
 The reference modules take their blocks from `from integral_operators import *`, so replacing the module globals `OperatorBlock_2D` /
 `OperatorBlock_3D` with a recording stand-in before a model is constructed is enough: no reference block is built or run.
 
-Writes tests/golden/model_census.json (data only): {"<class>-S<S>-pad<pad>[-both]": case} with
-    cls, args, kwargs, input   what tests/test_model_census_cpu.py needs to build our class and its zeros input
+Writes tests/golden/model_census.json and, for the two 3-D models for 256 x 256 simulations (classes of uno_amd.harness.models),
+tests/golden/model_census_256.json (data only): {"<class>-S<S>-pad<pad>[-both]": case} with
+    cls, args, kwargs, input   what tests/test_model_census_cpu.py / tests/test_model_census_256_cpu.py need to build our class and its zeros input
     ctor     per block in construction order: the positional arguments (in, out, default grid, modes), then Normalize, Non_Lin
     calls    per block call in order: [the input's shape[1:] (channels first, so the skip concatenations are pinned), the output grid]
     out      the output's shape
@@ -31,6 +32,9 @@ S2D, PADS2D = (56, 64, 100, 256), (0, 4)
 # class -> (in_width, width, input steps)
 MODELS3D = {"Uno3D_T20": (6, 2, 10), "Uno3D_T10": (6, 2, 10), "Uno3D_T9": (6, 2, 6), "Uno3D_T40": (6, 2, 10)}
 MODELS2D = {"UNO": (14, 4, 10), "UNO_P": (14, 4, 10), "UNO_S256": (5, 4, 1)}
+# the 3-D models for 256 x 256 simulations (their grids are D/4 ... D/32: the sizes they are for, and half of that)
+S3D_256 = (256, 128)
+MODELS3D_256 = {"Uno3D_T20_256": (6, 2, 10), "Uno3D_T10_256": (6, 2, 10)}
 
 
 class Recorder(nn.Module):
@@ -86,10 +90,18 @@ def main():
         for S in S2D:
             for pad in PADS2D:
                 cases[f"{name}-S{S}-pad{pad}"] = record(getattr(n2, name), (in_width, width), {"pad": pad}, (1, S, S, T_in))
-    path = os.path.join(args.out, "model_census.json")
-    with open(path, "w") as f:
-        f.write("{\n" + ",\n".join(f"{json.dumps(k)}: {json.dumps(v)}" for k, v in cases.items()) + "\n}\n")
-    print(path, len(cases), "cases,", sum("raises" in c for c in cases.values()), "raise,", os.path.getsize(path), "bytes")
+    cases_256 = {}
+    for name, (in_width, width, T_in) in MODELS3D_256.items():
+        for S in S3D_256:
+            for pad in PADS3D:
+                for both in (False, True):
+                    key = f"{name}-S{S}-pad{pad}" + ("-both" if both else "")
+                    cases_256[key] = record(getattr(n3, name), (in_width, width), {"pad": pad, "pad_both": both}, (1, S, S, T_in, 1))
+    for fname, group in (("model_census.json", cases), ("model_census_256.json", cases_256)):
+        path = os.path.join(args.out, fname)
+        with open(path, "w") as f:
+            f.write("{\n" + ",\n".join(f"{json.dumps(k)}: {json.dumps(v)}" for k, v in group.items()) + "\n}\n")
+        print(path, len(group), "cases,", sum("raises" in c for c in group.values()), "raise,", os.path.getsize(path), "bytes")
 
 
 if __name__ == "__main__":

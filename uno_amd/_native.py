@@ -39,6 +39,9 @@ _SIGNATURES = {
     "uno_fft_resample3d_any_ws_bytes": (C.c_longlong, [_i] * 6),
     "uno_fft_resample3d_any": (C.c_int, [_fp] * 3 + [_i] * 8 + [_fp, _fp, _i, _fp, _fp, _i, C.c_float, _i, _i, _fp]),
     "uno_fft_resample3d_any_acc": (C.c_int, [_fp] * 4 + [_i] * 8 + [_fp, _fp, _i, _fp, _fp, _i, C.c_float, _i, _i, _fp]),
+    "uno_fft_resample3d_wide_ws_bytes": (C.c_longlong, [_i] * 6),
+    "uno_fft_resample3d_wide": (C.c_int, [_fp] * 3 + [_i] * 8 + [_fp, _fp, _i, _fp, _fp, _i, C.c_float, _i, _i, _fp]),
+    "uno_fft_resample3d_wide_acc": (C.c_int, [_fp] * 4 + [_i] * 8 + [_fp, _fp, _i, _fp, _fp, _i, C.c_float, _i, _i, _fp]),
     "uno_dft2d_forward": (C.c_int, [_fp, _fp] + [_i] * 5 + [C.c_float, _i, _i, _fp]),
     "uno_dft2d_forward_bf16": (C.c_int, [_fp, _fp] + [_i] * 5 + [C.c_float, _i, _i, _fp]),
     "uno_dft2d_inverse_bf16": (C.c_int, [_fp, _fp] + [_i] * 5 + [C.c_float, _i, _i, _fp]),
@@ -334,9 +337,9 @@ def spectral_conv2d_backward(gy, xt, w1, w2, H: int, W: int, need_gx=True, need_
     return gx, gw1, gw2
 
 
-def _fft_resample3d(any_grid: bool, x, out_size, f1, f2, m3, scale, adjoint, out, act):
-    """fft_resample3d / fft_resample3d_any: the two kernel families take the same arguments"""
-    name = "uno_fft_resample3d_any" if any_grid else "uno_fft_resample3d"
+def _fft_resample3d(family: str, x, out_size, f1, f2, m3, scale, adjoint, out, act):
+    """fft_resample3d / fft_resample3d_any / fft_resample3d_wide (family "" / "_any" / "_wide"): the kernel families take the same arguments"""
+    name = "uno_fft_resample3d" + family
     _require(x, torch.float32, "x")
     *lead, D1, D2, D3 = x.shape
     M1, M2, M3 = (int(v) for v in out_size)
@@ -345,7 +348,7 @@ def _fft_resample3d(any_grid: bool, x, out_size, f1, f2, m3, scale, adjoint, out
         if t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous():
             raise RuntimeError("uno_amd: frequency tables must be contiguous int32 device tensors")
     J1, J2 = f1[0].numel(), f2[0].numel()
-    if any_grid and (f1[1].numel() != J1 or f2[1].numel() != J2):
+    if family and (f1[1].numel() != J1 or f2[1].numel() != J2):       # the pruned-DFT entry point alone takes tables of its own per side
         raise RuntimeError("uno_amd: the forward and inverse frequency tables of an axis must have the same length")
     L = lib()
     with torch.cuda.device(x.device):
@@ -370,14 +373,20 @@ def fft_resample3d(x, out_size, f1, f2, m3: int, scale: float, adjoint: bool, ou
     axes 1 / 2 and m3 half-spectrum bins, pruned inverse DFT with f1[1] / f2[1]; adjoint=True: Hermitian weights on the
     forward side instead of the inverse side (the transpose of the operator with sizes and tables swapped).
     out: ACCUMULATE into this (..., M1, M2, M3) tensor (returned); act: also return gelu(out) written in the same pass -> (out, act)."""
-    return _fft_resample3d(False, x, out_size, f1, f2, m3, scale, adjoint, out, act)
+    return _fft_resample3d("", x, out_size, f1, f2, m3, scale, adjoint, out, act)
 
 
 def fft_resample3d_any(x, out_size, f1, f2, m3: int, scale: float, adjoint: bool, out=None, act=False):
     """fft_resample3d on the any-grid kernels (uno_fft_resample3d_any / _acc): any number of kept rows, any 1 <= m3 <= n/2 + 1, axis
     lengths 2 ... 128.  Same tables, the same adjoint convention and the same `out` / `act`; the forward and inverse tables of an axis
     must have the same length."""
-    return _fft_resample3d(True, x, out_size, f1, f2, m3, scale, adjoint, out, act)
+    return _fft_resample3d("_any", x, out_size, f1, f2, m3, scale, adjoint, out, act)
+
+
+def fft_resample3d_wide(x, out_size, f1, f2, m3: int, scale: float, adjoint: bool, out=None, act=False):
+    """fft_resample3d on the wide-axis kernels (uno_fft_resample3d_wide / _acc): the two leading axes of 2 ... 256, the last of 2 ... 64,
+    any number of kept rows, any 1 <= m3 <= n/2 + 1; the long-axis sums run on the f32 MFMA.  Arguments as fft_resample3d_any."""
+    return _fft_resample3d("_wide", x, out_size, f1, f2, m3, scale, adjoint, out, act)
 
 
 def dft2d_forward(images, m1, m2, scale=1.0, hermitian_cols=False, mask_overlap=False, out=None, channel_offset=0):

@@ -505,6 +505,62 @@ int uno_fft_resample3d_any_acc(const float* x, float* y, float* y_act, void* ws,
                                    f2_in, f2_out, m3, scale, herm_in, herm_out, stream);
 }
 
+// ---- the same operator on the wide-axis kernels (resample3d_wide.hip): complex axes of 2 ... 256, a real axis of 2 ... 64, long-axis stages on the MFMA
+long long uno_fft_resample3d_wide_ws_bytes(int n_vol, int D1, int M1, int J1, int J2, int m3) {
+    (void)J1;       // the J1 spectrum rows live in LDS only
+    return 8LL * n_vol * ((long long)D1 + M1) * J2 * m3;
+}
+
+static int fft_resample3d_wide_impl(const char* who, const float* x, float* y, float* y_act, int accumulate, void* ws, int n_vol, int D1,
+                                    int D2, int D3, int M1, int M2, int M3, int J1, const int* f1_in, const int* f1_out, int J2,
+                                    const int* f2_in, const int* f2_out, int m3, float scale, int herm_in, int herm_out, void* stream) {
+    const int lead[4] = {D1, D2, M1, M2}, last[2] = {D3, M3};
+    bool ok = true;
+    for (int d : lead) ok = ok && d >= 2 && d <= 256;
+    for (int d : last) ok = ok && d >= 2 && d <= 64;
+    if (!ok) {
+        set_error("%s: grid (%d,%d,%d) -> (%d,%d,%d): the two leading axis lengths must be in 2 ... 256 and the last in 2 ... 64", who, D1, D2, D3,
+                  M1, M2, M3);
+        return -1;
+    }
+    if (J1 < 1 || J1 > 256 || J2 < 1 || J2 > 256) { set_error("%s: kept-row counts J1=%d, J2=%d must be in 1 ... 256", who, J1, J2); return -1; }
+    if (m3 < 1 || m3 > D3 / 2 + 1 || m3 > M3 / 2 + 1) {
+        set_error("%s: need 1 <= modes3=%d <= n/2+1 on the last axis %d -> %d", who, m3, D3, M3);
+        return -1;
+    }
+    if (n_vol < 0 || (long long)n_vol * 256 > 0x7fffffffLL) { set_error("%s: bad volume count %d (0 ... 2^23 - 1)", who, n_vol); return -1; }
+    size_t lds[3];
+    resample3d_wide_lds_bytes(D1, D2, D3, M1, M2, M3, J1, J2, m3, lds);
+    if (lds[0] > 160 * 1024 || lds[1] > 160 * 1024 || lds[2] > 160 * 1024) {
+        set_error("%s: grid (%d,%d,%d) -> (%d,%d,%d) with J1=%d, J2=%d, modes3=%d needs %zu / %zu / %zu bytes of LDS (forward plane / leading "
+                  "axis / inverse plane kernel): the limit is 163840 per workgroup", who, D1, D2, D3, M1, M2, M3, J1, J2, m3, lds[0], lds[1], lds[2]);
+        return -2;
+    }
+    if (accumulate) {       // the kernels read x while they write y, and read y back before they write y_act
+        if (y_act && y_act == y) { set_error("%s: y_act must not alias y", who); return -1; }
+        if (x && x == y) { set_error("%s: x must not alias y", who); return -1; }
+        if (x && x == y_act) { set_error("%s: x must not alias y_act", who); return -1; }
+    }
+    if (n_vol == 0) return 0;
+    if (!x || !y || !ws || !f1_in || !f1_out || !f2_in || !f2_out) { set_error("%s: null pointer", who); return -1; }
+    return launch_resample3d_wide(x, y, y_act, accumulate, ws, n_vol, D1, D2, D3, M1, M2, M3, J1, f1_in, f1_out, J2, f2_in, f2_out, m3, scale,
+                                  herm_in, herm_out, (hipStream_t)stream);
+}
+
+int uno_fft_resample3d_wide(const float* x, float* y, void* ws, int n_vol, int D1, int D2, int D3, int M1, int M2, int M3,
+                            int J1, const int* f1_in, const int* f1_out, int J2, const int* f2_in, const int* f2_out, int m3,
+                            float scale, int herm_in, int herm_out, void* stream) {
+    return fft_resample3d_wide_impl("uno_fft_resample3d_wide", x, y, nullptr, 0, ws, n_vol, D1, D2, D3, M1, M2, M3, J1, f1_in, f1_out, J2, f2_in,
+                                    f2_out, m3, scale, herm_in, herm_out, stream);
+}
+
+int uno_fft_resample3d_wide_acc(const float* x, float* y, float* y_act, void* ws, int n_vol, int D1, int D2, int D3, int M1, int M2, int M3,
+                                int J1, const int* f1_in, const int* f1_out, int J2, const int* f2_in, const int* f2_out, int m3,
+                                float scale, int herm_in, int herm_out, void* stream) {
+    return fft_resample3d_wide_impl("uno_fft_resample3d_wide_acc", x, y, y_act, 1, ws, n_vol, D1, D2, D3, M1, M2, M3, J1, f1_in, f1_out, J2,
+                                    f2_in, f2_out, m3, scale, herm_in, herm_out, stream);
+}
+
 static int check_modes3d(const char* who, int H, int W, int T, int Ho, int Wo, int To, int m1, int m2, int m3) {
     if (H < 1 || W < 1 || T < 1 || Ho < 1 || Wo < 1 || To < 1) { set_error("%s: empty grid", who); return -1; }
     if (m1 < 1 || m1 > H || m1 > Ho) { set_error("%s: modes1=%d incompatible with axis %d -> %d", who, m1, H, Ho); return -1; }

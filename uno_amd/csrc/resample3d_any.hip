@@ -20,8 +20,7 @@
 // K3a also has an accumulate form (y += result) and an accumulate + activation form (y_act = gelu(y) in the same pass): the point-wise
 // branch of a one-buffer OperatorBlock_3D (reference integral_operators.py:506-512) on these grids.  Separate instantiations: the plain
 // form's code is what it was.
-#include "uno_common.h"
-#include <algorithm>
+#include "resample3d_common.h"
 
 namespace uno {
 
@@ -39,12 +38,9 @@ struct Resample3dAnyParams {
     int accumulate;             // K3a: y += result instead of y = result
 };
 
-constexpr int RA_THREADS = 256;
 constexpr int RA_TILE = 32;     // columns per K5a tile
 
 __host__ __device__ __forceinline__ int ra_up4(int n) { return (n + 3) & ~3; }
-__host__ __device__ __forceinline__ unsigned ra_magic(int N) { return 0xFFFFFFFFu / (unsigned)N + 1u; }     // ceil(2^32 / N): p / N == umulhi(p, magic) for p < 2^14, 2 <= N <= 128
-__device__ __forceinline__ int ra_mod(int f, int N) { f %= N; return f < 0 ? f + N : f; }       // table entries are the caller's: keep every twiddle index inside the table
 
 // out[a][l] = sum_b in[b][l] e^{-+ 2 pi i F / N}; forward (INV = false): F = freq[a] b, inverse: F = freq[b] a.  in: LDS, rows of Lp = 4 k
 // complex; a thread owns columns l0 ... l0 + 3 of one output row and hands them to `store` (columns >= the row's length hold garbage)
@@ -263,29 +259,6 @@ __global__ __launch_bounds__(RA_THREADS) void resample3d_any_inv_plane_kernel(Re
             }
         }
     }
-}
-
-static int ra_cus() {
-    static int cus[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!cus[dev]) {
-        hipDeviceProp_t prop;
-        cus[dev] = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-    }
-    return usable_cus(cus[dev]);
-}
-
-// persistent grid: the usable CUs x the workgroups of RA_THREADS threads a CU holds beside each other at this LDS size (at most 8)
-static int ra_grid(long long n_items, size_t lds) {
-    const long long per_cu = std::max<long long>(1, std::min<long long>(8, (160 * 1024) / (long long)std::max<size_t>(lds, 1)));
-    return (int)std::max<long long>(1, std::min<long long>(n_items, (long long)ra_cus() * per_cu));
-}
-
-static int ra_check(const char* who) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("%s launch: %s", who, hipGetErrorString(e)); return -5; }
-    return 0;
 }
 
 int launch_resample3d_any(const float* x, float* y, float* y_act, int accumulate, void* ws, int n_vol, int D1, int D2, int D3, int M1, int M2, int M3, int J1,

@@ -332,6 +332,12 @@ int launch_cdft_generic(const CdftParams& p, bool inverse, hipStream_t s);
 int launch_resample3d_any(const float* x, float* y, float* y_act, int accumulate, void* ws, int n_vol, int D1, int D2, int D3, int M1, int M2, int M3, int J1,
                           const int* f1_in, const int* f1_out, int J2, const int* f2_in, const int* f2_out, int m3, float scale,
                           int herm_in, int herm_out, hipStream_t s);
+// resample3d_wide.hip: the same operator for complex axes of 2 ... 256 and a real axis of 2 ... 64, long-axis stages on the MFMA (arguments
+// validated by the caller, which also refuses what resample3d_wide_lds_bytes - K1w / K5w / K3w - puts beyond 160 KB)
+void resample3d_wide_lds_bytes(int D1, int D2, int D3, int M1, int M2, int M3, int J1, int J2, int m3, size_t out[3]);
+int launch_resample3d_wide(const float* x, float* y, float* y_act, int accumulate, void* ws, int n_vol, int D1, int D2, int D3, int M1, int M2, int M3,
+                           int J1, const int* f1_in, const int* f1_out, int J2, const int* f2_in, const int* f2_out, int m3, float scale,
+                           int herm_in, int herm_out, hipStream_t s);
 int launch_resample2d(const void* in, void* out, float* tmp, int n_img, int H, int W, int Ho, int Wo, const int* startH,
                       const float* wtH, int KH, const int* startW, const float* wtW, int KW, const int* tile_p0,
                       const float* tile_w, int NP, int accumulate, int bf16, hipStream_t s);

@@ -16,7 +16,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..integral_operators import (GradJoin, SpectrumShare, OperatorBlock_2D, OperatorBlock_3D, channel_mix, channel_mix_cat, channel_mix_cat_project,
-                                  enable_native_resample3d_any, enable_one_buffer_any_grid, gelu_channel_mix, gelu_channel_mix_pad, gelu_pad2d, gelu_project, gelu_project2,
+                                  enable_native_resample3d_any, enable_native_resample3d_wide, enable_one_buffer_any_grid, gelu_channel_mix, gelu_channel_mix_pad, gelu_pad2d, gelu_project, gelu_project2,
                                   lift_gelu_pad)
 
 
@@ -239,10 +239,16 @@ class Uno3D_T20(nn.Module):
     skip connections through (identity) trilinear resizes, time-axis padding int(pad * 0.1 * T).
     Input (B, S, S, T, 1) -> output (B, S, S, 2T, 1); in_width = 1 + 5 positional features.
 
-    The NS-3-D family is this class: `Uno3D_T10`, `Uno3D_T9` and `Uno3D_T40` contribute their table of blocks, the width of their
-    first lift layer and their plan of grids; constructor and forward pass are said here once."""
+    The NS-3-D family is this class: `Uno3D_T10`, `Uno3D_T9`, `Uno3D_T40` and the nine-block `Uno3D_T20_256` / `Uno3D_T10_256` contribute
+    their table of blocks, the width of their first lift layer and their plan of grids; constructor and forward pass are said here once."""
 
     _NAMES = ("conv0", "conv1", "conv2", "conv3", "conv6", "conv7", "conv8")
+    _NORMALIZED = ("conv0", "conv3", "conv7")
+    # output channels of every block but the last (which has 2 * width) in units of factor * width; a block's input channels are its
+    # predecessor's output plus what the predecessor's skip connection appends
+    _WIDTHS = (2, 4, 8, 16, 4, 2)
+    # block -> the earlier block whose output is appended to its own (None: the padded lift)
+    _SKIPS = {"conv6": "conv1", "conv7": "conv0", "conv8": None}
     # (dim1, dim2, dim3, modes1, modes2, modes3) of conv0 .. conv8: the default grids are overridden at call time, the modes are fixed
     _BLOCKS = ((48, 48, 10, 22, 22, 5), (32, 32, 10, 14, 14, 5), (16, 16, 12, 6, 6, 5), (16, 16, 12, 6, 6, 6), (32, 32, 18, 6, 6, 6),
                (48, 48, 20, 14, 14, 8), (64, 64, 20, 22, 22, 8))
@@ -263,10 +269,11 @@ class Uno3D_T20(nn.Module):
         lift = self._lift_width(in_width, w)
         self.fc = nn.Linear(in_width, lift)
         self.fc0 = nn.Linear(lift, w)
-        cin = (w, 2 * f * w, 4 * f * w, 8 * f * w, 16 * f * w, 8 * f * w, 4 * f * w)
-        cout = (2 * f * w, 4 * f * w, 8 * f * w, 16 * f * w, 4 * f * w, 2 * f * w, 2 * w)
-        for i, (name, row) in enumerate(zip(self._NAMES, self._BLOCKS)):
-            setattr(self, name, block_cls(cin[i], cout[i], *row, Normalize=name in ("conv0", "conv3", "conv7")))
+        cout = dict(zip(self._NAMES, [m * f * w for m in self._WIDTHS] + [2 * w]))
+        cin = w
+        for name, row in zip(self._NAMES, self._BLOCKS):
+            setattr(self, name, block_cls(cin, cout[name], *row, Normalize=name in self._NORMALIZED))
+            cin = cout[name] + (cout.get(self._SKIPS[name], w) if name in self._SKIPS else 0)
         self.fc1 = nn.Linear(3 * w, 4 * w)
         self.fc2 = nn.Linear(4 * w, 1)
         self._grid_cache = {}
@@ -294,16 +301,11 @@ class Uno3D_T20(nn.Module):
         self.padding = int(self.pad * 0.1 * lifted.shape[-1])
         lifted = F.pad(lifted, [self.padding, self.padding, 0, 0, 0, 0] if self.pad_both else [0, self.padding, 0, 0, 0, 0])
         g, crop = self._plan(*lifted.shape[-3:], self.padding)
-        c0 = self.conv0(lifted, *g[0])
-        c1 = self.conv1(c0, *g[1])
-        c2 = self.conv2(c1, *g[2])
-        c3 = self.conv3(c2, *g[3])
-        c6 = self.conv6(c3, *g[4])
-        c6 = torch.cat([c6, self._resize(c1, c6)], dim=1)
-        c7 = self.conv7(c6, *g[5])
-        c7 = torch.cat([c7, self._resize(c0, c7)], dim=1)
-        c8 = self.conv8(c7, *g[6])
-        c8 = torch.cat([c8, self._resize(lifted, c8)], dim=1)
+        outs, c8 = {None: lifted}, lifted
+        for name, grid in zip(self._NAMES, g):
+            c8 = outs[name] = getattr(self, name)(c8, *grid)
+            if name in self._SKIPS:
+                c8 = torch.cat([c8, self._resize(outs[self._SKIPS[name]], c8)], dim=1)
         if self.padding != 0:           # (the crop is written from `padding` as the reference writes it: -0 would empty the tensor)
             c8 = c8[..., crop:-crop] if self.pad_both else c8[..., :-crop]
         out = gelu_project(channel_mix(c8.contiguous(), self.fc1.weight, self.fc1.bias), self.fc2.weight, self.fc2.bias)
@@ -364,3 +366,52 @@ class Uno3D_T40(Uno3D_T20):
             enable_native_resample3d_any(self)
             if one_buffer_any:
                 enable_one_buffer_any_grid(self)
+
+
+class Uno3D_T20_256(Uno3D_T20):
+    """Navier-Stokes 3-D U-NO for 256 x 256 simulations, 10 input steps to 20 output steps - own counterpart of the reference's
+    `Uno3D_T20_256` (navier_stokes_uno3d.py:993-1181): nine blocks on grids D/4, D/16, D/32 (four times), D/16, D/4, D (4x contraction
+    and expansion per level, as the 2-D `UNO_S256`), modes up to (32, 32, 8), a lift of width // 2, normalisation on conv0, conv3,
+    conv5 and conv7, the time axis stretched 1.2 / 1.6 / 1.8 / 2 times and a `2 * padding` crop.  Input (B, S, S, T, 1) -> output
+    (B, S, S, 2T, 1).  At S = 256 its first and last layers resample (256,256,T) <-> (64,64,T), outside the pruned-DFT and the any-grid
+    kernels' ranges: on product blocks the model opts its point-wise layers into the any-grid and the wide-axis kernels, and with
+    `one_buffer_any=True` its blocks into the one-buffer form on those grids.  (The reference's `Uno3D_T40_256` and `Uno3D_T9_256` have
+    no counterpart: upstream the first cannot run a forward pass and the second cannot be constructed.)"""
+
+    _NAMES = ("conv0", "conv1", "conv2", "conv3", "conv4", "conv5", "conv6", "conv7", "conv8")
+    _NORMALIZED = ("conv0", "conv3", "conv5", "conv7")
+    _WIDTHS = (2, 4, 8, 16, 16, 8, 4, 2)
+    _BLOCKS = ((64, 64, 10, 32, 32, 5), (16, 16, 10, 8, 8, 5), (8, 8, 12, 4, 4, 5), (8, 8, 12, 4, 4, 6), (8, 8, 16, 4, 4, 6),
+               (8, 8, 16, 4, 4, 8), (16, 16, 18, 4, 4, 8), (64, 64, 20, 8, 8, 8), (256, 256, 20, 32, 32, 8))
+    _DIV = (4, 16, 32, 32, 32, 32, 16, 4, 1)        # output grid of conv0 .. conv8 as divisors of the padded grid (reference :1092-1128)
+
+    @staticmethod
+    def _lift_width(in_width, width):
+        return width // 2
+
+    @classmethod
+    def _plan(cls, d1, d2, d3, padding):
+        times = (d3, d3, int(d3 * 1.2), int(d3 * 1.2), int(d3 * 1.6), int(d3 * 1.6), int(d3 * 1.8), int(2.0 * d3), 2 * d3)
+        return [(d1 // k, d2 // k, t) for k, t in zip(cls._DIV, times)], 2 * padding
+
+    def __init__(self, in_width, width, pad=2, factor=1, pad_both=False, block_cls=OperatorBlock_3D, one_buffer_any=False):
+        super().__init__(in_width, width, pad, factor, pad_both, block_cls)
+        if issubclass(block_cls, OperatorBlock_3D):
+            enable_native_resample3d_any(self)
+            enable_native_resample3d_wide(self)
+            if one_buffer_any:
+                enable_one_buffer_any_grid(self)
+
+
+class Uno3D_T10_256(Uno3D_T20_256):
+    """Navier-Stokes 3-D U-NO for 256 x 256 simulations, 10 input steps to 10 output steps - own counterpart of the reference's
+    `Uno3D_T10_256` (navier_stokes_uno3d.py:1184-1372): `Uno3D_T20_256` with 5 / 4 time modes, a time axis that shrinks to
+    int(0.8 * d3) through the five inner blocks and returns to d3, and a `padding` crop.  Input (B, S, S, T, 1) -> output (B, S, S, T, 1)."""
+
+    _BLOCKS = ((64, 64, 10, 32, 32, 5), (16, 16, 10, 8, 8, 4), (8, 8, 8, 4, 4, 4), (8, 8, 8, 4, 4, 4), (8, 8, 8, 4, 4, 4),
+               (8, 8, 8, 4, 4, 4), (16, 16, 8, 4, 4, 4), (64, 64, 10, 8, 8, 4), (256, 256, 10, 32, 32, 5))
+
+    @classmethod
+    def _plan(cls, d1, d2, d3, padding):
+        times = (d3, d3) + (int(0.8 * d3),) * 5 + (d3, d3)
+        return [(d1 // k, d2 // k, t) for k, t in zip(cls._DIV, times)], padding

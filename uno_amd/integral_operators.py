@@ -32,10 +32,10 @@ from .block2d import SpectrumShare, _OperatorBlock2dCatFn, _OperatorBlock2dFn, _
 from .pointwise import (GradJoin, _dev_act, channel_mix, channel_mix_cat, channel_mix_cat_project, gelu_channel_mix, gelu_channel_mix_pad,
                         gelu_pad2d, gelu_project, gelu_project2, instance_norm_gelu, lift_gelu_pad)
 from .resample import resample2d_bicubic_aa
-from .spectral3d import (_FftResample3dAnyFn, _FftResample3dFn, _OperatorBlock3dFn, _resample3d_plan, _resample3d_plan_any, spectral_conv3d)
+from .spectral3d import (RESAMPLE3D_FAMILIES, _OperatorBlock3dFn, _resample3d_plan, _resample3d_plan_any, _resample3d_plan_wide, spectral_conv3d)
 
 __all__ = [
-    "enable_mixed_precision", "enable_native_resample3d_any", "enable_one_buffer_any_grid", "GradJoin", "SpectrumShare", "channel_mix_cat_project", "release_pass_state",
+    "enable_mixed_precision", "enable_native_resample3d_any", "enable_native_resample3d_wide", "enable_one_buffer_any_grid", "GradJoin", "SpectrumShare", "channel_mix_cat_project", "release_pass_state",
     "SpectralConv1d_Uno", "pointwise_op_1D", "OperatorBlock_1D",
     "SpectralConv2d_Uno", "pointwise_op_2D", "OperatorBlock_2D",
     "SpectralConv3d_Uno", "pointwise_op_3D", "OperatorBlock_3D",
@@ -263,15 +263,39 @@ def enable_native_resample3d_any(module: nn.Module, enabled: bool = True) -> nn.
     return module
 
 
+# ... and on a grid neither family takes, with the two leading axes in 2 ... 256 and the last in 2 ... 64 (resample3d_wide_applies): True - run
+# the wide-axis HIP kernels (uno_fft_resample3d_wide: the long-axis sums on the f32 MFMA).  Opt-in in the same way: per module the attribute
+# `native_wide_grid` (enable_native_resample3d_wide).  A zero-edit user of the reference's Uno3D_T20_256 / Uno3D_T10_256 sets this switch
+# (and, for pad 3 on both sides, NATIVE_RESAMPLE3D_ANY): their first and last layers resample (256,256,T) <-> (64,64,T).
+NATIVE_RESAMPLE3D_WIDE = False
+
+
+def enable_native_resample3d_wide(module: nn.Module, enabled: bool = True) -> nn.Module:
+    """Let every pointwise_op_3D under `module` run grids outside the older kernel families' ranges on the wide-axis HIP kernels (sets
+    `native_wide_grid`); a grid the pruned-DFT kernels - or, where opted in, the any-grid kernels - take keeps that family."""
+    for m in module.modules():
+        if isinstance(m, pointwise_op_3D):
+            m.native_wide_grid = bool(enabled)
+    return module
+
+
 def _resample3d_kernels(w, din, dout, device):
-    """Which resample kernels the point-wise layer `w` takes for din -> dout: (plan, any_grid) - the pruned-DFT plan (any_grid False),
-    inside its range; outside it the any-grid plan (True) where the layer is opted in and resample3d_any_applies holds; else
-    (None, False)."""
+    """Which resample kernels the point-wise layer `w` takes for din -> dout: (plan, family).  The families are tried in order - "pruned"
+    inside its range; then "any" where the layer is opted in (`native_any_grid` / NATIVE_RESAMPLE3D_ANY) and resample3d_any_applies
+    holds; then "wide" where it is opted in (`native_wide_grid` / NATIVE_RESAMPLE3D_WIDE) and resample3d_wide_applies holds - so a grid
+    an older family takes keeps that family; else (None, None)."""
     plan = _resample3d_plan(din, dout, device)
-    if plan is None and (getattr(w, "native_any_grid", False) or NATIVE_RESAMPLE3D_ANY):
+    if plan is not None:
+        return plan, "pruned"
+    if getattr(w, "native_any_grid", False) or NATIVE_RESAMPLE3D_ANY:
         plan = _resample3d_plan_any(din, dout, device)
-        return plan, plan is not None
-    return plan, False
+        if plan is not None:
+            return plan, "any"
+    if getattr(w, "native_wide_grid", False) or NATIVE_RESAMPLE3D_WIDE:
+        plan = _resample3d_plan_wide(din, dout, device)
+        if plan is not None:
+            return plan, "wide"
+    return None, None
 
 
 class pointwise_op_3D(nn.Module):
@@ -281,7 +305,7 @@ class pointwise_op_3D(nn.Module):
     integral_operators.py:430-468.  The convolution runs on the channel-mix kernels (K8 / K9) for float32 device
     tensors - MIOpen executes a 1x1x1 Conv3d with its naive direct kernels, 0.9 s of a 2.2 s first NS-3D step - the
     FFT resampling runs on the pruned-DFT kernels (_FftResample3dFn; outside their shape range the layer runs the any-grid kernels where
-    `native_any_grid` / NATIVE_RESAMPLE3D_ANY opts in, else raises unless STOCK_FFT_RESAMPLE3D allows torch.fft); the trilinear resize to the size the tensor already has is an exact
+    `native_any_grid` / NATIVE_RESAMPLE3D_ANY or the wide-axis kernels where `native_wide_grid` / NATIVE_RESAMPLE3D_WIDE opts in, else raises unless STOCK_FFT_RESAMPLE3D allows torch.fft); the trilinear resize to the size the tensor already has is an exact
     identity under align_corners=True and is skipped on the device."""
 
     def __init__(self, in_codim, out_codim, dim1, dim2, dim3):
@@ -307,9 +331,9 @@ class pointwise_op_3D(nn.Module):
         on_device = x.is_cuda and x.dtype == torch.float32 and x.dim() == 5
         out = channel_mix(x.contiguous(), self.conv.weight, self.conv.bias) if on_device else self.conv(x)
         if on_device:
-            plan, any_grid = _resample3d_kernels(self, out.shape[-3:], (dim1, dim2, dim3), out.device)
+            plan, family = _resample3d_kernels(self, out.shape[-3:], (dim1, dim2, dim3), out.device)
             if plan is not None:
-                return (_FftResample3dAnyFn if any_grid else _FftResample3dFn).apply(out, (dim1, dim2, dim3), plan)
+                return RESAMPLE3D_FAMILIES[family][0].apply(out, (dim1, dim2, dim3), plan)
         if on_device and not STOCK_FFT_RESAMPLE3D:
             # no silent dispatch to a stock library from a product component: the pruned-DFT resampling kernels do not cover this grid
             raise RuntimeError(
@@ -317,7 +341,9 @@ class pointwise_op_3D(nn.Module):
                 "pruned-DFT kernels (they take an even number of kept rows per complex axis - at most 80 / 48 - and (W, T) planes of at most "
                 "1792 elements with T <= 64); set uno_amd.integral_operators.STOCK_FFT_RESAMPLE3D = True to run this layer's resampling "
                 "through torch.fft (rocFFT) instead, or - for axis lengths of 2 ... 128 - uno_amd.integral_operators.NATIVE_RESAMPLE3D_ANY = True "
-                "(enable_native_resample3d_any(model) for one model) to run it on the any-grid HIP kernels")
+                "(enable_native_resample3d_any(model) for one model) to run it on the any-grid HIP kernels, or - for leading axes of 2 ... 256 "
+                "and a last axis of 2 ... 64 - uno_amd.integral_operators.NATIVE_RESAMPLE3D_WIDE = True (enable_native_resample3d_wide(model)) "
+                "to run it on the wide-axis HIP kernels")
         spec = torch.fft.rfftn(out, dim=[-3, -2, -1])
         h1, h2, h3 = dim1 // 2, dim2 // 2, dim3 // 2
         if on_device:
@@ -334,7 +360,8 @@ class pointwise_op_3D(nn.Module):
 
 ONE_BUFFER_3D = True        # OperatorBlock_3D in one buffer (_OperatorBlock3dFn); False: the two branches and stock sum / GELU (A/B switch)
 # ... and on a grid outside the pruned-DFT range whose point-wise layer runs the any-grid kernels: True - the same one-buffer form with
-# uno_fft_resample3d_any_acc as its last transform.  Opt-in like NATIVE_RESAMPLE3D_ANY: the default (False) leaves every block on the two
+# uno_fft_resample3d_any_acc as its last transform - or, where the layer runs the wide-axis kernels (`native_wide_grid` /
+# NATIVE_RESAMPLE3D_WIDE), uno_fft_resample3d_wide_acc.  Opt-in like NATIVE_RESAMPLE3D_ANY: the default (False) leaves every block on the two
 # branches there; a single block opts in through its `one_buffer_any_grid` attribute (enable_one_buffer_any_grid).
 ONE_BUFFER_3D_ANY = False
 
@@ -380,8 +407,8 @@ class OperatorBlock_3D(nn.Module):
     def _fused(self, x, dim1, dim2, dim3):
         """(conv(x) + w(x) [activated], whether the GELU has been applied) through the one-buffer form, or None when the layer has to take
         the two branches separately (CPU tensors, other dtypes, mismatched grids, grids outside the pruned-DFT resampling kernels' range
-        unless the block is opted into the one-buffer form on the any-grid kernels - `one_buffer_any_grid` / ONE_BUFFER_3D_ANY with the
-        point-wise layer's `native_any_grid` / NATIVE_RESAMPLE3D_ANY - and resample3d_any_applies holds)."""
+        unless the block is opted into the one-buffer form there - `one_buffer_any_grid` / ONE_BUFFER_3D_ANY - and its point-wise layer
+        into the any-grid or the wide-axis kernels, see _resample3d_kernels)."""
         conv, w = self.conv, self.w
         if not (ONE_BUFFER_3D and x.is_cuda and x.dtype == torch.float32 and x.dim() == 5 and x.shape[1] == conv.in_channels
                 and w.conv.weight.dtype == torch.float32):
@@ -393,14 +420,14 @@ class OperatorBlock_3D(nn.Module):
             if (conv.dim1, conv.dim2, conv.dim3) != dims:
                 return None
         din = tuple(x.shape[-3:])
-        plan, any_grid = _resample3d_kernels(w, din, dims, x.device)
-        if plan is None or (any_grid and not (getattr(self, "one_buffer_any_grid", False) or ONE_BUFFER_3D_ANY)):
+        plan, family = _resample3d_kernels(w, din, dims, x.device)
+        if plan is None or (family != "pruned" and not (getattr(self, "one_buffer_any_grid", False) or ONE_BUFFER_3D_ANY)):
             return None
         if dim1 is not None:
             conv.dim1, conv.dim2, conv.dim3 = dim1, dim2, dim3
         gelu = self.non_lin and not self.normalize
         out = _OperatorBlock3dFn.apply(x, conv.weights1, conv.weights2, conv.weights3, conv.weights4, w.conv.weight, w.conv.bias,
-                                       dims, plan, gelu, any_grid)
+                                       dims, plan, gelu, family)
         return out, gelu
 
 

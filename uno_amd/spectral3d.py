@@ -1,7 +1,7 @@
 """3-D spectral convolution on the HIP path (SpectralConv3d_Uno.forward, reference
 integral_operators.py:385-427): rfftn over (H, W, T) restricted to the four low-frequency corners ->
 per-mode channel mixing with weights1..4 -> zero-padded irfftn, with a custom autograd adjoint that
-saves only the truncated input spectrum.  Also pointwise_op_3D's FFT resampling on the pruned-DFT and the any-grid kernels
+saves only the truncated input spectrum.  Also pointwise_op_3D's FFT resampling on the pruned-DFT, the any-grid and the wide-axis kernels
 (plans + Functions) and the 3-D operator block in one buffer."""
 from __future__ import annotations
 
@@ -81,16 +81,33 @@ def resample3d_any_applies(din, dout) -> bool:
     return len(k1) >= 1 and len(k2) >= 1 and 1 <= _modes3(din, dout) <= din[2] // 2 + 1
 
 
+RESAMPLE3D_WIDE_MAX_AXIS = 256      # the wide-axis kernels: the two leading (complex) axes in 2 ... 256 ...
+RESAMPLE3D_WIDE_MAX_LAST = 64       # ... and the last (real) axis in 2 ... 64
+
+
+def resample3d_wide_applies(din, dout) -> bool:
+    """True when the wide-axis kernels (uno_fft_resample3d_wide) take the FFT crop / resample din -> dout: leading axes of 2 ... 256 and a
+    last axis of 2 ... 64 (then every kept-row count is in 1 ... 256 and modes3 <= 32, which keeps the kernels' LDS need inside a CU's:
+    the entry point's own refusal needs the 33 bins only a hand-made call can ask for).  A host predicate: no device, no library call."""
+    din, dout = tuple(int(v) for v in din), tuple(int(v) for v in dout)
+    if len(din) != 3 or len(dout) != 3 or not all(2 <= v <= RESAMPLE3D_WIDE_MAX_AXIS for v in (*din[:2], *dout[:2])) \
+            or not all(2 <= v <= RESAMPLE3D_WIDE_MAX_LAST for v in (din[2], dout[2])):
+        return False
+    k1, k2 = _kept_indices(din[0], dout[0]), _kept_indices(din[1], dout[1])
+    return len(k1) >= 1 and len(k2) >= 1 and 1 <= _modes3(din, dout) <= din[2] // 2 + 1
+
+
 _RESAMPLE3D_PLANS = {}
+_FAMILY_APPLIES = {"pruned": _resample3d_pruned_applies, "any": resample3d_any_applies, "wide": resample3d_wide_applies}
 
 
-def _cached_plan(any_grid: bool, din, dout, device):
-    """(f1, f2, m3) of the kernel family for din -> dout, or None outside its range (no device is touched then); the tables are cached
-    per (family, grids, device)."""
-    key = (any_grid, tuple(din), tuple(dout), str(device))
+def _cached_plan(family: str, din, dout, device):
+    """(f1, f2, m3) of the kernel family ("pruned" | "any" | "wide") for din -> dout, or None outside its range (no device is touched
+    then); the tables are cached per (family, grids, device)."""
+    key = (family, tuple(din), tuple(dout), str(device))
     if key not in _RESAMPLE3D_PLANS:
         plan = None
-        if (resample3d_any_applies if any_grid else _resample3d_pruned_applies)(din, dout):
+        if _FAMILY_APPLIES[family](din, dout):
             t1 = _native.table_to_device(torch.tensor(_kept_indices(din[0], dout[0]), dtype=torch.int32), device)
             t2 = _native.table_to_device(torch.tensor(_kept_indices(din[1], dout[1]), dtype=torch.int32), device)
             plan = (t1, t2, _modes3(din, dout))
@@ -101,12 +118,17 @@ def _cached_plan(any_grid: bool, din, dout, device):
 def _resample3d_plan(din, dout, device):
     """(f1, f2, m3) for _native.fft_resample3d, or None when the shape is outside the kernels' range (odd row counts, too many
     rows or bins, planes too large): the caller then takes the any-grid kernels (_resample3d_plan_any) where it is opted in."""
-    return _cached_plan(False, din, dout, device)
+    return _cached_plan("pruned", din, dout, device)
 
 
 def _resample3d_plan_any(din, dout, device):
     """(f1, f2, m3) for _native.fft_resample3d_any, or None when resample3d_any_applies says no."""
-    return _cached_plan(True, din, dout, device)
+    return _cached_plan("any", din, dout, device)
+
+
+def _resample3d_plan_wide(din, dout, device):
+    """(f1, f2, m3) for _native.fft_resample3d_wide, or None when resample3d_wide_applies says no."""
+    return _cached_plan("wide", din, dout, device)
 
 
 class _FftResample3dFn(torch.autograd.Function):
@@ -134,21 +156,34 @@ class _FftResample3dAnyFn(_FftResample3dFn):
     resample = staticmethod(_native.fft_resample3d_any)
 
 
+class _FftResample3dWideFn(_FftResample3dFn):
+    """_FftResample3dFn on the wide-axis kernels (K1w, K5w, K3w: leading axes of 2 ... 256, long-axis sums on the MFMA)."""
+    resample = staticmethod(_native.fft_resample3d_wide)
+
+
+# kernel family -> (autograd Function of the resample alone, library call); _OperatorBlock3dFn takes the family's name
+RESAMPLE3D_FAMILIES = {
+    "pruned": (_FftResample3dFn, _native.fft_resample3d),
+    "any": (_FftResample3dAnyFn, _native.fft_resample3d_any),
+    "wide": (_FftResample3dWideFn, _native.fft_resample3d_wide),
+}
+
+
 class _OperatorBlock3dFn(torch.autograd.Function):
     """s = SpectralConv3d_Uno(x) + pointwise_op_3D(x) in ONE buffer (reference integral_operators.py:506-512: `x1_out = self.conv(...);
     x2_out = self.w(...); x_out = x1_out + x2_out`, then F.gelu for blocks without normalisation).
 
     The spectral branch's inverse transform writes s; the point-wise branch - 1x1x1 convolution (K8), then the reference's FFT crop /
     resample on the pruned-DFT kernels - ends in a plane-batched inverse transform that ACCUMULATES into s and, for a block whose sum is
-    followed directly by the GELU, writes the activation in the same pass (uno_fft_resample3d_acc; with `any_grid`, a plan of
-    _resample3d_plan_any: the any-grid kernels and uno_fft_resample3d_any_acc).  Backward: the spectral branch
+    followed directly by the GELU, writes the activation in the same pass (uno_fft_resample3d_acc; `family` "any" / "wide" with a plan of
+    _resample3d_plan_any / _resample3d_plan_wide: uno_fft_resample3d_any_acc / uno_fft_resample3d_wide_acc).  Backward: the spectral branch
     writes grad_x, the transposed 1x1x1 convolution accumulates into it.  The element-wise sum (three passes over the output), the
     GELU (two) and autograd's sum of the two input gradients (three over the input) are gone."""
 
     @staticmethod
-    def forward(ctx, x, w1, w2, w3, w4, cw, cb, dims, plan, fuse_gelu, any_grid):
+    def forward(ctx, x, w1, w2, w3, w4, cw, cb, dims, plan, fuse_gelu, family):
         ctx.leaves = (cw, cb)
-        resample = _native.fft_resample3d_any if any_grid else _native.fft_resample3d
+        resample = RESAMPLE3D_FAMILIES[family][1]
         x = _plain(x)
         ws = [_plain(w) for w in (w1, w2, w3, w4)]
         B, Ci = x.shape[0], x.shape[1]
