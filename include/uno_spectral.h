@@ -652,6 +652,41 @@ long long uno_channel_mix_ws_bytes(int Ci, int Co, long long P, int bf16);
 int uno_transpose_batched(const float* in, float* out, int B, long long R, int C, long long ld_in, long long sb_in,
                           long long ld_out, long long sb_out, void* stream);
 
+/* Short-row windows (additive, ABI 14): the two ends of the NS-3D models on (B, C, H, W, Tp) tensors without the concatenation, the
+ * time-axis crop, the separate GELU and the time-axis padding.  A window is rows x cols logical pixels; logical pixel (r, c) lives at
+ * element r * pitch + col0 + c of its channel plane and planes are `plane` >= rows * pitch elements apart (rows = H * W, pitch = Tp).
+ * Accepted: 1 <= cols, 0 <= col0, col0 + cols <= pitch <= 256 (any parity), rows * pitch < 2^24, 1 <= C1 <= Ci <= 1024, 1 <= Co;
+ * anything else returns a negative code with a message naming these limits before any launch.  B == 0 or rows == 0: a successful
+ * no-op (nothing is written).  float32; no allocation, no synchronisation, no table: capturable on the first call; the launch geometry
+ * is a function of the shape alone (not of uno_reserve_cus or the sweep direction) and no result depends on what the outputs held. */
+/* y (B, Co, rows * cols) dense = w (Co, Ci) . cat([gelu](x1), x2) + bias with x1 (B, C1, plane), x2 (B, Ci - C1, plane) read through
+ * the window and nothing outside it (x2 == NULL: one source of Ci channels).  Replaces `torch.cat([x_c8, x_fc0], dim=1)`, the crop
+ * `x_c8[..., :-self.padding]` and `self.fc1` of the reference (navier_stokes_uno3d.py:358-382; the `[padding:-padding]` form of :566-570). */
+int uno_channel_mix2_rows(const float* x1, const float* x2, int C1, const float* w, const float* bias, float* y, int B, int Ci, int Co,
+                          int rows, int cols, int pitch, int col0, long long plane, int act_in, void* stream);
+/* Backward of the above for the sources (what autograd does for navier_stokes_uno3d.py:358-382: zero-fill, slice copy, two narrowing
+ * copies): gy (B, Co, rows * cols) dense -> g1 (B, C1, plane) and g2 (B, Ci - C1, plane; NULL: not wanted) = w^T gy inside the window
+ * and +0.0f in the border columns, the first rows * pitch elements of every plane from ONE pass (elements beyond are not touched by
+ * this call; the Python binding, which allocates g1 / g2 itself, zero-fills such a tail).
+ * dgelu_of (B, C1, plane; NULL: none): g1 is multiplied by gelu'(dgelu_of) on the window (the act_in form). */
+int uno_channel_mix2_rows_grad(const float* gy, const float* w, int C1, const float* dgelu_of, float* g1, float* g2, int B, int Ci,
+                               int Co, int rows, int cols, int pitch, int col0, long long plane, void* stream);
+/* Weight / bias gradient of the same layer (fc1 of navier_stokes_uno3d.py:380): gw (Co, Ci), gb (Co) or NULL from gy dense and the
+ * windowed sources; the contract of uno_channel_wgrad2 (two stages, fixed summation order, no atomics; accumulate = 1 adds to gw / gb);
+ * ws: uno_channel_wgrad_ws_bytes(B, Ci, Co, rows * cols) bytes. */
+int uno_channel_wgrad2_rows(const float* gy, const float* x1, const float* x2, int C1, float* gw, float* gb, void* ws, int B, int Ci,
+                            int Co, int rows, int cols, int pitch, int col0, long long plane, int act_x, int accumulate, void* stream);
+/* The time-axis form of uno_channel_mix_act_padded - `x_fc0 = self.fc0(x_fc)`, `F.gelu(x_fc0)` and `F.pad(x_fc0, [0, self.padding, ...])`
+ * of the reference (navier_stokes_uno3d.py:304-318) from the layer's own store: x (B, Ci, rows * cols) dense -> y (B, Co, rows * cols)
+ * = w . [gelu](x) + bias (NULL: not kept) and y_act (B, Co, rows * pitch) = gelu(y) at columns [col0, col0 + cols) of every row,
+ * +0.0f left and right of them. */
+int uno_channel_mix_act_padded_rows(const float* x, const float* w, const float* bias, float* y, float* y_act, int B, int Ci, int Co,
+                                    int rows, int cols, int pitch, int col0, int act_in, void* stream);
+/* gz (n_planes, rows * cols) dense = gelu'(pre) * g_padded[window], pre dense, g_padded (n_planes, plane): the backward of the padding
+ * and the GELU of navier_stokes_uno3d.py:306-318; the layer's own gradients follow from uno_channel_mix / uno_channel_wgrad on gz. */
+int uno_dgelu_rows(const float* pre, const float* g_padded, float* gz, long long n_planes, int rows, int cols, int pitch, int col0,
+                   long long plane, void* stream);
+
 /* Optional in-library kernel timing (HIP events recorded on the launch stream around every kernel
  * this library enqueues), used by bench.py for the live roofline figure.
  *   uno_profile_begin(max_records): start recording (drops records beyond max_records).

@@ -130,6 +130,11 @@ _SIGNATURES = {
     "uno_gelu_pad_bf16": (C.c_int, [_fp, _fp, _fp] + [_i] * 6 + [_fp]),
     "uno_instnorm_forward_bf16": (C.c_int, [_fp] * 6 + [C.c_longlong, _i, C.c_longlong, C.c_float, _i, _fp]),
     "uno_instnorm_backward_bf16": (C.c_int, [_fp] * 9 + [C.c_longlong, _i, C.c_longlong, _i, _fp]),
+    "uno_channel_mix2_rows": (C.c_int, [_fp, _fp, _i, _fp, _fp, _fp] + [_i] * 7 + [C.c_longlong, _i, _fp]),
+    "uno_channel_mix2_rows_grad": (C.c_int, [_fp, _fp, _i, _fp, _fp, _fp] + [_i] * 7 + [C.c_longlong, _fp]),
+    "uno_channel_wgrad2_rows": (C.c_int, [_fp, _fp, _fp, _i, _fp, _fp, _fp] + [_i] * 7 + [C.c_longlong, _i, _i, _fp]),
+    "uno_channel_mix_act_padded_rows": (C.c_int, [_fp] * 5 + [_i] * 8 + [_fp]),
+    "uno_dgelu_rows": (C.c_int, [_fp, _fp, _fp, C.c_longlong, _i, _i, _i, _i, C.c_longlong, _fp]),
     "uno_profile_begin": (C.c_int, [_i]),
     "uno_profile_end": (C.c_int, []),
     "uno_profile_get": (C.c_int, [_i, C.c_char_p, _i, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
@@ -1001,6 +1006,120 @@ def channel_wgrad2(gy, x1, x2, need_bias: bool = True, act_x: bool = False, out_
                 _ptr(ws), B, Ci, Co, *size, 1 if act_x else 0, 1 if accumulate else 0, _stream(gy))
     _check(rc, "uno_channel_wgrad2")
     return gw, gb
+
+
+def rows_window_ok(rows: int, cols: int, pitch: int, col0: int, plane: int, Ci: int = 1, Co: int = 1) -> bool:
+    """the accepted range of the short-row window entry points (uno_spectral.h: uno_channel_mix2_rows and its family)"""
+    return (rows >= 0 and cols >= 1 and col0 >= 0 and col0 + cols <= pitch <= 256 and rows * pitch < (1 << 24) and plane >= rows * pitch
+            and 1 <= Ci <= 1024 and Co >= 1)
+
+
+def _rows_args(window, plane: int):
+    rows, cols, pitch, col0 = (int(v) for v in window)
+    return rows, cols, pitch, col0, int(plane)
+
+
+def channel_mix2_rows(x1, x2, w, bias, window, act_in: bool = False):
+    """uno_channel_mix2_rows: x1 (B, C1, plane), x2 (B, C2, plane) or None read through window = (rows, cols, pitch, col0), w (Co, C1 + C2)
+    -> y (B, Co, rows * cols) dense = w . cat([gelu](x1), x2) + bias."""
+    for t, n in ((x1, "x1"), (w, "weight")) + (((x2, "x2"),) if x2 is not None else ()) + (((bias, "bias"),) if bias is not None else ()):
+        _require(t, torch.float32, n)
+    B, C1, plane = x1.shape
+    Ci = C1 + (x2.shape[1] if x2 is not None else 0)
+    Co = w.shape[0]
+    if w.shape[1] != Ci or (x2 is not None and (x2.shape[0] != B or x2.shape[2] != plane)):
+        raise RuntimeError("uno_amd: weight / sources of a short-row layer disagree")
+    geo = _rows_args(window, plane)
+    y = torch.empty((B, Co, geo[0] * geo[1]), dtype=torch.float32, device=x1.device)
+    with torch.cuda.device(x1.device):
+        rc = lib().uno_channel_mix2_rows(_ptr(x1), _opt(x2), C1, _ptr(w), _opt(bias), _ptr(y), B, Ci, Co, *geo, 1 if act_in else 0, _stream(x1))
+    _check(rc, "uno_channel_mix2_rows")
+    return y
+
+
+def channel_mix2_rows_grad(gy, w, C1: int, window, plane: int, need_g2: bool = True, dgelu_of=None):
+    """uno_channel_mix2_rows_grad: gy (B, Co, rows * cols) dense -> (g1 (B, C1, plane), g2 (B, Ci - C1, plane) or None): w^T gy inside
+    the window, +0 in the border columns of the first rows * pitch elements of every plane; what lies beyond is zeroed here (plane >
+    rows * pitch does not occur in the models)."""
+    _require(gy, torch.float32, "grad_output")
+    _require(w, torch.float32, "weight")
+    B, Co, _ = gy.shape
+    Ci = w.shape[1]
+    geo = _rows_args(window, plane)
+    whole = geo[0] * geo[2] == plane
+    g1 = torch.empty((B, C1, plane), dtype=torch.float32, device=gy.device)
+    g2 = torch.empty((B, Ci - C1, plane), dtype=torch.float32, device=gy.device) if (need_g2 and Ci > C1) else None
+    if not whole:
+        for t in (g1, g2):
+            if t is not None:
+                t[:, :, geo[0] * geo[2]:].zero_()
+    if dgelu_of is not None:
+        _require(dgelu_of, torch.float32, "dgelu_of")
+        if tuple(dgelu_of.shape) != (B, C1, plane):
+            raise RuntimeError("uno_amd: dgelu_of does not match the first source")
+    with torch.cuda.device(gy.device):
+        rc = lib().uno_channel_mix2_rows_grad(_ptr(gy), _ptr(w), C1, _opt(dgelu_of), _ptr(g1), _opt(g2), B, Ci, Co, *geo, _stream(gy))
+    _check(rc, "uno_channel_mix2_rows_grad")
+    return g1, g2
+
+
+def channel_wgrad2_rows(gy, x1, x2, window, need_bias: bool = True, act_x: bool = False, out_w=None, out_b=None, accumulate: bool = False):
+    """uno_channel_wgrad2_rows: gy (B, Co, rows * cols) dense, x1 / x2 on the window -> gw (Co, Ci), gb (Co) or None; out_w / out_b /
+    accumulate as channel_wgrad2."""
+    for t, n in ((gy, "grad_output"), (x1, "x1")) + (((x2, "x2"),) if x2 is not None else ()):
+        _require(t, torch.float32, n)
+    B, Co, _ = gy.shape
+    C1, plane = x1.shape[1], x1.shape[2]
+    Ci = C1 + (x2.shape[1] if x2 is not None else 0)
+    geo = _rows_args(window, plane)
+    gw, gb, accumulate = _real_grad_buffers(out_w, out_b, Ci, Co, need_bias, gy.device, accumulate)
+    if B == 0 or geo[0] == 0:
+        if not accumulate:
+            gw.zero_()
+            if gb is not None:
+                gb.zero_()
+        return gw, gb
+    L = lib()
+    with torch.cuda.device(gy.device):
+        ws = torch.empty(max(1, L.uno_channel_wgrad_ws_bytes(B, Ci, Co, geo[0] * geo[1])), dtype=torch.uint8, device=gy.device)
+        rc = L.uno_channel_wgrad2_rows(_ptr(gy), _ptr(x1), _opt(x2), C1, _ptr(gw), _opt(gb), _ptr(ws), B, Ci, Co, *geo,
+                                       1 if act_x else 0, 1 if accumulate else 0, _stream(gy))
+    _check(rc, "uno_channel_wgrad2_rows")
+    return gw, gb
+
+
+def channel_mix_act_padded_rows(x, w, bias, window, act_in: bool = False, keep_y: bool = True):
+    """uno_channel_mix_act_padded_rows: x (B, Ci, rows * cols) dense, window = (rows, cols, pitch, col0) -> y (B, Co, rows * cols) =
+    w . [gelu](x) + bias (None with keep_y=False) and act (B, Co, rows * pitch) = gelu(y) in columns [col0, col0 + cols), zero elsewhere."""
+    for t, n in ((x, "x"), (w, "weight")) + (((bias, "bias"),) if bias is not None else ()):
+        _require(t, torch.float32, n)
+    B, Ci, P = x.shape
+    Co = w.shape[0]
+    rows, cols, pitch, col0 = (int(v) for v in window)
+    if w.shape[1] != Ci or rows * cols != P:
+        raise RuntimeError("uno_amd: weight / window do not match the layer")
+    y = torch.empty((B, Co, P), dtype=torch.float32, device=x.device) if keep_y else None
+    act = torch.empty((B, Co, rows * pitch), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = lib().uno_channel_mix_act_padded_rows(_ptr(x), _ptr(w), _opt(bias), _opt(y), _ptr(act), B, Ci, Co, rows, cols, pitch, col0,
+                                                   1 if act_in else 0, _stream(x))
+    _check(rc, "uno_channel_mix_act_padded_rows")
+    return y, act
+
+
+def dgelu_rows(pre, g_padded, window):
+    """uno_dgelu_rows: pre (B, C, rows * cols) dense, g_padded (B, C, plane) -> gz = gelu'(pre) * g_padded[window], dense."""
+    _require(pre, torch.float32, "pre-activation")
+    _require(g_padded, torch.float32, "grad_output")
+    B, Cc, P = pre.shape
+    geo = _rows_args(window, g_padded.shape[2])
+    if tuple(g_padded.shape[:2]) != (B, Cc) or geo[0] * geo[1] != P:
+        raise RuntimeError("uno_amd: grad_output / window do not match the pre-activation")
+    gz = torch.empty_like(pre)
+    with torch.cuda.device(pre.device):
+        rc = lib().uno_dgelu_rows(_ptr(pre), _ptr(g_padded), _ptr(gz), B * Cc, *geo, _stream(pre))
+    _check(rc, "uno_dgelu_rows")
+    return gz
 
 
 def channel_wgrad(gy, x, need_bias: bool = True, act_x: bool = False):

@@ -18,6 +18,22 @@ import torch.nn.functional as F
 from ..integral_operators import (GradJoin, SpectrumShare, OperatorBlock_2D, OperatorBlock_3D, channel_mix, channel_mix_cat, channel_mix_cat_project,
                                   enable_native_resample3d_any, enable_native_resample3d_wide, enable_one_buffer_any_grid, gelu_channel_mix, gelu_channel_mix_pad, gelu_pad2d, gelu_project, gelu_project2,
                                   lift_gelu_pad)
+from ..pointwise import gelu_channel_mix_pad_last
+
+# The two ends of the NS-3D models on the short-row window kernels (csrc/channel_mix_rows.hip): the lift's second layer writes its padded
+# activation itself (no F.gelu / F.pad passes) and fc1 reads conv8's output and the resized lift where they lie, through the time window
+# the crop keeps (no last skip concatenation, no cropped copy; whole-plane gradients from one backward launch).  Opt-in: the default
+# (False) leaves every model on the stock ops bit for bit; a single model opts in through its `native_ends` attribute
+# (enable_native_ends_3d).  Product blocks on device tensors only.
+NATIVE_ENDS_3D = False
+
+
+def enable_native_ends_3d(model: nn.Module, enabled: bool = True) -> nn.Module:
+    """Opt the NS-3D models inside `model` into the short-row window kernels for their lift and head (sets `native_ends`)."""
+    for m in model.modules():
+        if isinstance(m, Uno3D_T20):
+            m.native_ends = bool(enabled)
+    return model
 
 
 def _block_cat(block, xs, *dims):
@@ -288,6 +304,13 @@ class Uno3D_T20(nn.Module):
             return torch.cat((torch.sin(gx), torch.sin(gy), torch.cos(gx), torch.cos(gy), gz), dim=-1).contiguous().to(device)
         return _cached(self._grid_cache, (tuple(shape[:4]), str(device)), build)
 
+    native_ends = False         # enable_native_ends_3d: lift and head on the short-row window kernels
+
+    def _native_ends(self, x):
+        """the opted-in ends apply: switch or attribute on, product blocks, device tensors"""
+        return bool((NATIVE_ENDS_3D or self.native_ends) and x.is_cuda and x.dtype == torch.float32
+                    and isinstance(getattr(self, self._NAMES[-1]), OperatorBlock_3D))
+
     @staticmethod
     def _resize(t, like):
         # the reference resizes every skip tensor with trilinear / align_corners (navier_stokes_uno3d.py:352-372); on the
@@ -297,15 +320,27 @@ class Uno3D_T20(nn.Module):
 
     def forward(self, x):
         x = torch.cat((x, self.get_grid(x.shape, x.device)), dim=-1).permute(0, 4, 1, 2, 3).contiguous()
-        lifted = F.gelu(gelu_channel_mix(channel_mix(x, self.fc.weight, self.fc.bias), self.fc0.weight, self.fc0.bias))
-        self.padding = int(self.pad * 0.1 * lifted.shape[-1])
-        lifted = F.pad(lifted, [self.padding, self.padding, 0, 0, 0, 0] if self.pad_both else [0, self.padding, 0, 0, 0, 0])
+        native = self._native_ends(x)
+        if native:      # the padded activation from fc0's own store epilogue
+            h = channel_mix(x, self.fc.weight, self.fc.bias)
+            self.padding = int(self.pad * 0.1 * h.shape[-1])
+            lifted = gelu_channel_mix_pad_last(h, self.fc0.weight, self.fc0.bias, self.padding if self.pad_both else 0, self.padding)
+        else:
+            lifted = F.gelu(gelu_channel_mix(channel_mix(x, self.fc.weight, self.fc.bias), self.fc0.weight, self.fc0.bias))
+            self.padding = int(self.pad * 0.1 * lifted.shape[-1])
+            lifted = F.pad(lifted, [self.padding, self.padding, 0, 0, 0, 0] if self.pad_both else [0, self.padding, 0, 0, 0, 0])
         g, crop = self._plan(*lifted.shape[-3:], self.padding)
         outs, c8 = {None: lifted}, lifted
+        last = self._NAMES[-1]
         for name, grid in zip(self._NAMES, g):
             c8 = outs[name] = getattr(self, name)(c8, *grid)
-            if name in self._SKIPS:
+            if name in self._SKIPS and not (native and name == last):
                 c8 = torch.cat([c8, self._resize(outs[self._SKIPS[name]], c8)], dim=1)
+        if native:      # fc1 on the two sources of the last skip connection, through the time window the crop keeps
+            Tp = c8.shape[-1]
+            window = None if self.padding == 0 else (crop, Tp - 2 * crop) if self.pad_both else (0, Tp - crop)
+            out = channel_mix_cat([c8, self._resize(outs[self._SKIPS[last]], c8)], self.fc1.weight, self.fc1.bias, last_window=window)
+            return gelu_project(out, self.fc2.weight, self.fc2.bias).permute(0, 2, 3, 4, 1).contiguous()
         if self.padding != 0:           # (the crop is written from `padding` as the reference writes it: -0 would empty the tensor)
             c8 = c8[..., crop:-crop] if self.pad_both else c8[..., :-crop]
         out = gelu_project(channel_mix(c8.contiguous(), self.fc1.weight, self.fc1.bias), self.fc2.weight, self.fc2.bias)

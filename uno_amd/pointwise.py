@@ -433,12 +433,95 @@ def channel_mix_cat_project(xs, weight, bias, weight2, bias2, gelu_first: bool =
     return gelu_project(channel_mix_cat(xs, weight, bias, gelu_first=gelu_first, defer_grad=defer_grad), weight2, bias2)
 
 
-def channel_mix_cat(xs, weight: torch.Tensor, bias: torch.Tensor | None, gelu_first: bool = False, defer_grad=None) -> torch.Tensor:
+def _wgrad_rows_into(leaves, gy, x1, x2, window, need_w, need_b, act_x=False):
+    """_wgrad_into for a layer whose sources are read through a short-row window (uno_channel_wgrad2_rows): the same in-place rules
+    (INPLACE_PARAM_GRADS, the accumulate path) through _layer_grad_targets."""
+    if not (need_w or need_b):
+        return None, None
+    lt = _layer_grad_targets(leaves, need_b) if need_w else None        # committed: the call below writes them
+    if lt is not None:
+        _native.channel_wgrad2_rows(gy, x1, x2, window, need_bias=need_b, act_x=act_x, out_w=lt.out_w, out_b=lt.out_b, accumulate=lt.accumulate)
+        return lt.gw, lt.gb
+    return _native.channel_wgrad2_rows(gy, x1, x2, window, need_bias=need_b, act_x=act_x)
+
+
+class _ChannelMixCatRowsFn(torch.autograd.Function):
+    """y = W . cat([gelu](x1), x2)[..., col0 : col0 + cols] + bias for channels-first tensors whose LAST axis is short (the time axis of
+    the NS-3D models: reference navier_stokes_uno3d.py:358-382) with neither the concatenation nor the cropped copy: the kernels read
+    the two sources through the window (uno_channel_mix2_rows) and the backward pass returns whole-plane gradients for both - the
+    border columns zero - from one launch (uno_channel_mix2_rows_grad), the parameter gradients from uno_channel_wgrad2_rows."""
+
+    @staticmethod
+    def forward(ctx, x1, x2, w, bias, gelu_first, window, leaves=None):
+        x1, x2, w = _plain(x1), _plain(x2), _plain(w)
+        y = _native.channel_mix2_rows(x1, x2, w, None if bias is None else _plain(bias), window, act_in=gelu_first)
+        ctx.save_for_backward(x1, x2, w)
+        ctx.has_bias, ctx.gelu_first, ctx.window, ctx.leaves = bias is not None, gelu_first, window, leaves
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        x1, x2, w = ctx.saved_tensors
+        gy = _plain(gy)
+        g1 = g2 = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            g1, g2 = _native.channel_mix2_rows_grad(gy, w, x1.shape[1], ctx.window, x1.shape[2], need_g2=ctx.needs_input_grad[1],
+                                                    dgelu_of=x1 if ctx.gelu_first else None)
+            if not ctx.needs_input_grad[0]:         # (the kernel has no form without the first source: its gradient is computed and dropped;
+                g1 = None                           # the models always need both)
+        gw, gb = _wgrad_rows_into(ctx.leaves, gy, x1, x2, ctx.window, ctx.needs_input_grad[2], ctx.has_bias and ctx.needs_input_grad[3],
+                                  act_x=ctx.gelu_first)
+        return g1, g2, gw, gb, None, None, None
+
+
+def _last_window_rows(xs, weight, last_window):
+    """(rows, cols, pitch, col0) when the short-row kernels take channel_mix_cat(xs, ..., last_window=), else None"""
+    if len(xs) != 2 or not all(x.is_cuda and x.dtype == torch.float32 for x in xs) or weight.dtype != torch.float32:
+        return None
+    x1, x2 = xs
+    if x1.dim() < 3 or x1.shape[0] != x2.shape[0] or x1.shape[2:] != x2.shape[2:] or x2.shape[1] < 1:
+        return None
+    col0, cols = int(last_window[0]), int(last_window[1])
+    pitch = x1.shape[-1]
+    rows = 1
+    for d in x1.shape[2:-1]:
+        rows *= d
+    if x1.shape[0] == 0 or rows == 0:
+        return None
+    if not _native.rows_window_ok(rows, cols, pitch, col0, rows * pitch, x1.shape[1] + x2.shape[1], weight.shape[0]):
+        return None
+    return rows, cols, pitch, col0
+
+
+def channel_mix_cat(xs, weight: torch.Tensor, bias: torch.Tensor | None, gelu_first: bool = False, defer_grad=None,
+                    last_window=None) -> torch.Tensor:
     """channel_mix(torch.cat(xs, dim=1), weight, bias) - the projection after a skip connection (reference
     darcy_flow_uno2d.py:122-127: `torch.cat([x_c5, x_fc0], dim=1)` then `fc1`) - without materialising the
     concatenation when there are two float32 device tensors.  gelu_first: xs[0] is a PRE-activation tensor and stands
     for gelu(xs[0]) (the block in front deferred its GELU to this consumer).  defer_grad: a GradJoin whose owner is xs[1]'s other
-    consumer - xs[1]'s gradient is then accumulated into that consumer's buffer (fused device path only)."""
+    consumer - xs[1]'s gradient is then accumulated into that consumer's buffer (fused device path only).
+    last_window = (col0, cols): the layer is applied to torch.cat(xs, 1)[..., col0 : col0 + cols] (the time-axis crop of the NS-3D models,
+    reference navier_stokes_uno3d.py:371-379) -> dense (B, Co, ..., cols); two float32 device tensors inside the short-row kernels' range
+    are read where they lie (no concatenation, no cropped copy; defer_grad does not go with it), anything else takes the stock ops."""
+    if last_window is not None:
+        win = _last_window_rows(xs, weight, last_window)
+        if win is not None:
+            x1, x2 = xs
+            B = x1.shape[0]
+            w = weight.reshape(weight.shape[0], -1)
+            if defer_grad is not None:          # the window form returns xs[1]'s gradient as a tensor: the join is not honoured
+                defer_grad.void()
+            y = _ChannelMixCatRowsFn.apply(x1.reshape(B, x1.shape[1], -1), x2.reshape(B, x2.shape[1], -1), w, bias, bool(gelu_first), win,
+                                           (weight, bias))
+            return y.view(B, w.shape[0], *x1.shape[2:-1], win[1])
+        xs = list(xs)
+        if defer_grad is not None:
+            defer_grad.void()
+        if gelu_first:
+            xs[0] = F.gelu(xs[0])
+        col0, cols = int(last_window[0]), int(last_window[1])
+        return channel_mix(torch.cat(xs, dim=1)[..., col0:col0 + cols].contiguous(), weight, bias)
     if len(xs) == 2 and all(_dev_act(x) for x in xs) and xs[0].dtype == xs[1].dtype and weight.dtype == torch.float32:
         x1, x2 = xs
         B = x1.shape[0]
@@ -524,6 +607,47 @@ def gelu_channel_mix_pad(pre: torch.Tensor, weight: torch.Tensor, bias: torch.Te
         if _native.channel_mix_act_padded_ok(pre, Hp, Wp):
             return _GeluChannelMixPadFn.apply(pre, weight.reshape(weight.shape[0], pre.shape[1]), bias, Hp, Wp, (weight, bias))
     return gelu_pad2d(gelu_channel_mix(pre, weight, bias), pad_h, pad_w)
+
+
+class _GeluChannelMixPadLastFn(torch.autograd.Function):
+    """zero-pad along the LAST axis (gelu(W . gelu(pre) + bias)): the second lift layer of the NS-3D models, its activation and the
+    time-axis padding (reference navier_stokes_uno3d.py:304-318) from ONE forward kernel whose store epilogue writes the padded
+    activation (uno_channel_mix_act_padded_rows).  The dense pre-activation result is kept: the backward pass multiplies gelu' of it
+    into the window of the padded gradient (uno_dgelu_rows) and runs the layer's two gradient kernels as in _GeluChannelMixFn."""
+
+    @staticmethod
+    def forward(ctx, pre, w, bias, window, leaves=None):
+        pre, w = _plain(pre), _plain(w)
+        y, act = _native.channel_mix_act_padded_rows(pre, w, None if bias is None else _plain(bias), window, act_in=True, keep_y=True)
+        ctx.save_for_backward(pre, w, y)
+        ctx.has_bias, ctx.window, ctx.leaves = bias is not None, window, leaves
+        return act
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gact):
+        pre, w, y = ctx.saved_tensors
+        gz = _native.dgelu_rows(y, _plain(gact), ctx.window)
+        g_pre = _native.channel_mix(gz, w, None, transpose_w=True, dgelu_of=pre) if ctx.needs_input_grad[0] else None
+        gw, gb = _wgrad_into(ctx.leaves, gz, pre, None, ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2], act_x=True)
+        return g_pre, gw, gb, None, None
+
+
+def gelu_channel_mix_pad_last(pre: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None, pad_left: int, pad_right: int) -> torch.Tensor:
+    """F.pad(F.gelu(gelu_channel_mix(pre, weight, bias)), [pad_left, pad_right]) - the 3-D sibling of gelu_channel_mix_pad: the lift's
+    second layer, its GELU and the zero padding of the LAST (time) axis (reference navier_stokes_uno3d.py:304-318) with the activation
+    and the padding written by the layer's own kernel for a float32 device tensor inside the short-row kernels' range; the stock ops
+    otherwise."""
+    pl, pr = int(pad_left), int(pad_right)
+    if pre.dim() >= 3 and pre.is_cuda and pre.dtype == torch.float32 and weight.dtype == torch.float32 and pl >= 0 and pr >= 0 and pre.numel() > 0:
+        B, Ci, T = pre.shape[0], pre.shape[1], pre.shape[-1]
+        rows = pre.numel() // (B * Ci * T)
+        pitch = T + pl + pr
+        Co = weight.shape[0]
+        if _native.rows_window_ok(rows, T, pitch, pl, rows * pitch, Ci, Co):
+            act = _GeluChannelMixPadLastFn.apply(pre.reshape(B, Ci, -1), weight.reshape(Co, Ci), bias, (rows, T, pitch, pl), (weight, bias))
+            return act.view(B, Co, *pre.shape[2:-1], pitch)
+    return F.pad(F.gelu(gelu_channel_mix(pre, weight, bias)), [pl, pr] + [0, 0] * (pre.dim() - 3))
 
 
 class _LiftFn(torch.autograd.Function):
