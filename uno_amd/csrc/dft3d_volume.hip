@@ -702,10 +702,16 @@ __global__ __launch_bounds__(64 * VI_WAVES) void dft3d_inv_volume_kernel(Vol3dPa
         zlo[ks] = mk * 2 * m3 + nz;
         zhi[ks] = (2 * m2 - 1 - mk) * 2 * m3 + nz;
     }
+    // One buffer resource PER PLANE (scalar arithmetic on the base address) and no scalar offset in the stores.  With the plane's offset
+    // in the stores' scalar-offset operand - the first form of this kernel - the compiler assumes that a 16-byte store has read its data
+    // registers by the time the next instruction issues, and lets a VALU instruction overwrite them there (<1, 2, 2, 4, true>: a
+    // v_pk_fma_f32 right behind the store of the first column piece of the Q rows; <2, 2, 2, 6, true>: a v_sub_f32 behind the last piece of
+    // the P rows).  On gfx950 the store then sends the NEW value for the last four lanes of every 16: wrong outputs in rows 12 .. 15 of a
+    // slot tile, varying from run to run (tests/test_hip_dft3d_instances.py, 17 x 33 x 20 modes (5, 10, 8) and 33 x 34 x 20 modes (1, 17, 1)).
+    // Without a scalar offset the compiler keeps the wait states between such a store and a write of its data registers itself.
     // store plan: byte offsets (inside a plane) of this lane's 4-column pieces of rows P / Q of tile pair u; absent rows / columns -> OOB
     constexpr unsigned OOB = 0xC0000000u;
-    const size_t vol_bytes = (size_t)D1 * D2 * D3 * 4;
-    const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc((void*)(p.out + (size_t)vol * D1 * D2 * D3), 0, (int)vol_bytes, 0x00020000);
+    float* const yvol = p.out + (size_t)vol * D1 * D2 * D3;
     unsigned oP[U], oQ[U], oPl[U], oQl[U];
     const int wl = 16 * (NWT - 1) + 4 * gq;                                      // first column of the piece in the last tile
     const int nlast = min(max(D3 - wl, 0), 4);                                   // its valid columns
@@ -720,17 +726,20 @@ __global__ __launch_bounds__(64 * VI_WAVES) void dft3d_inv_volume_kernel(Vol3dPa
         oQl[u] = (q_ok && nlast > 0) ? oQ[u] + 64u * (NWT - 1) : OOB;
     }
     const unsigned plane_bytes = (unsigned)(D2 * D3) * 4u;
-    auto put = [&](const f32x4& Y, unsigned off, unsigned offl, int wt, unsigned sbase) {
+    auto plane_rsrc = [&](int d1) -> __amdgpu_buffer_rsrc_t {
+        return __builtin_amdgcn_make_buffer_rsrc((void*)(yvol + (size_t)d1 * (size_t)(D2 * D3)), 0, (int)plane_bytes, 0x00020000);
+    };
+    auto put = [&](const f32x4& Y, unsigned off, unsigned offl, int wt, const __amdgpu_buffer_rsrc_t& yrs) {
         u32x4v d;
 #pragma unroll
         for (int e = 0; e < 4; ++e) d[e] = __float_as_uint(Y[e]);
         if (wt < NWT - 1) {
-            __builtin_amdgcn_raw_buffer_store_b128(d, yrs, off + 64u * wt, sbase, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(d, yrs, off + 64u * wt, 0, 0);
         } else if (A4) {
-            __builtin_amdgcn_raw_buffer_store_b128(d, yrs, offl, sbase, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(d, yrs, offl, 0, 0);
         } else {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) __builtin_amdgcn_raw_buffer_store_b32(d[e], yrs, e < nlast ? offl + 4u * e : OOB, sbase, 0);
+            for (int e = 0; e < 4; ++e) __builtin_amdgcn_raw_buffer_store_b32(d[e], yrs, e < nlast ? offl + 4u * e : OOB, 0, 0);
         }
     };
     // The three stages of a plane (dim2 GEMM -> untwist -> T-axis GEMM + stores) depend on each other, and a wave's VALU work only runs
@@ -775,7 +784,7 @@ __global__ __launch_bounds__(64 * VI_WAVES) void dft3d_inv_volume_kernel(Vol3dPa
             pl.UP[u] = UP; pl.UQ[u] = UQ;
         }
     };
-    auto t_stage = [&](const Plane& pl, int u, unsigned sbase) {
+    auto t_stage = [&](const Plane& pl, int u, const __amdgpu_buffer_rsrc_t& yrs) {
 #pragma unroll
         for (int wt = 0; wt < NWT; ++wt) {
             f32x4 YP = f32x4{0, 0, 0, 0}, YQ = f32x4{0, 0, 0, 0};
@@ -784,8 +793,8 @@ __global__ __launch_bounds__(64 * VI_WAVES) void dft3d_inv_volume_kernel(Vol3dPa
                 YP = mfma16(G(wt, r), pl.UP[u][r], YP);
                 YQ = mfma16(G(wt, r), pl.UQ[u][r], YQ);
             }
-            put(YP, oP[u], oPl[u], wt, sbase);
-            put(YQ, oQ[u], oQl[u], wt, sbase);
+            put(YP, oP[u], oPl[u], wt, yrs);
+            put(YQ, oQ[u], oQl[u], wt, yrs);
         }
     };
     const int my_planes = max((D1 - wave + VI_WAVES - 1) / VI_WAVES, 0);
@@ -799,14 +808,14 @@ __global__ __launch_bounds__(64 * VI_WAVES) void dft3d_inv_volume_kernel(Vol3dPa
     }
     for (int j = 0; j + 1 < my_planes; ++j) {
         const int d1 = wave + VI_WAVES * j;
-        const unsigned sbase = (unsigned)d1 * plane_bytes;
+        const __amdgpu_buffer_rsrc_t yrs = plane_rsrc(d1);
         float lo[NK2], hi[NK2];
         f32x4 Pc2[U], Qs2[U];
         Plane nxt;
         read_rows(d1 + VI_WAVES, lo, hi);
-        t_stage(cur, 0, sbase);
+        t_stage(cur, 0, yrs);
         dim2_stage(lo, hi, Pc2, Qs2);
-        if (U > 1) t_stage(cur, U - 1, sbase);
+        if (U > 1) t_stage(cur, U - 1, yrs);
         untwist(Pc2, Qs2, nxt);
         cur = nxt;
         // the interleave, spelled out for the scheduler (it clusters the MFMAs and leaves the untwist behind them otherwise):
@@ -829,9 +838,9 @@ __global__ __launch_bounds__(64 * VI_WAVES) void dft3d_inv_volume_kernel(Vol3dPa
         }
     }
     if (my_planes > 0) {
-        const unsigned sbase = (unsigned)(wave + VI_WAVES * (my_planes - 1)) * plane_bytes;
+        const __amdgpu_buffer_rsrc_t yrs = plane_rsrc(wave + VI_WAVES * (my_planes - 1));
 #pragma unroll
-        for (int u = 0; u < U; ++u) t_stage(cur, u, sbase);
+        for (int u = 0; u < U; ++u) t_stage(cur, u, yrs);
     }
     VOL_STAMP_NOWAIT(5);
     VOL_STAMP(6);
