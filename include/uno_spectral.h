@@ -147,6 +147,38 @@ int uno_spectral_conv3d_backward(const float* gy, const float* xtrunc, const flo
                                  float* const* gw, void* ws, int B, int Ci, int Co, int H, int W, int T,
                                  int Ho, int Wo, int To, int m1, int m2, int m3, void* stream);
 
+/* The two 3-D transforms of the calls above as stages of their own (no ABI change: new entry points only).
+ *   forward: volumes x (n_vol, D1, D2, D3) f32 -> corner-major truncated spectra (.., 4, m1, m2, m3) c64, times `scale`;
+ *            adjoint = 1: the Hermitian-weighted, masked form the backward pass applies to the output gradient.
+ *   inverse: spectra -> volumes y (n_vol, D1, D2, D3) f32, times `scale`; weighted = 1: Hermitian weights and later-wins masks
+ *            (the forward pass's irfftn).
+ * Placement on the SPECTRUM side, the convention of uno_dft2d_forward_grouped: volume i of a (B, group) batch <-> spectrum volume
+ * (i / group) * stride + offset + i % group of a (B, stride, 4, m1, m2, m3) tensor - each source of a channel concatenation is
+ * transformed into (read from) its channel range of one spectrum tensor.  group = stride = offset = 0: plain (spectrum volume i).
+ * Grouped calls need group >= 1, offset >= 0, offset + group <= stride and n_vol % group == 0.  The volume side is always dense.
+ * Per call the library takes the one-workgroup-per-volume kernels or the plane-by-plane path, as inside the layer; the latter uses
+ * ws, uno_dft3d_ws_bytes(n_vol, D1, m2, m3) = 8 * n_vol * D1 * 2 m2 * m3 bytes (always required).  Arguments are checked on the
+ * host before any launch (negative return, uno_last_error names the argument); n_vol == 0 succeeds without touching the device. */
+long long uno_dft3d_ws_bytes(int n_vol, int D1, int m2, int m3);
+int uno_dft3d_forward_grouped(const float* x, float* spec, void* ws, int n_vol, int D1, int D2, int D3, int m1, int m2, int m3,
+                              float scale, int adjoint, int group, int stride, int offset, void* stream);
+int uno_dft3d_inverse_grouped(const float* spec, float* y, void* ws, int n_vol, int D1, int D2, int D3, int m1, int m2, int m3,
+                              float scale, int weighted, int group, int stride, int offset, void* stream);
+
+/* uno_spectral_conv3d_forward / _backward on the channel concatenation of two tensors, which is never built (a skip connection):
+ *   x1 (B, C1, H, W, T), x2 (B, Ci - C1, H, W, T), 0 < C1 < Ci;  gx1 / gx2 [out] of the same shapes, distinct buffers.
+ * w, y, xtrunc (B, Ci, 4, m1, m2, m3), gw and both workspace sizes are those of the one-source calls; each source is transformed
+ * into (its gradient out of) its channel range of the one spectrum tensor, everything else is unchanged.  The choice between the
+ * transform kernel families is made for the concatenation's volume count, so each source runs the kernels the one-source call on
+ * the concatenation runs and the results are those of that call, bit for bit.  x2 == NULL / gx2 == NULL:
+ * the one-source call on x1 / gx1 (C1 ignored).  With gx2 given gx1 is required.  All launches go on `stream`. */
+int uno_spectral_conv3d_forward2(const float* x1, const float* x2, int C1, const float* const* w, float* y, float* xtrunc, void* ws,
+                                 int B, int Ci, int Co, int H, int W, int T, int Ho, int Wo, int To, int m1, int m2, int m3,
+                                 void* stream);
+int uno_spectral_conv3d_backward2(const float* gy, const float* xtrunc, const float* const* w, float* gx1, float* gx2, int C1,
+                                  float* const* gw, void* ws, int B, int Ci, int Co, int H, int W, int T, int Ho, int Wo, int To,
+                                  int m1, int m2, int m3, void* stream);
+
 /* Pruned complex DFT along the leading axis of a 3-D transform:
  *   inverse = 0: planes (n_img, H, 2*m2*m3) c64 -> corner-major spectrum (n_img, 4, m1, m2, m3) c64
  *   inverse = 1: the reverse direction (e^{+i...}); mask_overlap applies on the spectrum side. */

@@ -63,6 +63,11 @@ _SIGNATURES = {
     "uno_spectral_conv3d_forward": (C.c_int, [_fp, C.POINTER(_fp), _fp, _fp, _fp] + [_i] * 12 + [_fp]),
     "uno_spectral_conv3d_backward": (C.c_int, [_fp, _fp, C.POINTER(_fp), _fp, C.POINTER(_fp), _fp] + [_i] * 12 + [_fp]),
     "uno_cdft_axis": (C.c_int, [_fp, _fp] + [_i] * 6 + [C.c_float, _i, _fp]),
+    "uno_dft3d_ws_bytes": (C.c_longlong, [_i] * 4),
+    "uno_dft3d_forward_grouped": (C.c_int, [_fp, _fp, _fp] + [_i] * 7 + [C.c_float] + [_i] * 4 + [_fp]),
+    "uno_dft3d_inverse_grouped": (C.c_int, [_fp, _fp, _fp] + [_i] * 7 + [C.c_float] + [_i] * 4 + [_fp]),
+    "uno_spectral_conv3d_forward2": (C.c_int, [_fp, _fp, _i, C.POINTER(_fp), _fp, _fp, _fp] + [_i] * 12 + [_fp]),
+    "uno_spectral_conv3d_backward2": (C.c_int, [_fp, _fp, C.POINTER(_fp), _fp, _fp, _i, C.POINTER(_fp), _fp] + [_i] * 12 + [_fp]),
     "uno_resample2d": (C.c_int, [_fp, _fp, _fp] + [_i] * 5 + [_fp, _fp, _i, _fp, _fp, _i, _fp, _fp, _i, _i, _fp]),
     "uno_channel_mix": (C.c_int, [_fp, _fp, _fp, _fp, _i, _i, _i, C.c_longlong, _i, _i, _i, _fp, _fp]),
     "uno_channel_wgrad_ws_bytes": (C.c_longlong, [_i, _i, _i, C.c_longlong]),
@@ -666,6 +671,123 @@ def spectral_conv3d_backward(gy, xt, ws_, H: int, W: int, T: int, need_gx=True, 
                                                 H, W, T, Ho, Wo, To, m1, m2, m3, _stream(gy))
     _check(rc, "uno_spectral_conv3d_backward")
     return gx, gws
+
+
+def spectral_conv3d_forward2(x1, x2, ws_, Ho: int, Wo: int, To: int):
+    """spectral_conv3d_forward on the channel concatenation of x1 (B,C1,H,W,T) and x2 (B,C2,H,W,T), which is not built
+    -> (y, xtrunc (B,C1+C2,4,m1,m2,m3) c64)."""
+    _require(x1, torch.float32, "x1")
+    _require(x2, torch.float32, "x2")
+    if x1.device != x2.device or x1.shape[0] != x2.shape[0] or x1.shape[2:] != x2.shape[2:]:
+        raise RuntimeError(f"uno_amd: the two sources {tuple(x1.shape)} and {tuple(x2.shape)} must share device, batch and grid")
+    if len(ws_) != 4:
+        raise RuntimeError("uno_amd: the 3-D spectral convolution takes four weight tensors")
+    for w in ws_:
+        _require(w, torch.complex64, "weights")
+        if tuple(w.shape) != tuple(ws_[0].shape):
+            raise RuntimeError("uno_amd: weights1..4 must have one shape")
+    B, C1, H, W, T = x1.shape
+    Ci = C1 + x2.shape[1]
+    Ci2, Co, m1, m2, m3 = ws_[0].shape
+    if Ci2 != Ci:
+        raise RuntimeError(f"uno_amd: weight shape {tuple(ws_[0].shape)} does not match input channels {C1} + {x2.shape[1]}")
+    L = lib()
+    with torch.cuda.device(x1.device):
+        y = torch.empty((B, Co, Ho, Wo, To), dtype=torch.float32, device=x1.device)
+        xt = torch.empty((B, Ci, 4, m1, m2, m3), dtype=torch.complex64, device=x1.device)
+        scratch = torch.empty(max(1, L.uno_spectral_conv3d_fwd_ws_bytes(B, Ci, Co, H, Ho, m1, m2, m3)), dtype=torch.uint8,
+                              device=x1.device)
+        with _any_mode_scratch(x1.device, (B * max(C1, Ci - C1) * H, W, T, m2, m3), (B * Co * Ho, Wo, To, m2, m3)):
+            rc = L.uno_spectral_conv3d_forward2(_ptr(x1), _ptr(x2), C1, _ptr_array(ws_), _ptr(y), _ptr(xt), _ptr(scratch), B, Ci, Co,
+                                                H, W, T, Ho, Wo, To, m1, m2, m3, _stream(x1))
+    _check(rc, "uno_spectral_conv3d_forward2")
+    return y, xt
+
+
+def spectral_conv3d_backward2(gy, xt, ws_, C1: int, H: int, W: int, T: int, need_gx=True, need_gw=True):
+    """-> (gx1 (B,C1,H,W,T), gx2 (B,Ci-C1,H,W,T), [gw1..4]); need_gx=False: (None, None, ...)."""
+    _require(gy, torch.float32, "grad_output")
+    _require(xt, torch.complex64, "xtrunc")
+    for w in ws_:
+        _require(w, torch.complex64, "weights")
+    B, Co, Ho, Wo, To = gy.shape
+    Ci, Co2, m1, m2, m3 = ws_[0].shape
+    if Co2 != Co:
+        raise RuntimeError("uno_amd: grad_output channels do not match the weights")
+    if not 0 < C1 < Ci:
+        raise RuntimeError(f"uno_amd: the first source's channel count {C1} must lie inside (0, {Ci})")
+    L = lib()
+    with torch.cuda.device(gy.device):
+        gx1 = torch.empty((B, C1, H, W, T), dtype=torch.float32, device=gy.device) if need_gx else None
+        gx2 = torch.empty((B, Ci - C1, H, W, T), dtype=torch.float32, device=gy.device) if need_gx else None
+        gws = [torch.empty_like(w) for w in ws_] if need_gw else None
+        scratch = torch.empty(max(1, L.uno_spectral_conv3d_bwd_ws_bytes(B, Ci, Co, H, Ho, m1, m2, m3)), dtype=torch.uint8,
+                              device=gy.device)
+        with _any_mode_scratch(gy.device, (B * Co * Ho, Wo, To, m2, m3), (B * max(C1, Ci - C1) * H, W, T, m2, m3)):
+            rc = L.uno_spectral_conv3d_backward2(_ptr(gy), _ptr(xt), _ptr_array(ws_), _opt(gx1), _opt(gx2), C1,
+                                                 _ptr_array(gws) if need_gw else None, _ptr(scratch), B, Ci, Co,
+                                                 H, W, T, Ho, Wo, To, m1, m2, m3, _stream(gy))
+    _check(rc, "uno_spectral_conv3d_backward2")
+    return gx1, gx2, gws
+
+
+def _grouping3d(n_vol: int, group: int, spec, who: str):
+    """(group, stride) to hand to a 3-D stage call on spec (B, stride, 4, m1, m2, m3); group <= 0: plain, (0, 0)"""
+    if spec.dim() != 6 or spec.shape[2] != 4:
+        raise RuntimeError(f"uno_amd: {who}: the spectrum tensor must be (batch, channels, 4, m1, m2, m3), got {tuple(spec.shape)}")
+    if group <= 0:
+        if spec.shape[0] * spec.shape[1] != n_vol:
+            raise RuntimeError(f"uno_amd: {who}: {n_vol} volumes against {spec.shape[0] * spec.shape[1]} spectra")
+        return 0, 0
+    if n_vol % group or n_vol // group != spec.shape[0]:
+        raise RuntimeError(f"uno_amd: {who}: {n_vol} volumes in groups of {group} against a spectrum batch of {spec.shape[0]}")
+    return group, spec.shape[1]
+
+
+def dft3d_forward(x, modes=None, scale: float = 1.0, adjoint: bool = False, out=None, group: int = 0, offset: int = 0):
+    """uno_dft3d_forward_grouped: x (..., D1, D2, D3) f32 -> truncated corner-major spectra.  Plain (group = 0): a fresh
+    (*lead, 4, m1, m2, m3) c64 tensor for modes = (m1, m2, m3).  Grouped: x (B, group, D1, D2, D3) is written into channels
+    [offset, offset + group) of out (B, stride, 4, m1, m2, m3) c64, the rest of which is left untouched; returns out."""
+    _require(x, torch.float32, "x")
+    *lead, D1, D2, D3 = x.shape
+    n_vol = _count(lead)
+    if out is None:
+        m1, m2, m3 = modes
+        out = torch.empty((n_vol, 1, 4, m1, m2, m3), dtype=torch.complex64, device=x.device)
+        result = out.view(*lead, 4, m1, m2, m3)
+    else:
+        _require(out, torch.complex64, "spectrum")
+        result = out
+    m1, m2, m3 = out.shape[3:]
+    group, stride = _grouping3d(n_vol, group, out, "dft3d_forward")
+    L = lib()
+    with torch.cuda.device(x.device):
+        scratch = torch.empty(max(1, L.uno_dft3d_ws_bytes(n_vol, D1, m2, m3)), dtype=torch.uint8, device=x.device)
+        with _any_mode_scratch(x.device, (n_vol * D1, D2, D3, m2, m3)):
+            rc = L.uno_dft3d_forward_grouped(_ptr(x), _ptr(out), _ptr(scratch), n_vol, D1, D2, D3, m1, m2, m3, float(scale),
+                                             1 if adjoint else 0, group, stride, offset, _stream(x))
+    _check(rc, "uno_dft3d_forward_grouped")
+    return result
+
+
+def dft3d_inverse(spec, dims, scale: float = 1.0, weighted: bool = False, group: int = 0, offset: int = 0):
+    """uno_dft3d_inverse_grouped: spec (B, C, 4, m1, m2, m3) c64 -> volumes (B, C, D1, D2, D3) f32 (plain), or - grouped - the
+    volumes (B, group, D1, D2, D3) of channels [offset, offset + group) of spec, which is read where it lies."""
+    _require(spec, torch.complex64, "spectrum")
+    D1, D2, D3 = (int(d) for d in dims)
+    B, C = spec.shape[:2]
+    m1, m2, m3 = spec.shape[3:]
+    n_vol = B * (group if group > 0 else C)
+    group, stride = _grouping3d(n_vol, group, spec, "dft3d_inverse")
+    L = lib()
+    with torch.cuda.device(spec.device):
+        y = torch.empty((B, n_vol // B if B else 0, D1, D2, D3), dtype=torch.float32, device=spec.device)
+        scratch = torch.empty(max(1, L.uno_dft3d_ws_bytes(n_vol, D1, m2, m3)), dtype=torch.uint8, device=spec.device)
+        with _any_mode_scratch(spec.device, (n_vol * D1, D2, D3, m2, m3)):
+            rc = L.uno_dft3d_inverse_grouped(_ptr(spec), _ptr(y), _ptr(scratch), n_vol, D1, D2, D3, m1, m2, m3, float(scale),
+                                             1 if weighted else 0, group, stride, offset, _stream(spec))
+    _check(rc, "uno_dft3d_inverse_grouped")
+    return y
 
 
 def resample2d(x, Ho: int, Wo: int, tabH, tabW, tilesH=None, out=None):

@@ -23,7 +23,7 @@ static int check_modes2d(const char* who, int H, int W, int Ho, int Wo, int m1, 
 }
 
 static int dft2d(bool inverse, const float* in, float* out, int n_img, int H, int W, int m1, int m2, float scale,
-                 int herm, int mask, hipStream_t s, int sp_group = 0, int sp_stride = 0, int sp_offset = 0, int bf16 = 0) {
+                 int herm, int mask, hipStream_t s, int sp_group = 0, int sp_stride = 0, int sp_offset = 0, int bf16 = 0, int n_decide = 0) {
     const char* who = inverse ? "uno_dft2d_inverse" : "uno_dft2d_forward";
     if (n_img < 0) { set_error("%s: negative image count", who); return -1; }
     if (n_img > 0 && (!in || !out)) { set_error("%s: null pointer", who); return -1; }
@@ -45,8 +45,11 @@ static int dft2d(bool inverse, const float* in, float* out, int n_img, int H, in
     if (!p.twH || !p.twW) return -6;
     // mode counts beyond the compiled MFMA range (the reference's default modes, integral_operators.py:153-158): any-mode form
     if (m1 > 40 || m2 > 48) return launch_dft2d_generic(p, inverse, thread_scratch().ptr, thread_scratch().bytes, s);
-    // many small images (3-D planes, coarse 2-D levels): plane-batched kernels (dft2d_plane.hip)
-    if (inverse ? dft2d_inv_plane_applies(p) : dft2d_fwd_plane_applies(p))
+    // many small images (3-D planes, coarse 2-D levels): plane-batched kernels (dft2d_plane.hip).  n_decide > 0: the image count the choice
+    // is made for (one source of a two-source layer call takes the kernels its concatenation would take)
+    Dft2dParams q = p;
+    if (n_decide > 0) q.n_img = n_decide;
+    if (inverse ? dft2d_inv_plane_applies(q) : dft2d_fwd_plane_applies(q))
         return inverse ? launch_dft2d_inv_plane(p, s) : launch_dft2d_fwd_plane(p, s);
     // bfloat16 images: row stage on the bf16 MFMA (dft2d_b16.hip)
     if (dft2d_b16_applies(p)) {
@@ -376,8 +379,9 @@ int uno_mode_wgrad_acc(const float* xtrunc, const float* go, float* const* gw, i
     return mode_wgrad_impl(xtrunc, go, gw, B, Ci, Co, ncorner, modes_per_corner, accumulate, stream);
 }
 
-int uno_cdft_axis(const float* in, float* out, int inverse, int n_img, int H, int m1, int m2, int m3, float scale,
-                  int mask_overlap, void* stream) {
+// `group` > 0: grouped placement of the corner-major side (CdftParams::sp_group); the callers have validated it
+static int cdft_axis(const float* in, float* out, int inverse, int n_img, int H, int m1, int m2, int m3, float scale, int mask_overlap,
+                     int group, int stride, int offset, void* stream) {
     if (n_img < 0 || H < 1 || m1 < 1 || m1 > H || m2 < 1 || m3 < 1) {
         set_error("uno_cdft_axis: bad sizes n_img=%d H=%d modes=(%d,%d,%d)", n_img, H, m1, m2, m3);
         return -1;
@@ -387,10 +391,16 @@ int uno_cdft_axis(const float* in, float* out, int inverse, int n_img, int H, in
     CdftParams p;
     p.in = in; p.out = out; p.n_img = n_img; p.H = H; p.C = 2 * m2 * m3; p.m1 = m1; p.m2 = m2; p.m3 = m3;
     p.scale = scale; p.mask = mask_overlap ? 1 : 0;
+    if (group > 0) { p.sp_group = group; p.sp_stride = stride; p.sp_offset = offset; }
     p.tw = twiddle_table(H);
     if (!p.tw) return -6;
     if (m1 > 40) return launch_cdft_generic(p, inverse != 0, (hipStream_t)stream);
     return launch_cdft(p, inverse != 0, (hipStream_t)stream);
+}
+
+int uno_cdft_axis(const float* in, float* out, int inverse, int n_img, int H, int m1, int m2, int m3, float scale,
+                  int mask_overlap, void* stream) {
+    return cdft_axis(in, out, inverse, n_img, H, m1, m2, m3, scale, mask_overlap, 0, 0, 0, stream);
 }
 
 // ---- FFT crop / resample of pointwise_op_3D (reference integral_operators.py:448-463) as pruned transforms with explicit
@@ -574,34 +584,39 @@ static int check_modes3d(const char* who, int H, int W, int T, int Ho, int Wo, i
 
 // volumes (n_vol, D1, D2, D3) -> corner-major truncated spectra (n_vol, 4, m1, m2, m3); `adjoint` = the Hermitian-weighted, masked form
 // the backward pass applies to the output gradient.  One workgroup per volume where that fits (K1v), else plane by plane (K1p) into
-// the workspace Z (n_vol * D1, 2 m2, m3) c64 and the leading axis from there (K5).
+// the workspace Z (n_vol * D1, 2 m2, m3) c64 and the leading axis from there (K5).  `group` > 0 places spectrum i at volume
+// (i / group) * stride + offset + i % group of `spec` (validated by the callers); the volume side and Z keep their addressing.
+// n_decide > 0: the volume count the choice between the kernel families is made for (the two-source layer calls pass the
+// concatenation's, so that each source runs the kernels the one-source call on the concatenation runs: the same bits per volume).
 static int fwd_transform3d(const float* x, float* spec, float* Z, int n_vol, int D1, int D2, int D3, int m1, int m2, int m3, float scale,
-                           int adjoint, hipStream_t s) {
-    if (vol3d_fwd_applies(n_vol, D1, D2, D3, m1, m2, m3)) {
+                           int adjoint, hipStream_t s, int group = 0, int stride = 0, int offset = 0, int n_decide = 0) {
+    if (vol3d_fwd_applies(n_decide > 0 ? n_decide : n_vol, D1, D2, D3, m1, m2, m3)) {
         Vol3dParams v;
         v.in = x; v.out = spec; v.n_vol = n_vol; v.D1 = D1; v.D2 = D2; v.D3 = D3; v.m1 = m1; v.m2 = m2; v.m3 = m3;
         v.scale = scale; v.herm = adjoint;
+        if (group > 0) { v.sp_group = group; v.sp_stride = stride; v.sp_offset = offset; }
         v.tw1 = twiddle_table(2 * D1); v.tw2 = twiddle_table(2 * D2); v.tw3 = twiddle_table(D3);
         if (!v.tw1 || !v.tw2 || !v.tw3) return -6;
         return launch_dft3d_fwd_volume(v, s);
     }
-    if (int rc = dft2d(false, x, Z, n_vol * D1, D2, D3, m2, m3, scale, adjoint, adjoint, s)) return rc;
-    return uno_cdft_axis(Z, spec, 0, n_vol, D1, m1, m2, m3, 1.0f, adjoint, (void*)s);
+    if (int rc = dft2d(false, x, Z, n_vol * D1, D2, D3, m2, m3, scale, adjoint, adjoint, s, 0, 0, 0, 0, n_decide * D1)) return rc;
+    return cdft_axis(Z, spec, 0, n_vol, D1, m1, m2, m3, 1.0f, adjoint, group, stride, offset, (void*)s);
 }
 
 // the inverse: corner-major spectra -> volumes; `weighted` = Hermitian weights + later-wins masks (the forward pass's irfftn)
 static int inv_transform3d(const float* spec, float* y, float* Z, int n_vol, int D1, int D2, int D3, int m1, int m2, int m3, float scale,
-                           int weighted, hipStream_t s) {
-    if (vol3d_inv_applies(n_vol, D1, D2, D3, m1, m2, m3)) {
+                           int weighted, hipStream_t s, int group = 0, int stride = 0, int offset = 0, int n_decide = 0) {
+    if (vol3d_inv_applies(n_decide > 0 ? n_decide : n_vol, D1, D2, D3, m1, m2, m3)) {
         Vol3dParams v;
         v.in = spec; v.out = y; v.n_vol = n_vol; v.D1 = D1; v.D2 = D2; v.D3 = D3; v.m1 = m1; v.m2 = m2; v.m3 = m3;
         v.scale = scale; v.herm = weighted;
+        if (group > 0) { v.sp_group = group; v.sp_stride = stride; v.sp_offset = offset; }
         v.tw1 = twiddle_table(2 * D1); v.tw2 = twiddle_table(2 * D2); v.tw3 = twiddle_table(D3);
         if (!v.tw1 || !v.tw2 || !v.tw3) return -6;
         return launch_dft3d_inv_volume(v, s);
     }
-    if (int rc = uno_cdft_axis(spec, Z, 1, n_vol, D1, m1, m2, m3, 1.0f, weighted, (void*)s)) return rc;
-    return dft2d(true, Z, y, n_vol * D1, D2, D3, m2, m3, scale, weighted, weighted, s);
+    if (int rc = cdft_axis(spec, Z, 1, n_vol, D1, m1, m2, m3, 1.0f, weighted, group, stride, offset, (void*)s)) return rc;
+    return dft2d(true, Z, y, n_vol * D1, D2, D3, m2, m3, scale, weighted, weighted, s, 0, 0, 0, 0, n_decide * D1);
 }
 
 long long uno_spectral_conv3d_fwd_ws_bytes(int B, int Ci, int Co, int H, int Ho, int m1, int m2, int m3) {
@@ -668,6 +683,115 @@ int uno_spectral_conv3d_backward(const float* gy, const float* xtrunc, const flo
         if (int rc = inv_transform3d(gX, gx, Z1, B * Ci, H, W, T, m1, m2, m3, inv_n, 0, s)) return rc;
     }
     return 0;
+}
+
+// ---- the 3-D transforms as stages of their own, with a grouped placement on the spectrum side (uno_dft2d_forward_grouped's convention)
+long long uno_dft3d_ws_bytes(int n_vol, int D1, int m2, int m3) {
+    if (n_vol <= 0 || D1 <= 0 || m2 <= 0 || m3 <= 0) return 0;
+    return 8LL * n_vol * D1 * 2 * m2 * m3;
+}
+
+// group <= 0 with stride == offset == 0: plain; else the grouped placement's conditions.  0, or -1 with the offending argument named.
+static int check_grouping3d(const char* who, int n_vol, int group, int stride, int offset) {
+    if (group <= 0) {
+        if (stride != 0 || offset != 0) { set_error("%s: group=%d must be >= 1 when stride=%d / offset=%d are given (plain: all three 0)", who, group, stride, offset); return -1; }
+        return 0;
+    }
+    if (offset < 0) { set_error("%s: offset=%d must be >= 0", who, offset); return -1; }
+    if ((long long)offset + group > stride) { set_error("%s: stride=%d must be >= offset + group = %d + %d", who, stride, offset, group); return -1; }
+    if (n_vol % group) { set_error("%s: n_vol=%d must be a multiple of group=%d", who, n_vol, group); return -1; }
+    return 0;
+}
+
+static int dft3d_stage(const char* who, bool inverse, const float* in, float* out, void* ws, int n_vol, int D1, int D2, int D3, int m1, int m2,
+                       int m3, float scale, int flag, int group, int stride, int offset, void* stream) {
+    if (n_vol < 0) { set_error("%s: n_vol=%d must be >= 0", who, n_vol); return -1; }
+    if (int rc = check_modes3d(who, D1, D2, D3, D1, D2, D3, m1, m2, m3)) return rc;
+    if (int rc = check_grouping3d(who, n_vol, group, stride, offset)) return rc;
+    if (n_vol == 0) return 0;
+    const char* in_name = inverse ? "spec" : "x";
+    const char* out_name = inverse ? "y" : "spec";
+    if (!in) { set_error("%s: null pointer %s", who, in_name); return -1; }
+    if (!out) { set_error("%s: null pointer %s", who, out_name); return -1; }
+    if (!ws) { set_error("%s: null pointer ws (uno_dft3d_ws_bytes)", who); return -1; }
+    float* Z = static_cast<float*>(ws);
+    if (inverse) return inv_transform3d(in, out, Z, n_vol, D1, D2, D3, m1, m2, m3, scale, flag ? 1 : 0, (hipStream_t)stream, group, stride, offset);
+    return fwd_transform3d(in, out, Z, n_vol, D1, D2, D3, m1, m2, m3, scale, flag ? 1 : 0, (hipStream_t)stream, group, stride, offset);
+}
+
+int uno_dft3d_forward_grouped(const float* x, float* spec, void* ws, int n_vol, int D1, int D2, int D3, int m1, int m2, int m3, float scale,
+                              int adjoint, int group, int stride, int offset, void* stream) {
+    return dft3d_stage("uno_dft3d_forward_grouped", false, x, spec, ws, n_vol, D1, D2, D3, m1, m2, m3, scale, adjoint, group, stride, offset, stream);
+}
+
+int uno_dft3d_inverse_grouped(const float* spec, float* y, void* ws, int n_vol, int D1, int D2, int D3, int m1, int m2, int m3, float scale,
+                              int weighted, int group, int stride, int offset, void* stream) {
+    return dft3d_stage("uno_dft3d_inverse_grouped", true, spec, y, ws, n_vol, D1, D2, D3, m1, m2, m3, scale, weighted, group, stride, offset, stream);
+}
+
+// ---- the 3-D layer on the channel concatenation of two tensors, never built: each source is transformed into (out of) its channel
+// range of the one spectrum tensor by the kernels the concatenation would run (n_decide = B * Ci: results bit-equal to the one-source
+// call on the concatenation); the per-mode GEMMs and the other transform are the one-source calls'
+static int check_two_sources(const char* who, int C1, int Ci) {
+    if (C1 < 1 || C1 >= Ci) { set_error("%s: C1=%d must satisfy 0 < C1 < Ci=%d", who, C1, Ci); return -1; }
+    return 0;
+}
+
+int uno_spectral_conv3d_forward2(const float* x1, const float* x2, int C1, const float* const* w, float* y, float* xtrunc, void* ws, int B,
+                                 int Ci, int Co, int H, int W, int T, int Ho, int Wo, int To, int m1, int m2, int m3, void* stream) {
+    const char* who = "uno_spectral_conv3d_forward2";
+    if (!x2) return uno_spectral_conv3d_forward(x1, w, y, xtrunc, ws, B, Ci, Co, H, W, T, Ho, Wo, To, m1, m2, m3, stream);
+    if (B < 0 || Ci < 1 || Co < 1) { set_error("%s: bad sizes B=%d Ci=%d Co=%d", who, B, Ci, Co); return -1; }
+    if (int rc = check_two_sources(who, C1, Ci)) return rc;
+    if (int rc = check_modes3d(who, H, W, T, Ho, Wo, To, m1, m2, m3)) return rc;
+    if (B == 0) return 0;
+    if (!x1 || !w || !y || !xtrunc || !ws) { set_error("%s: null pointer", who); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    const long long C = 2LL * m2 * m3, Mc = (long long)m1 * m2 * m3;
+    const int C2 = Ci - C1;
+    float* Z1 = static_cast<float*>(ws);                         // (B*C1*H | B*C2*H, 2 m2, m3) c64: one part per source
+    float* Z1b = Z1 + 2LL * B * C1 * H * C;
+    float* Z2 = Z1 + 2LL * B * Ci * H * C;                        // (B*Co*Ho, 2 m2, m3) c64
+    float* O5 = Z2 + 2LL * B * Co * Ho * C;                       // (B, Co, 4, m1, m2, m3) c64
+    const float inv_n = 1.0f / ((float)H * (float)W * (float)T);
+    if (int rc = fwd_transform3d(x1, xtrunc, Z1, B * C1, H, W, T, m1, m2, m3, inv_n, 0, s, C1, Ci, 0, B * Ci)) return rc;
+    if (int rc = fwd_transform3d(x2, xtrunc, Z1b, B * C2, H, W, T, m1, m2, m3, inv_n, 0, s, C2, Ci, C1, B * Ci)) return rc;
+    if (int rc = uno_mode_mix(xtrunc, w, O5, 0, B, Ci, Co, 4, (int)Mc, stream)) return rc;
+    return inv_transform3d(O5, y, Z2, B * Co, Ho, Wo, To, m1, m2, m3, 1.0f, 1, s);
+}
+
+int uno_spectral_conv3d_backward2(const float* gy, const float* xtrunc, const float* const* w, float* gx1, float* gx2, int C1,
+                                  float* const* gw, void* ws, int B, int Ci, int Co, int H, int W, int T, int Ho, int Wo, int To, int m1,
+                                  int m2, int m3, void* stream) {
+    const char* who = "uno_spectral_conv3d_backward2";
+    if (!gx2) return uno_spectral_conv3d_backward(gy, xtrunc, w, gx1, gw, ws, B, Ci, Co, H, W, T, Ho, Wo, To, m1, m2, m3, stream);
+    if (B < 0 || Ci < 1 || Co < 1) { set_error("%s: bad sizes B=%d Ci=%d Co=%d", who, B, Ci, Co); return -1; }
+    if (int rc = check_two_sources(who, C1, Ci)) return rc;
+    if (int rc = check_modes3d(who, H, W, T, Ho, Wo, To, m1, m2, m3)) return rc;
+    if (!gx1) { set_error("%s: null pointer gx1 (gx2 is given)", who); return -1; }
+    if (gx1 == gx2) { set_error("%s: gx1 must not alias gx2", who); return -1; }
+    hipStream_t s = (hipStream_t)stream;
+    const long long C = 2LL * m2 * m3, Mc = (long long)m1 * m2 * m3;
+    if (B == 0) {
+        if (gw)
+            for (int c = 0; c < 4; ++c)
+                if (hipMemsetAsync(gw[c], 0, 8ULL * Ci * Co * Mc, s) != hipSuccess) { set_error("memset failed"); return -5; }
+        return 0;
+    }
+    if (!gy || !xtrunc || !w || !ws) { set_error("%s: null pointer", who); return -1; }
+    const int C2 = Ci - C1;
+    float* Z1 = static_cast<float*>(ws);
+    float* Z1b = Z1 + 2LL * B * C1 * H * C;
+    float* Z2 = Z1 + 2LL * B * Ci * H * C;
+    float* gO = Z2 + 2LL * B * Co * Ho * C;
+    float* gX = gO + 2LL * B * Co * 4 * Mc;
+    if (int rc = fwd_transform3d(gy, gO, Z2, B * Co, Ho, Wo, To, m1, m2, m3, 1.0f, 1, s)) return rc;
+    if (gw)
+        if (int rc = uno_mode_wgrad(xtrunc, gO, gw, B, Ci, Co, 4, (int)Mc, stream)) return rc;
+    if (int rc = uno_mode_mix(gO, w, gX, 1, B, Ci, Co, 4, (int)Mc, stream)) return rc;
+    const float inv_n = 1.0f / ((float)H * (float)W * (float)T);
+    if (int rc = inv_transform3d(gX, gx1, Z1, B * C1, H, W, T, m1, m2, m3, inv_n, 0, s, C1, Ci, 0, B * Ci)) return rc;
+    return inv_transform3d(gX, gx2, Z1b, B * C2, H, W, T, m1, m2, m3, inv_n, 0, s, C2, Ci, C1, B * Ci);
 }
 
 static int spectral_conv2d_forward(const float* x, const float* w1, const float* w2, float* y, float* xtrunc, void* ws,

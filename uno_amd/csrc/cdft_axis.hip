@@ -77,7 +77,7 @@ __global__ __launch_bounds__(256) void cdft_fwd_kernel(CdftParams p) {
         }
     }
     if (!cvalid) return;
-    float2* out = reinterpret_cast<float2*>(p.out) + (size_t)blockIdx.x * 4 * m1 * p.m2 * p.m3;
+    float2* out = reinterpret_cast<float2*>(p.out) + grouped_volume(blockIdx.x, p.sp_group, p.sp_stride, p.sp_offset) * 4 * m1 * p.m2 * p.m3;
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
@@ -106,7 +106,7 @@ __global__ __launch_bounds__(256) void cdft_inv_kernel(CdftParams p) {
     const bool cvalid = c < C;
     const unsigned H8 = 8u * H;
     constexpr int KSJ = 4 * JT;
-    const float2* in = reinterpret_cast<const float2*>(p.in) + (size_t)blockIdx.x * 4 * m1 * p.m2 * p.m3;
+    const float2* in = reinterpret_cast<const float2*>(p.in) + grouped_volume(blockIdx.x, p.sp_group, p.sp_stride, p.sp_offset) * 4 * m1 * p.m2 * p.m3;
 
     // B operand, resident for the whole image: O[j = 4 ks + kk][c]
     float Or[KSJ], Oi[KSJ];

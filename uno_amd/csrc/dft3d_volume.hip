@@ -434,7 +434,8 @@ __global__ __launch_bounds__(64 * VF_WAVES) void dft3d_fwd_volume_kernel(Vol3dPa
     // ---- phase 2: leading axis out of LDS, blocks of 16 complex columns dealt to the waves.  A lane owns one complex column
     // (re and im are two MFMA column tiles), so i S needs no lane exchange and a row of the result leaves as 128 contiguous bytes.
     // (results leave through raw buffer stores: columns / rows outside the spectrum carry an out-of-range offset and are dropped)
-    float2* out = reinterpret_cast<float2*>(p.out) + (size_t)vol * (size_t)(4 * m1 * m2 * m3);            // 4 corners x m1 m2 m3 complex
+    // (a grouped placement moves the resource's base, once per workgroup: the stores below keep their offsets and a zero scalar offset)
+    float2* out = reinterpret_cast<float2*>(p.out) + grouped_volume(vol, p.sp_group, p.sp_stride, p.sp_offset) * (size_t)(4 * m1 * m2 * m3);      // 4 corners x m1 m2 m3 complex
     constexpr unsigned OOB = 0xC0000000u;
     typedef unsigned u32x2v __attribute__((ext_vector_type(2)));
     const unsigned rowbytes = (unsigned)(m2 * m3) * 8u, cbytes = (unsigned)m1 * rowbytes;
@@ -626,7 +627,7 @@ __global__ __launch_bounds__(64 * VI_WAVES) void dft3d_inv_volume_kernel(Vol3dPa
     // ---- phase 1: leading axis.  A lane owns one complex column of the volume's spectrum (16 of them per block): 8-byte loads,
     // i Dk and the untwist without lane exchange, 8-byte LDS writes.
     const int vol = blockIdx.x;
-    const float2* O = reinterpret_cast<const float2*>(p.in) + (size_t)vol * (size_t)(4 * m1 * m2 * m3);
+    const float2* O = reinterpret_cast<const float2*>(p.in) + grouped_volume(vol, p.sp_group, p.sp_stride, p.sp_offset) * (size_t)(4 * m1 * m2 * m3);
     const size_t cstride = (size_t)m1 * m2 * m3;                                 // complex elements per corner
     int rowI[MTS][4], rowN[MTS][4];                                              // LDS rows (float offsets) of slot i and its partner; < 0: none
 #pragma unroll

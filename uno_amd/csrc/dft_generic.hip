@@ -157,7 +157,7 @@ __global__ __launch_bounds__(256) void gen_cdft_kernel(CdftParams p, int inverse
         const int K = p.rowfreq ? p.rowfreq[j] : corner_freq(j, m1, H);
         const float f = (p.mask && !p.rowfreq && !row_survives(j, m1, H)) ? 0.f : p.scale;
         const float2* in = reinterpret_cast<const float2*>(p.in) + (size_t)img * H * C;
-        float2* out = reinterpret_cast<float2*>(p.out) + (size_t)img * 4 * m1 * p.m2 * p.m3;
+        float2* out = reinterpret_cast<float2*>(p.out) + grouped_volume(img, p.sp_group, p.sp_stride, p.sp_offset) * 4 * m1 * p.m2 * p.m3;
         for (int c = threadIdx.x; c < C; c += blockDim.x) {
             float ar = 0.f, ai = 0.f;
             int idx = 0;
@@ -172,7 +172,7 @@ __global__ __launch_bounds__(256) void gen_cdft_kernel(CdftParams p, int inverse
     } else {
         // one workgroup per (volume, plane h): Z[h][c] = sum_j keep_j O[j][c] exp(+i theta_j h)
         const int img = blockIdx.x / H, h = blockIdx.x - img * H;
-        const float2* in = reinterpret_cast<const float2*>(p.in) + (size_t)img * 4 * m1 * p.m2 * p.m3;
+        const float2* in = reinterpret_cast<const float2*>(p.in) + grouped_volume(img, p.sp_group, p.sp_stride, p.sp_offset) * 4 * m1 * p.m2 * p.m3;
         float2* out = reinterpret_cast<float2*>(p.out) + ((size_t)img * H + h) * C;
         for (int c = threadIdx.x; c < C; c += blockDim.x) {
             float ar = 0.f, ai = 0.f;

@@ -239,7 +239,17 @@ struct CdftParams {
     float scale = 1.f;
     int mask = 0;           // zero lo-corner rows overwritten by the hi corner (on the spectrum side)
     const int* rowfreq = nullptr;     // optional: frequency of spectrum row j, j < 2*m1, instead of the corner rule
+    // placement of the corner-major spectra (the side that is not (n_img, H, C)): volume i <-> spectrum volume
+    // (i / sp_group) * sp_stride + sp_offset + i % sp_group; sp_group <= 0: plain (spectrum volume i)
+    int sp_group = 0, sp_stride = 0, sp_offset = 0;
 };
+
+// The spectrum volume of volume `vol` under the grouped placement of CdftParams / Vol3dParams.  Callers pass a workgroup-uniform `vol`
+// (from blockIdx) and fold the result into the spectrum's base pointer / buffer resource once per workgroup.
+__host__ __device__ __forceinline__ size_t grouped_volume(int vol, int group, int stride, int offset) {
+    if (group <= 0) return (size_t)vol;
+    return (size_t)(vol / group) * (size_t)stride + (size_t)offset + (size_t)(vol % group);
+}
 
 // One workgroup per (sample, channel) volume: all three pruned transforms of the 3-D layer (dft3d_volume.hip).
 struct Vol3dParams {
@@ -252,6 +262,7 @@ struct Vol3dParams {
     float scale = 1.f;
     int herm = 0;           // 1: multiply T-mode l by the Hermitian weight c_l of D3
     const float* ctab = nullptr;      // host-built operand table of the kernel (filled in by the launcher)
+    int sp_group = 0, sp_stride = 0, sp_offset = 0;       // placement of the spectra (K1v: out, K3v: in), as in CdftParams
 };
 
 const float2* twiddle_table(int N);      // device-resident, cached per (device, N); nullptr on failure

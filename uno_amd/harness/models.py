@@ -36,6 +36,22 @@ def enable_native_ends_3d(model: nn.Module, enabled: bool = True) -> nn.Module:
     return model
 
 
+# The INNER skip connections of the NS-3D models (the inputs of conv7 and conv8 of the seven-block models, of their counterparts in the
+# nine-block ones) without torch.cat: the next block takes (its predecessor's output, the resized skip tensor) where they lie
+# (OperatorBlock_3D.forward_cat).  The last skip (into fc1) is NATIVE_ENDS_3D's.  Opt-in like that switch: the default (False) leaves every
+# model on the stock concatenation bit for bit; a single model opts in through its `cat_free_skips` attribute
+# (enable_cat_free_skips_3d).  Product blocks on float32 device tensors only.
+CAT_FREE_SKIPS_3D = False
+
+
+def enable_cat_free_skips_3d(model: nn.Module, enabled: bool = True) -> nn.Module:
+    """Opt the NS-3D models inside `model` into two-source blocks for their inner skip connections (sets `cat_free_skips`)."""
+    for m in model.modules():
+        if isinstance(m, Uno3D_T20):
+            m.cat_free_skips = bool(enabled)
+    return model
+
+
 def _block_cat(block, xs, *dims):
     """block(torch.cat(xs, dim=1), *dims); product blocks take the sources as they are."""
     if hasattr(block, "forward_cat"):
@@ -311,6 +327,13 @@ class Uno3D_T20(nn.Module):
         return bool((NATIVE_ENDS_3D or self.native_ends) and x.is_cuda and x.dtype == torch.float32
                     and isinstance(getattr(self, self._NAMES[-1]), OperatorBlock_3D))
 
+    cat_free_skips = False      # enable_cat_free_skips_3d: the inner skip connections through OperatorBlock_3D.forward_cat
+
+    def _cat_free_skips(self, x):
+        """the opted-in inner skips apply: switch or attribute on, product blocks, device tensors"""
+        return bool((CAT_FREE_SKIPS_3D or self.cat_free_skips) and x.is_cuda and x.dtype == torch.float32
+                    and all(isinstance(getattr(self, n), OperatorBlock_3D) for n in self._NAMES))
+
     @staticmethod
     def _resize(t, like):
         # the reference resizes every skip tensor with trilinear / align_corners (navier_stokes_uno3d.py:352-372); on the
@@ -332,10 +355,16 @@ class Uno3D_T20(nn.Module):
         g, crop = self._plan(*lifted.shape[-3:], self.padding)
         outs, c8 = {None: lifted}, lifted
         last = self._NAMES[-1]
+        cat_free, skip = self._cat_free_skips(x), None      # skip: the resized tensor the next block takes as its second source
         for name, grid in zip(self._NAMES, g):
-            c8 = outs[name] = getattr(self, name)(c8, *grid)
+            block = getattr(self, name)
+            c8 = outs[name] = block(c8, *grid) if skip is None else _block_cat(block, (c8, skip), *grid)
+            skip = None
             if name in self._SKIPS and not (native and name == last):
-                c8 = torch.cat([c8, self._resize(outs[self._SKIPS[name]], c8)], dim=1)
+                if cat_free and name != last:
+                    skip = self._resize(outs[self._SKIPS[name]], c8)
+                else:
+                    c8 = torch.cat([c8, self._resize(outs[self._SKIPS[name]], c8)], dim=1)
         if native:      # fc1 on the two sources of the last skip connection, through the time window the crop keeps
             Tp = c8.shape[-1]
             window = None if self.padding == 0 else (crop, Tp - 2 * crop) if self.pad_both else (0, Tp - crop)

@@ -32,7 +32,7 @@ from .block2d import SpectrumShare, _OperatorBlock2dCatFn, _OperatorBlock2dFn, _
 from .pointwise import (GradJoin, _dev_act, channel_mix, channel_mix_cat, channel_mix_cat_project, gelu_channel_mix, gelu_channel_mix_pad,
                         gelu_pad2d, gelu_project, gelu_project2, instance_norm_gelu, lift_gelu_pad)
 from .resample import resample2d_bicubic_aa
-from .spectral3d import (RESAMPLE3D_FAMILIES, _OperatorBlock3dFn, _resample3d_plan, _resample3d_plan_any, _resample3d_plan_wide, spectral_conv3d)
+from .spectral3d import (RESAMPLE3D_FAMILIES, _OperatorBlock3dCatFn, _OperatorBlock3dFn, _resample3d_plan, _resample3d_plan_any, _resample3d_plan_wide, spectral_conv3d)
 
 __all__ = [
     "enable_mixed_precision", "enable_native_resample3d_any", "enable_native_resample3d_wide", "enable_one_buffer_any_grid", "GradJoin", "SpectrumShare", "channel_mix_cat_project", "release_pass_state",
@@ -404,13 +404,38 @@ class OperatorBlock_3D(nn.Module):
             out = F.gelu(out)
         return out
 
+    def forward_cat(self, xs, dim1=None, dim2=None, dim3=None):
+        """self(torch.cat(xs, dim=1), dim1, dim2, dim3) for a skip connection (reference navier_stokes_uno3d.py: the inputs of the
+        up-sampling blocks) - two float32 device tensors of equal batch and grid whose channels sum to in_channels, on a grid where
+        forward() would take the one-buffer form, are consumed where they lie (_OperatorBlock3dCatFn): the concatenation is never
+        built.  Anything else is forward() on the concatenation."""
+        xs = list(xs)
+        fused = None
+        if (len(xs) == 2 and all(x.is_cuda and x.dtype == torch.float32 and x.dim() == 5 for x in xs) and xs[0].device == xs[1].device
+                and xs[0].shape[0] == xs[1].shape[0] and xs[0].shape[2:] == xs[1].shape[2:]
+                and xs[0].shape[1] >= 1 and xs[1].shape[1] >= 1):
+            fused = self._fused(xs, dim1, dim2, dim3)
+        if fused is None:
+            return self.forward(torch.cat(xs, dim=1), dim1, dim2, dim3)
+        out, activated = fused
+        if self.normalize:
+            return instance_norm_gelu(out, self.normalize_layer, self.non_lin)
+        return out if (activated or not self.non_lin) else F.gelu(out)
+
     def _fused(self, x, dim1, dim2, dim3):
         """(conv(x) + w(x) [activated], whether the GELU has been applied) through the one-buffer form, or None when the layer has to take
         the two branches separately (CPU tensors, other dtypes, mismatched grids, grids outside the pruned-DFT resampling kernels' range
         unless the block is opted into the one-buffer form there - `one_buffer_any_grid` / ONE_BUFFER_3D_ANY - and its point-wise layer
-        into the any-grid or the wide-axis kernels, see _resample3d_kernels)."""
+        into the any-grid or the wide-axis kernels, see _resample3d_kernels).  x: the input, or the list of forward_cat's two sources,
+        which then go through the two-source form (_OperatorBlock3dCatFn) under the same conditions."""
         conv, w = self.conv, self.w
-        if not (ONE_BUFFER_3D and x.is_cuda and x.dtype == torch.float32 and x.dim() == 5 and x.shape[1] == conv.in_channels
+        pair =x if isinstance(x, list) else None           # forward_cat: two sources it has checked against each other
+        if pair is not None:
+            x = pair[0]
+            channels = pair[0].shape[1] + pair[1].shape[1]
+        else:
+            channels = x.shape[1] if x.dim() == 5 else -1
+        if not (ONE_BUFFER_3D and x.is_cuda and x.dtype == torch.float32 and x.dim() == 5 and channels == conv.in_channels
                 and w.conv.weight.dtype == torch.float32):
             return None
         if dim1 is not None:        # the spectral layer keeps a call-time override, the point-wise one does not (:391-394, :444-446)
@@ -426,6 +451,10 @@ class OperatorBlock_3D(nn.Module):
         if dim1 is not None:
             conv.dim1, conv.dim2, conv.dim3 = dim1, dim2, dim3
         gelu = self.non_lin and not self.normalize
+        if pair is not None:
+            out = _OperatorBlock3dCatFn.apply(pair[0], pair[1], conv.weights1, conv.weights2, conv.weights3, conv.weights4, w.conv.weight,
+                                              w.conv.bias, dims, plan, gelu, family)
+            return out, gelu
         out = _OperatorBlock3dFn.apply(x, conv.weights1, conv.weights2, conv.weights3, conv.weights4, w.conv.weight, w.conv.bias,
                                        dims, plan, gelu, family)
         return out, gelu

@@ -2,14 +2,14 @@
 integral_operators.py:385-427): rfftn over (H, W, T) restricted to the four low-frequency corners ->
 per-mode channel mixing with weights1..4 -> zero-padded irfftn, with a custom autograd adjoint that
 saves only the truncated input spectrum.  Also pointwise_op_3D's FFT resampling on the pruned-DFT, the any-grid and the wide-axis kernels
-(plans + Functions) and the 3-D operator block in one buffer."""
+(plans + Functions) and the 3-D operator block in one buffer, on one tensor or on the two sources of a skip connection."""
 from __future__ import annotations
 
 import torch
 from torch.autograd.function import once_differentiable
 
 from . import _native
-from .pointwise import _plain, _wgrad_into
+from .pointwise import _mix2_forward, _mix2_input_grads, _plain, _wgrad_into
 
 
 def _dense(t):         # (torch's strided copy for every layout; the one-buffer block below goes through pointwise._plain)
@@ -229,3 +229,68 @@ class _OperatorBlock3dFn(torch.autograd.Function):
                 gcw, gcb = _wgrad_into(ctx.leaves, g_t, x.view(B, Ci, -1), None, ctx.needs_input_grad[5], has_bias and ctx.needs_input_grad[6])
                 gcw = None if gcw is None else gcw.view(cw_shape)
         return (gx, *gws, gcw, gcb, None, None, None, None)
+
+
+class _OperatorBlock3dCatFn(torch.autograd.Function):
+    """_OperatorBlock3dFn on torch.cat([x1, x2], dim=1), never built (the inner skip connections of the NS-3D models, reference
+    navier_stokes_uno3d.py `torch.cat([x_c, skip], dim=1)` ahead of an OperatorBlock_3D).
+
+    Spectral branch: each source is transformed into its channel range of the one truncated spectrum, and its gradient out of its range of
+    the gradient spectrum (uno_spectral_conv3d_forward2 / _backward2).  1x1x1 convolution: the two-source channel-mix calls of
+    pointwise.py (one launch where the sources split at a multiple of 16 / 64 channels, two accumulating one-source launches
+    otherwise).  The resample and the accumulate / GELU epilogue are the one-source Function's.  Both sources are saved as they are."""
+
+    @staticmethod
+    def forward(ctx, x1, x2, w1, w2, w3, w4, cw, cb, dims, plan, fuse_gelu, family):
+        ctx.leaves = (cw, cb)
+        resample = RESAMPLE3D_FAMILIES[family][1]
+        x1, x2 = _plain(x1), _plain(x2)
+        ws = [_plain(w) for w in (w1, w2, w3, w4)]
+        B, C1, C2 = x1.shape[0], x1.shape[1], x2.shape[1]
+        din = tuple(x1.shape[2:])
+        Co = cw.shape[0]
+        cwm = _plain(cw).reshape(Co, C1 + C2)
+        cbp = None if cb is None else _plain(cb)
+        s, xt = _native.spectral_conv3d_forward2(x1, x2, ws, *dims)
+        t = _mix2_forward(x1.view(B, C1, -1), x2.view(B, C2, -1), cwm, cbp).view(B, Co, *din)
+        t1, t2, m3 = plan
+        scale = 1.0 / (dims[0] * dims[1] * dims[2])
+        if fuse_gelu:
+            s, out = resample(t, dims, (t1, t1), (t2, t2), m3, scale, adjoint=False, out=s, act=True)
+        else:
+            out = resample(t, dims, (t1, t1), (t2, t2), m3, scale, adjoint=False, out=s)
+        ctx.save_for_backward(xt, *ws, cwm, x1, x2, s if fuse_gelu else None)
+        ctx.geom = (din, tuple(dims), plan, cb is not None, tuple(cw.shape), resample)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        xt, w1, w2, w3, w4, cwm, x1, x2, pre = ctx.saved_tensors
+        din, dims, plan, has_bias, cw_shape, resample = ctx.geom
+        g = _plain(g)
+        if pre is not None:
+            g = torch.ops.aten.gelu_backward(g, pre)
+        B, Co = g.shape[0], g.shape[1]
+        C1, C2 = x1.shape[1], x2.shape[1]
+        need_gx = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        need_gw = any(ctx.needs_input_grad[2:6])
+        need_gc = ctx.needs_input_grad[6] or (has_bias and ctx.needs_input_grad[7])
+        gx1, gx2, gws = _native.spectral_conv3d_backward2(g, xt, [w1, w2, w3, w4], C1, *din, need_gx=need_gx, need_gw=need_gw)
+        gws = gws or [None] * 4
+        gcw = gcb = None
+        if need_gx or need_gc:
+            t1, t2, m3 = plan
+            scale = 1.0 / (dims[0] * dims[1] * dims[2])
+            g_t = resample(g, din, (t1, t1), (t2, t2), m3, scale, adjoint=True).view(B, Co, -1)
+            if need_gx:         # accumulates into the spectral branch's gx1 / gx2
+                _mix2_input_grads(g_t, cwm, C1, out1=gx1.view(B, C1, -1), out2=gx2.view(B, C2, -1))
+            if need_gc:
+                gcw, gcb = _wgrad_into(ctx.leaves, g_t, x1.view(B, C1, -1), x2.view(B, C2, -1), ctx.needs_input_grad[6],
+                                       has_bias and ctx.needs_input_grad[7])
+                gcw = None if gcw is None else gcw.view(cw_shape)
+        if not ctx.needs_input_grad[0]:
+            gx1 = None
+        if not ctx.needs_input_grad[1]:
+            gx2 = None
+        return (gx1, gx2, *gws, gcw, gcb, None, None, None, None)
