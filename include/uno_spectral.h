@@ -719,6 +719,32 @@ int uno_channel_mix_act_padded_rows(const float* x, const float* w, const float*
 int uno_dgelu_rows(const float* pre, const float* g_padded, float* gz, long long n_planes, int rows, int cols, int pitch, int col0,
                    long long plane, void* stream);
 
+/* K22 (additive, ABI 14): the 2-D Navier-Stokes pseudo-spectral solver of the reference's data generator (Data Generation/Navier Stocks/
+ * ns_datagen.py:15-140, vorticity form, Crank-Nicolson in time), whose torch.rfft / torch.irfft calls no current PyTorch has.
+ * State: the half spectrum w_h (B, N, N/2 + 1) c64, interleaved, un-normalised like fft2 - the reference's irfft(onesided=False) reads
+ * columns 0 ... N/2 of its full spectrum only, so nothing else ever influences an output.  f32; N a power of two in 32 ... 256; B >= 0,
+ * B * N below 2^31.  ws: uno_ns2d_ws_bytes(B, N) = 5 * 8 * B * N * (N/2 + 1) bytes of scratch, which a call need not find initialised
+ * (0 for sizes outside the range).  Every sum is a dense length-N sum on v_mfma_f32_16x16x4_f32 in a fixed order, and a sample's
+ * arithmetic does not depend on B: two runs, a run split into two calls and a sample inside any batch give the same bits.  No entry
+ * point synchronises, allocates or reads back (the (cos, sin) table of N is uploaded once per device as every transform here does, safe
+ * under graph capture).  Offsets are 64-bit.  B == 0 or n_steps == 0: success, no launch.
+ *   uno_ns2d_forward: w (B, N, N) f32 -> w_h = rfft2(w) (ns_datagen.py:26, 29: the initial vorticity and the forcing).  2 launches.
+ *   uno_ns2d_inverse: w_h -> w (B, N, N) f32 = irfft2(w_h, s = (N, N)) (ns_datagen.py:125-127: a recorded snapshot): complex inverse along
+ *     axis 0, then half spectrum -> real along axis 1 with the imaginary parts of columns 0 and N/2 ignored, 1 / N^2.  w_h is only read.
+ *     2 launches.
+ *   uno_ns2d_steps: n_steps time steps of ns_datagen.py:67-118 on w_h in place, 3 launches each from one loop: wave numbers
+ *     [0 ... N/2-1, -N/2 ... -1] on both axes, the Nyquist row and column carrying k = -N/2 in the derivative multipliers and in
+ *     lap = 4 pi^2 (kx^2 + ky^2) (not zeroed), lap[0,0] = 1, the dealias mask |k| <= (2/3)(N/2) on both axes on the non-linear term only,
+ *     w_h <- (-dt F_h + dt f_h + (1 - dt visc lap / 2) w_h) / (1 + dt visc lap / 2).  f_h: the forcing's half spectrum (uno_ns2d_forward of
+ *     f), (N, N/2 + 1) c64 shared by the batch (f_batched = 0) or (B, N, N/2 + 1) (f_batched != 0); must not alias w_h.
+ * Errors (-1, before any launch): null pointers, N not a power of two or outside 32 ... 256, B < 0 or too large, n_steps < 0, delta_t not
+ * finite or not positive, visc negative or not finite. */
+long long uno_ns2d_ws_bytes(int B, int N);
+int uno_ns2d_forward(const float* w, float* w_h, void* ws, int B, int N, void* stream);
+int uno_ns2d_inverse(const float* w_h, float* w, void* ws, int B, int N, void* stream);
+int uno_ns2d_steps(float* w_h, const float* f_h, int f_batched, void* ws, int B, int N, long long n_steps, double visc, double delta_t,
+                   void* stream);
+
 /* Optional in-library kernel timing (HIP events recorded on the launch stream around every kernel
  * this library enqueues), used by bench.py for the live roofline figure.
  *   uno_profile_begin(max_records): start recording (drops records beyond max_records).

@@ -140,6 +140,10 @@ _SIGNATURES = {
     "uno_channel_wgrad2_rows": (C.c_int, [_fp, _fp, _fp, _i, _fp, _fp, _fp] + [_i] * 7 + [C.c_longlong, _i, _i, _fp]),
     "uno_channel_mix_act_padded_rows": (C.c_int, [_fp] * 5 + [_i] * 8 + [_fp]),
     "uno_dgelu_rows": (C.c_int, [_fp, _fp, _fp, C.c_longlong, _i, _i, _i, _i, C.c_longlong, _fp]),
+    "uno_ns2d_ws_bytes": (C.c_longlong, [_i, _i]),
+    "uno_ns2d_forward": (C.c_int, [_fp, _fp, _fp, _i, _i, _fp]),
+    "uno_ns2d_inverse": (C.c_int, [_fp, _fp, _fp, _i, _i, _fp]),
+    "uno_ns2d_steps": (C.c_int, [_fp, _fp, _i, _fp, _i, _i, C.c_longlong, C.c_double, C.c_double, _fp]),
     "uno_profile_begin": (C.c_int, [_i]),
     "uno_profile_end": (C.c_int, []),
     "uno_profile_get": (C.c_int, [_i, C.c_char_p, _i, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
@@ -1853,6 +1857,77 @@ class AdamPlan:
                                                weight_decay, _ptr(counter), _ptr(scalars), _opt(hyper),
                                                C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
         _check(rc, "uno_adam_step_multi_dev")
+
+
+NS2D_SIZES = (32, 64, 128, 256)
+
+
+def ns2d_supported(N: int) -> bool:
+    """True for the grid sizes the K22 kernels take: a power of two in 32 ... 256"""
+    return N in NS2D_SIZES
+
+
+def ns2d_workspace(B: int, N: int, device):
+    """the scratch of the three ns2d calls for (B, N): uint8, uno_ns2d_ws_bytes(B, N) bytes, uninitialised"""
+    return torch.empty(max(1, int(lib().uno_ns2d_ws_bytes(int(B), int(N)))), dtype=torch.uint8, device=device)
+
+
+def _ns2d_args(t, dtype, name, ws):
+    """(B, N, workspace) of a state (B, N, N/2 + 1) c64 or a field (B, N, N) f32"""
+    _require(t, dtype, name)
+    if t.dim() != 3 or t.shape[2] != (t.shape[1] if dtype == torch.float32 else t.shape[1] // 2 + 1):
+        raise RuntimeError(f"uno_amd: {name} must be " + ("(B, N, N) float32" if dtype == torch.float32 else "(B, N, N/2 + 1) complex64")
+                           + f" (got {tuple(t.shape)})")
+    B, N = int(t.shape[0]), int(t.shape[1])
+    if not ns2d_supported(N):
+        raise RuntimeError(f"uno_amd: the native Navier-Stokes solver takes N in {NS2D_SIZES} (a power of two in 32 ... 256), got N={N}")
+    if ws is None:
+        ws = ns2d_workspace(B, N, t.device)
+    else:
+        _require(ws, torch.uint8, "workspace")
+        if ws.numel() < lib().uno_ns2d_ws_bytes(B, N):
+            raise RuntimeError("uno_amd: workspace smaller than uno_ns2d_ws_bytes(B, N)")
+    return B, N, ws
+
+
+def ns2d_forward(w, out=None, ws=None):
+    """w (B, N, N) f32 -> rfft2(w) (B, N, N/2 + 1) c64 (uno_ns2d_forward, K22); out / ws: the result / scratch tensors to use"""
+    B, N, ws = _ns2d_args(w, torch.float32, "w", ws)
+    w_h = torch.empty((B, N, N // 2 + 1), dtype=torch.complex64, device=w.device) if out is None else out
+    _require(w_h, torch.complex64, "w_h")
+    if tuple(w_h.shape) != (B, N, N // 2 + 1):
+        raise RuntimeError("uno_amd: w_h has the wrong shape")
+    with torch.cuda.device(w.device):
+        rc = lib().uno_ns2d_forward(_ptr(w), _ptr(w_h), _ptr(ws), B, N, _stream(w))
+    _check(rc, "uno_ns2d_forward")
+    return w_h
+
+
+def ns2d_inverse(w_h, out=None, ws=None):
+    """w_h (B, N, N/2 + 1) c64 -> irfft2(w_h, s=(N, N)) (B, N, N) f32 (uno_ns2d_inverse, K22); w_h is only read"""
+    B, N, ws = _ns2d_args(w_h, torch.complex64, "w_h", ws)
+    w = torch.empty((B, N, N), dtype=torch.float32, device=w_h.device) if out is None else out
+    _require(w, torch.float32, "w")
+    if tuple(w.shape) != (B, N, N):
+        raise RuntimeError("uno_amd: w has the wrong shape")
+    with torch.cuda.device(w_h.device):
+        rc = lib().uno_ns2d_inverse(_ptr(w_h), _ptr(w), _ptr(ws), B, N, _stream(w_h))
+    _check(rc, "uno_ns2d_inverse")
+    return w
+
+
+def ns2d_steps(w_h, f_h, n_steps: int, visc: float, delta_t: float, ws=None):
+    """n_steps Crank-Nicolson steps of the reference's navier_stokes_2d on the state w_h (B, N, N/2 + 1) c64, in place (uno_ns2d_steps,
+    K22: three launches per step from one C loop).  f_h: the forcing's half spectrum, (N, N/2 + 1) shared or (B, N, N/2 + 1) per sample."""
+    B, N, ws = _ns2d_args(w_h, torch.complex64, "w_h", ws)
+    _require(f_h, torch.complex64, "f_h")
+    if tuple(f_h.shape) not in ((N, N // 2 + 1), (B, N, N // 2 + 1)) or f_h.device != w_h.device:
+        raise RuntimeError(f"uno_amd: f_h must be ({N}, {N // 2 + 1}) or ({B}, {N}, {N // 2 + 1}) complex64 on the state's device")
+    with torch.cuda.device(w_h.device):
+        rc = lib().uno_ns2d_steps(_ptr(w_h), _ptr(f_h), 1 if f_h.dim() == 3 else 0, _ptr(ws), B, N, int(n_steps), float(visc), float(delta_t),
+                                  _stream(w_h))
+    _check(rc, "uno_ns2d_steps")
+    return w_h
 
 
 def profile_begin(max_records: int = 100000):

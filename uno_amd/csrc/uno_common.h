@@ -349,6 +349,13 @@ void resample3d_wide_lds_bytes(int D1, int D2, int D3, int M1, int M2, int M3, i
 int launch_resample3d_wide(const float* x, float* y, float* y_act, int accumulate, void* ws, int n_vol, int D1, int D2, int D3, int M1, int M2, int M3,
                            int J1, const int* f1_in, const int* f1_out, int J2, const int* f2_in, const int* f2_out, int m3, float scale,
                            int herm_in, int herm_out, hipStream_t s);
+// ns2d_solver.hip (K22): the reference data generator's 2-D Navier-Stokes solver on a half-spectrum state (B, N, N/2 + 1) c64, N a power of
+// two in 32 ... 256 (arguments validated by the caller); ws: ns2d_ws_bytes(B, N) bytes
+long long ns2d_ws_bytes(int B, int N);
+int launch_ns2d_forward(const float* w, float* w_h, void* ws, int B, int N, hipStream_t s);
+int launch_ns2d_inverse(const float* w_h, float* w, void* ws, int B, int N, hipStream_t s);
+int launch_ns2d_steps(float* w_h, const float* f_h, int f_batched, void* ws, int B, int N, long long n_steps, double visc, double delta_t,
+                      hipStream_t s);
 int launch_resample2d(const void* in, void* out, float* tmp, int n_img, int H, int W, int Ho, int Wo, const int* startH,
                       const float* wtH, int KH, const int* startW, const float* wtW, int KW, const int* tile_p0,
                       const float* tile_w, int NP, int accumulate, int bf16, hipStream_t s);
