@@ -2,7 +2,7 @@
 HIP kernels (uno_fft_resample3d_any) and through STOCK_FFT_RESAMPLE3D = True (torch.fft: what a user of these layers ran before),
 and one Uno3D_T40(6, 8, pad=3) training step both ways; then ("blocks") OperatorBlock_3D forward + backward on the same two layers
 with the any-grid kernels in both forms - one buffer (`one_buffer_any_grid`: uno_fft_resample3d_any_acc, no stock add / GELU / gradient
-sum) against the two branches - and the training step both ways; and ("kernels") K3a alone in its plain, accumulate and accumulate +
+sum) against the two branches - and the training step both ways; and ("kernels") K1a, K5a and K3a in its plain, accumulate and accumulate +
 GELU forms from the library's event records, which is also the program to put behind `rocprofv3 --kernel-trace --stats --`
 (developer tool; bench.py is the contract).
 usage: python tools/resample3d_any_time.py [iters] [reps] [all | layers | blocks | kernels]
@@ -167,7 +167,13 @@ if section in ("all", "kernels"):
             for _ in range(iters):
                 round_()
             torch.cuda.synchronize()
-            recs = [r for r in _native.profile_end() if "inv_plane" in r[0]]
+            every = _native.profile_end()
+            for kernel, part in (("K1a", "fwd_plane"), ("K5a", "axis")):        # the same launch in all three calls of a round
+                ms = sorted(r[1] for r in every if part in r[0])
+                med, nbytes = ms[len(ms) // 2], next(r[2] for r in every if part in r[0])
+                print(f"{kernel} {name} grid w{w} B{B} {part:<9} {med * 1e3:8.1f} us ({ms[0] * 1e3:.1f} .. {ms[-1] * 1e3:.1f})   "
+                      f"{nbytes / 1e6:7.1f} MB algorithmic = {nbytes / med / 1e6:5.0f} GB/s", flush=True)
+            recs = [r for r in every if "inv_plane" in r[0]]
             for i, form in enumerate(FORMS):
                 ms = sorted(r[1] for r in recs[i::3])
                 med, nbytes = ms[len(ms) // 2], recs[i][2]

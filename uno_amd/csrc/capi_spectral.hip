@@ -469,78 +469,49 @@ int uno_fft_resample3d_acc(const float* x, float* y, float* y_act, void* ws, int
                                1, y_act, stream);
 }
 
-// ---- the same operator on the any-grid kernels (resample3d_any.hip): any row counts, 1 <= modes3 <= n/2 + 1, axes of 2 ... 128
-long long uno_fft_resample3d_any_ws_bytes(int n_vol, int D1, int M1, int J1, int J2, int m3) {
-    (void)J1;       // the J1 spectrum rows live in LDS only
+// ---- the same operator on the two plane-at-a-time kernel families (resample3d_planes.h): any row counts, 1 <= modes3 <= n/2 + 1
+struct Resample3dFamily {
+    int max_lead, max_last, max_rows;       // largest length of the two leading axes, of the last axis, largest kept-row count (from 2, 2, 1)
+    int vol_bits;                           // n_vol < 2^vol_bits: n_vol x max_lead fits an int
+    decltype(&resample3d_any_lds_bytes) lds_bytes;
+    decltype(&launch_resample3d_any) launch;
+};
+// resample3d_any.hip: every sum on plain FMA; resample3d_wide.hip: the long-axis stages on the MFMA
+static const Resample3dFamily RESAMPLE3D_ANY = {128, 128, 128, 24, resample3d_any_lds_bytes, launch_resample3d_any};
+static const Resample3dFamily RESAMPLE3D_WIDE = {256, 64, 256, 23, resample3d_wide_lds_bytes, launch_resample3d_wide};
+
+static long long resample3d_planes_ws_bytes(int n_vol, int D1, int M1, int J2, int m3) {       // the J1 spectrum rows live in LDS only
     return 8LL * n_vol * ((long long)D1 + M1) * J2 * m3;
 }
+long long uno_fft_resample3d_any_ws_bytes(int n_vol, int D1, int M1, int J1, int J2, int m3) { (void)J1; return resample3d_planes_ws_bytes(n_vol, D1, M1, J2, m3); }
+long long uno_fft_resample3d_wide_ws_bytes(int n_vol, int D1, int M1, int J1, int J2, int m3) { (void)J1; return resample3d_planes_ws_bytes(n_vol, D1, M1, J2, m3); }
 
-static int fft_resample3d_any_impl(const char* who, const float* x, float* y, float* y_act, int accumulate, void* ws, int n_vol, int D1,
-                                   int D2, int D3, int M1, int M2, int M3, int J1, const int* f1_in, const int* f1_out, int J2,
-                                   const int* f2_in, const int* f2_out, int m3, float scale, int herm_in, int herm_out, void* stream) {
-    const int dims[6] = {D1, D2, D3, M1, M2, M3};
-    for (int d : dims)
-        if (d < 2 || d > 128) {
-            set_error("%s: grid (%d,%d,%d) -> (%d,%d,%d): every axis length must be in 2 ... 128", who, D1, D2, D3, M1, M2, M3);
-            return -1;
-        }
-    if (J1 < 1 || J1 > 128 || J2 < 1 || J2 > 128) { set_error("%s: kept-row counts J1=%d, J2=%d must be in 1 ... 128", who, J1, J2); return -1; }
-    if (m3 < 1 || m3 > D3 / 2 + 1 || m3 > M3 / 2 + 1) {
-        set_error("%s: need 1 <= modes3=%d <= n/2+1 on the last axis %d -> %d", who, m3, D3, M3);
-        return -1;
-    }
-    if (n_vol < 0 || (long long)n_vol * 128 > 0x7fffffffLL) { set_error("%s: bad volume count %d (0 ... 2^24 - 1)", who, n_vol); return -1; }
-    if (accumulate) {       // the kernels read x while they write y, and read y back before they write y_act
-        if (y_act && y_act == y) { set_error("%s: y_act must not alias y", who); return -1; }
-        if (x && x == y) { set_error("%s: x must not alias y", who); return -1; }
-        if (x && x == y_act) { set_error("%s: x must not alias y_act", who); return -1; }
-    }
-    if (n_vol == 0) return 0;
-    if (!x || !y || !ws || !f1_in || !f1_out || !f2_in || !f2_out) { set_error("%s: null pointer", who); return -1; }
-    return launch_resample3d_any(x, y, y_act, accumulate, ws, n_vol, D1, D2, D3, M1, M2, M3, J1, f1_in, f1_out, J2, f2_in, f2_out, m3, scale,
-                                 herm_in, herm_out, (hipStream_t)stream);
-}
-
-int uno_fft_resample3d_any(const float* x, float* y, void* ws, int n_vol, int D1, int D2, int D3, int M1, int M2, int M3,
-                           int J1, const int* f1_in, const int* f1_out, int J2, const int* f2_in, const int* f2_out, int m3,
-                           float scale, int herm_in, int herm_out, void* stream) {
-    return fft_resample3d_any_impl("uno_fft_resample3d_any", x, y, nullptr, 0, ws, n_vol, D1, D2, D3, M1, M2, M3, J1, f1_in, f1_out, J2, f2_in,
-                                   f2_out, m3, scale, herm_in, herm_out, stream);
-}
-
-int uno_fft_resample3d_any_acc(const float* x, float* y, float* y_act, void* ws, int n_vol, int D1, int D2, int D3, int M1, int M2, int M3,
-                               int J1, const int* f1_in, const int* f1_out, int J2, const int* f2_in, const int* f2_out, int m3,
-                               float scale, int herm_in, int herm_out, void* stream) {
-    return fft_resample3d_any_impl("uno_fft_resample3d_any_acc", x, y, y_act, 1, ws, n_vol, D1, D2, D3, M1, M2, M3, J1, f1_in, f1_out, J2,
-                                   f2_in, f2_out, m3, scale, herm_in, herm_out, stream);
-}
-
-// ---- the same operator on the wide-axis kernels (resample3d_wide.hip): complex axes of 2 ... 256, a real axis of 2 ... 64, long-axis stages on the MFMA
-long long uno_fft_resample3d_wide_ws_bytes(int n_vol, int D1, int M1, int J1, int J2, int m3) {
-    (void)J1;       // the J1 spectrum rows live in LDS only
-    return 8LL * n_vol * ((long long)D1 + M1) * J2 * m3;
-}
-
-static int fft_resample3d_wide_impl(const char* who, const float* x, float* y, float* y_act, int accumulate, void* ws, int n_vol, int D1,
-                                    int D2, int D3, int M1, int M2, int M3, int J1, const int* f1_in, const int* f1_out, int J2,
-                                    const int* f2_in, const int* f2_out, int m3, float scale, int herm_in, int herm_out, void* stream) {
+static int resample3d_planes_impl(const Resample3dFamily& fam, const char* who, const float* x, float* y, float* y_act, int accumulate, void* ws,
+                                  int n_vol, int D1, int D2, int D3, int M1, int M2, int M3, int J1, const int* f1_in, const int* f1_out, int J2,
+                                  const int* f2_in, const int* f2_out, int m3, float scale, int herm_in, int herm_out, void* stream) {
     const int lead[4] = {D1, D2, M1, M2}, last[2] = {D3, M3};
     bool ok = true;
-    for (int d : lead) ok = ok && d >= 2 && d <= 256;
-    for (int d : last) ok = ok && d >= 2 && d <= 64;
+    for (int d : lead) ok = ok && d >= 2 && d <= fam.max_lead;
+    for (int d : last) ok = ok && d >= 2 && d <= fam.max_last;
     if (!ok) {
-        set_error("%s: grid (%d,%d,%d) -> (%d,%d,%d): the two leading axis lengths must be in 2 ... 256 and the last in 2 ... 64", who, D1, D2, D3,
-                  M1, M2, M3);
+        if (fam.max_lead == fam.max_last)
+            set_error("%s: grid (%d,%d,%d) -> (%d,%d,%d): every axis length must be in 2 ... %d", who, D1, D2, D3, M1, M2, M3, fam.max_lead);
+        else
+            set_error("%s: grid (%d,%d,%d) -> (%d,%d,%d): the two leading axis lengths must be in 2 ... %d and the last in 2 ... %d", who, D1, D2, D3,
+                      M1, M2, M3, fam.max_lead, fam.max_last);
         return -1;
     }
-    if (J1 < 1 || J1 > 256 || J2 < 1 || J2 > 256) { set_error("%s: kept-row counts J1=%d, J2=%d must be in 1 ... 256", who, J1, J2); return -1; }
+    if (J1 < 1 || J1 > fam.max_rows || J2 < 1 || J2 > fam.max_rows) {
+        set_error("%s: kept-row counts J1=%d, J2=%d must be in 1 ... %d", who, J1, J2, fam.max_rows);
+        return -1;
+    }
     if (m3 < 1 || m3 > D3 / 2 + 1 || m3 > M3 / 2 + 1) {
         set_error("%s: need 1 <= modes3=%d <= n/2+1 on the last axis %d -> %d", who, m3, D3, M3);
         return -1;
     }
-    if (n_vol < 0 || (long long)n_vol * 256 > 0x7fffffffLL) { set_error("%s: bad volume count %d (0 ... 2^23 - 1)", who, n_vol); return -1; }
+    if (n_vol < 0 || (n_vol >> fam.vol_bits)) { set_error("%s: bad volume count %d (0 ... 2^%d - 1)", who, n_vol, fam.vol_bits); return -1; }
     size_t lds[3];
-    resample3d_wide_lds_bytes(D1, D2, D3, M1, M2, M3, J1, J2, m3, lds);
+    fam.lds_bytes(D1, D2, D3, M1, M2, M3, J1, J2, m3, lds);       // (never beyond the limit on the any-grid family's axes: 142 KB at most)
     if (lds[0] > 160 * 1024 || lds[1] > 160 * 1024 || lds[2] > 160 * 1024) {
         set_error("%s: grid (%d,%d,%d) -> (%d,%d,%d) with J1=%d, J2=%d, modes3=%d needs %zu / %zu / %zu bytes of LDS (forward plane / leading "
                   "axis / inverse plane kernel): the limit is 163840 per workgroup", who, D1, D2, D3, M1, M2, M3, J1, J2, m3, lds[0], lds[1], lds[2]);
@@ -553,22 +524,36 @@ static int fft_resample3d_wide_impl(const char* who, const float* x, float* y, f
     }
     if (n_vol == 0) return 0;
     if (!x || !y || !ws || !f1_in || !f1_out || !f2_in || !f2_out) { set_error("%s: null pointer", who); return -1; }
-    return launch_resample3d_wide(x, y, y_act, accumulate, ws, n_vol, D1, D2, D3, M1, M2, M3, J1, f1_in, f1_out, J2, f2_in, f2_out, m3, scale,
-                                  herm_in, herm_out, (hipStream_t)stream);
+    return fam.launch(x, y, y_act, accumulate, ws, n_vol, D1, D2, D3, M1, M2, M3, J1, f1_in, f1_out, J2, f2_in, f2_out, m3, scale, herm_in, herm_out,
+                      (hipStream_t)stream);
+}
+
+int uno_fft_resample3d_any(const float* x, float* y, void* ws, int n_vol, int D1, int D2, int D3, int M1, int M2, int M3,
+                           int J1, const int* f1_in, const int* f1_out, int J2, const int* f2_in, const int* f2_out, int m3,
+                           float scale, int herm_in, int herm_out, void* stream) {
+    return resample3d_planes_impl(RESAMPLE3D_ANY, "uno_fft_resample3d_any", x, y, nullptr, 0, ws, n_vol, D1, D2, D3, M1, M2, M3, J1, f1_in, f1_out, J2,
+                                  f2_in, f2_out, m3, scale, herm_in, herm_out, stream);
+}
+
+int uno_fft_resample3d_any_acc(const float* x, float* y, float* y_act, void* ws, int n_vol, int D1, int D2, int D3, int M1, int M2, int M3,
+                               int J1, const int* f1_in, const int* f1_out, int J2, const int* f2_in, const int* f2_out, int m3,
+                               float scale, int herm_in, int herm_out, void* stream) {
+    return resample3d_planes_impl(RESAMPLE3D_ANY, "uno_fft_resample3d_any_acc", x, y, y_act, 1, ws, n_vol, D1, D2, D3, M1, M2, M3, J1, f1_in, f1_out,
+                                  J2, f2_in, f2_out, m3, scale, herm_in, herm_out, stream);
 }
 
 int uno_fft_resample3d_wide(const float* x, float* y, void* ws, int n_vol, int D1, int D2, int D3, int M1, int M2, int M3,
                             int J1, const int* f1_in, const int* f1_out, int J2, const int* f2_in, const int* f2_out, int m3,
                             float scale, int herm_in, int herm_out, void* stream) {
-    return fft_resample3d_wide_impl("uno_fft_resample3d_wide", x, y, nullptr, 0, ws, n_vol, D1, D2, D3, M1, M2, M3, J1, f1_in, f1_out, J2, f2_in,
-                                    f2_out, m3, scale, herm_in, herm_out, stream);
+    return resample3d_planes_impl(RESAMPLE3D_WIDE, "uno_fft_resample3d_wide", x, y, nullptr, 0, ws, n_vol, D1, D2, D3, M1, M2, M3, J1, f1_in, f1_out,
+                                  J2, f2_in, f2_out, m3, scale, herm_in, herm_out, stream);
 }
 
 int uno_fft_resample3d_wide_acc(const float* x, float* y, float* y_act, void* ws, int n_vol, int D1, int D2, int D3, int M1, int M2, int M3,
                                 int J1, const int* f1_in, const int* f1_out, int J2, const int* f2_in, const int* f2_out, int m3,
                                 float scale, int herm_in, int herm_out, void* stream) {
-    return fft_resample3d_wide_impl("uno_fft_resample3d_wide_acc", x, y, y_act, 1, ws, n_vol, D1, D2, D3, M1, M2, M3, J1, f1_in, f1_out, J2,
-                                    f2_in, f2_out, m3, scale, herm_in, herm_out, stream);
+    return resample3d_planes_impl(RESAMPLE3D_WIDE, "uno_fft_resample3d_wide_acc", x, y, y_act, 1, ws, n_vol, D1, D2, D3, M1, M2, M3, J1, f1_in, f1_out,
+                                  J2, f2_in, f2_out, m3, scale, herm_in, herm_out, stream);
 }
 
 static int check_modes3d(const char* who, int H, int W, int T, int Ho, int Wo, int To, int m1, int m2, int m3) {

@@ -15,7 +15,7 @@
 // K22-B's first half with a store of the real rows.
 //
 // Every sum is DENSE (length-N stages, not radix splits) on v_mfma_f32_16x16x4_f32 - exact f32, k-ordered - on interleaved (re, im)
-// columns as rw_complex_stage of resample3d_wide.hip does, with the twiddle looked up in an LDS table at (a b) mod N.  The summation order
+// columns as ResampleWide::complex_stage of resample3d_wide.hip does, with the twiddle looked up in an LDS table at (a b) mod N.  The summation order
 // is fixed and a sample's arithmetic does not depend on B: two runs, a split run and any batch give the same bits.  Stores are plain
 // global stores (no buffer resource, no scalar offset: DESIGN.md section 4, K3v).  Every state / workspace offset is a 64-bit product.
 // Workgroups are persistent.  h is odd at every N, so every column-blocked stage has a ragged last block; it is handled by bounds, not by size.

@@ -1,5 +1,5 @@
-// What the two plane-at-a-time families of pointwise_op_3D's FFT crop / resample share (resample3d_any.hip: K1a / K5a / K3a;
-// resample3d_wide.hip: K1w / K5w / K3w): twiddle-index arithmetic, the persistent launch geometry and the launch check.
+// Twiddle-index arithmetic, the persistent launch geometry and the launch check of the plane-at-a-time kernels of pointwise_op_3D's FFT
+// crop / resample (resample3d_planes.h: K1a / K5a / K3a and K1w / K5w / K3w), which ns2d_solver.hip uses too.
 #pragma once
 #include "uno_common.h"
 #include <algorithm>

@@ -338,14 +338,15 @@ int launch_mode_gemm_pair(const ModeGemmParams& input_grad, const ModeGemmParams
 int launch_cdft(const CdftParams& p, bool inverse, hipStream_t s);
 int launch_dft2d_generic(const Dft2dParams& p, bool inverse, void* ws, size_t ws_bytes, hipStream_t s);      // dft_generic.hip: any mode count; ws: 8 n_img H m2 bytes
 int launch_cdft_generic(const CdftParams& p, bool inverse, hipStream_t s);
-// resample3d_any.hip: the FFT crop / resample of pointwise_op_3D for any row counts and axis lengths 2 ... 128 (arguments validated by the caller);
+// resample3d_any.hip / resample3d_wide.hip, both on the kernels of resample3d_planes.h: the FFT crop / resample of pointwise_op_3D for any row
+// counts, on plain FMA for axis lengths 2 ... 128 (any) or with the long-axis stages on the MFMA for complex axes of 2 ... 256 and a real axis
+// of 2 ... 64 (wide).  Arguments validated by the caller, which also refuses what *_lds_bytes - K1 / K5 / K3 - puts beyond 160 KB;
 // accumulate != 0: y += result and, with y_act != nullptr, y_act = gelu(y)
+void resample3d_any_lds_bytes(int D1, int D2, int D3, int M1, int M2, int M3, int J1, int J2, int m3, size_t out[3]);
+void resample3d_wide_lds_bytes(int D1, int D2, int D3, int M1, int M2, int M3, int J1, int J2, int m3, size_t out[3]);
 int launch_resample3d_any(const float* x, float* y, float* y_act, int accumulate, void* ws, int n_vol, int D1, int D2, int D3, int M1, int M2, int M3, int J1,
                           const int* f1_in, const int* f1_out, int J2, const int* f2_in, const int* f2_out, int m3, float scale,
                           int herm_in, int herm_out, hipStream_t s);
-// resample3d_wide.hip: the same operator for complex axes of 2 ... 256 and a real axis of 2 ... 64, long-axis stages on the MFMA (arguments
-// validated by the caller, which also refuses what resample3d_wide_lds_bytes - K1w / K5w / K3w - puts beyond 160 KB)
-void resample3d_wide_lds_bytes(int D1, int D2, int D3, int M1, int M2, int M3, int J1, int J2, int m3, size_t out[3]);
 int launch_resample3d_wide(const float* x, float* y, float* y_act, int accumulate, void* ws, int n_vol, int D1, int D2, int D3, int M1, int M2, int M3,
                            int J1, const int* f1_in, const int* f1_out, int J2, const int* f2_in, const int* f2_out, int m3, float scale,
                            int herm_in, int herm_out, hipStream_t s);
