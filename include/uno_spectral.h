@@ -745,6 +745,38 @@ int uno_ns2d_inverse(const float* w_h, float* w, void* ws, int B, int N, void* s
 int uno_ns2d_steps(float* w_h, const float* f_h, int f_batched, void* ws, int B, int N, long long n_steps, double visc, double delta_t,
                    void* stream);
 
+/* K23 (additive: these entry points were added WITHOUT an ABI bump, UNO_SPECTRAL_ABI_VERSION stays 14): the Darcy-flow data generator of
+ * the reference's MATLAB files (Data Generation/darcy Flow/GRF.m, demo.m, solve_gwf.m).  Grid: K x K nodes i / (K - 1), K in 8 ... 512;
+ * unknowns: the n x n interior nodes, n = K - 2, zero Dirichlet values on the border; 0 <= B <= 65535.  Planes are dense row-major.
+ * Every sum has a fixed order (no atomics) and a sample's arithmetic does not depend on B, on its batch partners or on check_every: two
+ * runs and a sample inside any batch give the same bits.  B == 0: success, no launch.
+ *   uno_darcy_table_pitch(N): rows = columns of the zero-padded operand table of an N x N transform (N rounded up to the 64-wide tile; 0
+ *     for N outside 1 ... 512).
+ *   uno_darcy_transform: Y[b] = post o (M X[b] M^T), b < B, N x N planes, N in 1 ... 512, float32 (f32 != 0: v_mfma_f32_16x16x4_f32) or
+ *     float64 (vector FMAs; one k-ascending chain per entry and pass).  M: (pitch, pitch) row-major, zero beyond N x N; post: (N, N) or
+ *     NULL; tmp: B N N elements of scratch; X, Y, tmp distinct.  2 launches.  Replaces idct2 (GRF.m:21: M = the orthonormal inverse
+ *     DCT-II matrix) and interp2(..., 'spline') between the uniform cell-centre and node grids (solve_gwf.m:11-12 and 35: M = the
+ *     not-a-knot spline matrix), and is the DST-I pair of the solver's fast Poisson preconditioner.
+ *   uno_darcy_apply: Ap (B, n, n) = A p, A the matrix of solve_gwf.m:16-32 applied and never formed: (K - 1)^2 times the sum over the
+ *     four faces of (c + c_neighbour) / 2 (p - p_neighbour), p = 0 outside the interior; coef (B, K, K): the NODAL coefficient, any
+ *     sign (the spline of a thresholded field overshoots below zero).  1 launch.
+ *   uno_darcy_solve: P (B, K, K) = the nodal solution of A P = F on the interior with a zero border (solve_gwf.m:14-33, A \ F(:) replaced by
+ *     conjugate gradients in float64, preconditioned by the constant-coefficient 5-point Laplacian applied as a float32 fast Poisson
+ *     solve; flexible beta).  coef, F (B, K, K) float64 nodal planes.  Sample b stops (is frozen) once |r|_2 <= rtol |b|_2 - status 1 -
+ *     or when p^T A p, rho or a norm is zero or not finite - status 2; status 0: max_iter reached.  iters (B) int32, relres (B)
+ *     float64 = |r|_2 / |b|_2 of the recursive residual, status (B) int32.  F = 0: P = 0, 0 iterations, status 1.  The loop runs in the
+ *     entry point, 9 launches per iteration; alpha and beta are formed on the device; the host reads the B status words once per
+ *     check_every iterations (a stream synchronisation: not capturable) and stops when all are set.  ws: uno_darcy_ws_bytes(B, K)
+ *     bytes, 8-byte aligned, need not be initialised (0 for sizes outside the range).
+ * Errors (-1, before any launch): null pointers, K outside 8 ... 512, B outside 0 ... 65535, rtol not positive and finite,
+ * max_iter < 1, check_every < 1, aliased buffers. */
+long long uno_darcy_ws_bytes(int B, int K);
+int uno_darcy_table_pitch(int N);
+int uno_darcy_transform(const void* M, const void* X, void* Y, void* tmp, const void* post, int B, int N, int f32, void* stream);
+int uno_darcy_apply(const double* coef, const double* p, double* Ap, int B, int K, void* stream);
+int uno_darcy_solve(const double* coef, const double* F, double* P, int* iters, double* relres, int* status, void* ws, int B, int K,
+                    double rtol, int max_iter, int check_every, void* stream);
+
 /* Optional in-library kernel timing (HIP events recorded on the launch stream around every kernel
  * this library enqueues), used by bench.py for the live roofline figure.
  *   uno_profile_begin(max_records): start recording (drops records beyond max_records).

@@ -144,6 +144,11 @@ _SIGNATURES = {
     "uno_ns2d_forward": (C.c_int, [_fp, _fp, _fp, _i, _i, _fp]),
     "uno_ns2d_inverse": (C.c_int, [_fp, _fp, _fp, _i, _i, _fp]),
     "uno_ns2d_steps": (C.c_int, [_fp, _fp, _i, _fp, _i, _i, C.c_longlong, C.c_double, C.c_double, _fp]),
+    "uno_darcy_ws_bytes": (C.c_longlong, [_i, _i]),
+    "uno_darcy_table_pitch": (C.c_int, [_i]),
+    "uno_darcy_transform": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _i, _i, _i, _fp]),
+    "uno_darcy_apply": (C.c_int, [_fp, _fp, _fp, _i, _i, _fp]),
+    "uno_darcy_solve": (C.c_int, [_fp] * 7 + [_i, _i, C.c_double, _i, _i, _fp]),
     "uno_profile_begin": (C.c_int, [_i]),
     "uno_profile_end": (C.c_int, []),
     "uno_profile_get": (C.c_int, [_i, C.c_char_p, _i, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
@@ -1928,6 +1933,113 @@ def ns2d_steps(w_h, f_h, n_steps: int, visc: float, delta_t: float, ws=None):
                                   _stream(w_h))
     _check(rc, "uno_ns2d_steps")
     return w_h
+
+
+DARCY_SIZES = (8, 512)
+
+
+def darcy_supported(K: int) -> bool:
+    """True for the grid sizes the K23 kernels take: 8 ... 512"""
+    return DARCY_SIZES[0] <= int(K) <= DARCY_SIZES[1]
+
+
+def darcy_workspace(B: int, K: int, device):
+    """the scratch of darcy_solve for (B, K): uint8, uno_darcy_ws_bytes(B, K) bytes, uninitialised"""
+    return torch.empty(max(8, int(lib().uno_darcy_ws_bytes(int(B), int(K)))), dtype=torch.uint8, device=device)
+
+
+def darcy_table(M: torch.Tensor, device=None) -> torch.Tensor:
+    """the (N, N) matrix of a K23-T transform as the kernel reads it: zero-padded to (pitch, pitch), pitch = uno_darcy_table_pitch(N)"""
+    N = int(M.shape[0])
+    pitch = int(lib().uno_darcy_table_pitch(N))
+    if M.dim() != 2 or M.shape[1] != N or pitch == 0:
+        raise RuntimeError(f"uno_amd: a transform table is (N, N) with N in 1 ... 512 (got {tuple(M.shape)})")
+    out = torch.zeros((pitch, pitch), dtype=M.dtype)
+    out[:N, :N] = M.detach().cpu()
+    return out if device is None else table_to_device(out, device)
+
+
+def _darcy_planes(t, name, K=None):
+    _require(t, torch.float64, name)
+    if t.dim() != 3 or t.shape[1] != t.shape[2] or (K is not None and t.shape[1] != K):
+        raise RuntimeError(f"uno_amd: {name} must be (B, {'K' if K is None else K}, {'K' if K is None else K}) float64 (got {tuple(t.shape)})")
+    return int(t.shape[0]), int(t.shape[1])
+
+
+def _darcy_size(K):
+    if not darcy_supported(K):
+        raise RuntimeError(f"uno_amd: the native Darcy solver takes grids of 8 ... 512 nodes a side, got K={K}")
+
+
+def darcy_transform(table, x, post=None, out=None):
+    """post o (M x[b] M^T) for x (B, N, N), float32 or float64 (uno_darcy_transform, K23-T); table: darcy_table(M) on x's device"""
+    if x.dtype not in (torch.float32, torch.float64):
+        raise RuntimeError(f"uno_amd: x must be float32 or float64 (got {x.dtype})")
+    _require(x, x.dtype, "x")
+    _require(table, x.dtype, "table")
+    if x.dim() != 3 or x.shape[1] != x.shape[2]:
+        raise RuntimeError(f"uno_amd: x must be (B, N, N) (got {tuple(x.shape)})")
+    B, N = int(x.shape[0]), int(x.shape[1])
+    pitch = int(lib().uno_darcy_table_pitch(N))
+    if pitch == 0 or tuple(table.shape) != (pitch, pitch):
+        raise RuntimeError(f"uno_amd: the table of an N={N} transform is ({pitch}, {pitch}) with N in 1 ... 512 (got {tuple(table.shape)})")
+    if post is not None:
+        _require(post, x.dtype, "post")
+        if tuple(post.shape) != (N, N):
+            raise RuntimeError("uno_amd: post has the wrong shape")
+    y = torch.empty_like(x) if out is None else out
+    _require(y, x.dtype, "out")
+    if tuple(y.shape) != tuple(x.shape):
+        raise RuntimeError("uno_amd: out has the wrong shape")
+    tmp = torch.empty_like(x)
+    with torch.cuda.device(x.device):
+        rc = lib().uno_darcy_transform(_ptr(table), _ptr(x), _ptr(y), _ptr(tmp), _opt(post), B, N, 1 if x.dtype == torch.float32 else 0,
+                                       _stream(x))
+    _check(rc, "uno_darcy_transform")
+    return y
+
+
+def darcy_apply(coef, p):
+    """A p (B, K-2, K-2) for the nodal coefficient coef (B, K, K) and p (B, K-2, K-2), float64 (uno_darcy_apply, K23-A)"""
+    B, K = _darcy_planes(coef, "coef")
+    _darcy_size(K)
+    _require(p, torch.float64, "p")
+    if tuple(p.shape) != (B, K - 2, K - 2) or p.device != coef.device:
+        raise RuntimeError(f"uno_amd: p must be ({B}, {K - 2}, {K - 2}) float64 on coef's device")
+    ap = torch.empty_like(p)
+    with torch.cuda.device(coef.device):
+        rc = lib().uno_darcy_apply(_ptr(coef), _ptr(p), _ptr(ap), B, K, _stream(coef))
+    _check(rc, "uno_darcy_apply")
+    return ap
+
+
+def darcy_solve(coef, F, rtol: float = 1e-10, max_iter: int = 500, check_every: int = 8, ws=None, out=None):
+    """The nodal solution (B, K, K) of the 5-point system of the nodal coefficient coef and right-hand side F, both (B, K, K) float64
+    (uno_darcy_solve, K23) -> (P, iterations (B) int32, relative residual (B) float64, status (B) int32: 1 converged, 0 max_iter
+    reached, 2 breakdown).  The three small tensors are still on the device: reading them is the caller's synchronisation."""
+    B, K = _darcy_planes(coef, "coef")
+    _darcy_size(K)
+    _darcy_planes(F, "F", K)
+    if int(F.shape[0]) != B or F.device != coef.device:
+        raise RuntimeError("uno_amd: F must have coef's shape and device")
+    if ws is None:
+        ws = darcy_workspace(B, K, coef.device)
+    else:
+        _require(ws, torch.uint8, "workspace")
+        if ws.numel() < lib().uno_darcy_ws_bytes(B, K):
+            raise RuntimeError("uno_amd: workspace smaller than uno_darcy_ws_bytes(B, K)")
+    P = torch.empty_like(coef) if out is None else out
+    _require(P, torch.float64, "out")
+    if tuple(P.shape) != (B, K, K):
+        raise RuntimeError("uno_amd: out has the wrong shape")
+    iters = torch.empty(B, dtype=torch.int32, device=coef.device)
+    relres = torch.empty(B, dtype=torch.float64, device=coef.device)
+    status = torch.empty(B, dtype=torch.int32, device=coef.device)
+    with torch.cuda.device(coef.device):
+        rc = lib().uno_darcy_solve(_ptr(coef), _ptr(F), _ptr(P), _ptr(iters), _ptr(relres), _ptr(status), _ptr(ws), B, K, float(rtol),
+                                   int(max_iter), int(check_every), _stream(coef))
+    _check(rc, "uno_darcy_solve")
+    return P, iters, relres, status
 
 
 def profile_begin(max_records: int = 100000):

@@ -357,6 +357,16 @@ int launch_ns2d_forward(const float* w, float* w_h, void* ws, int B, int N, hipS
 int launch_ns2d_inverse(const float* w_h, float* w, void* ws, int B, int N, hipStream_t s);
 int launch_ns2d_steps(float* w_h, const float* f_h, int f_batched, void* ws, int B, int N, long long n_steps, double visc, double delta_t,
                       hipStream_t s);
+// darcy_solver.hip (K23): the Darcy-flow data generator's plane transforms Y = post o (M X M^T) (M padded to darcy_table_pitch(N) rows and
+// columns; f32 != 0: float32 on the MFMA, else float64; skip: optional per-sample freeze words), the 5-point operator on the (K - 2)^2
+// interior nodes and its preconditioned CG solve (arguments validated by the caller); ws: darcy_ws_bytes(B, K) bytes
+int darcy_table_pitch(int N);
+long long darcy_ws_bytes(int B, int K);
+int launch_darcy_transform(const void* M, const void* X, void* Y, void* tmp, const void* post, const int* skip, int B, int N, int f32,
+                           hipStream_t s);
+int launch_darcy_apply(const double* coef, const double* p, double* ap, int B, int K, hipStream_t s);
+int launch_darcy_solve(const double* coef, const double* F, double* P, int* iters, double* relres, int* status, void* ws, int B, int K,
+                       double rtol, int max_iter, int check_every, hipStream_t s);
 int launch_resample2d(const void* in, void* out, float* tmp, int n_img, int H, int W, int Ho, int Wo, const int* startH,
                       const float* wtH, int KH, const int* startW, const float* wtW, int KW, const int* tile_p0,
                       const float* tile_w, int NP, int accumulate, int bf16, hipStream_t s);
