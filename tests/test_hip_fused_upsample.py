@@ -60,6 +60,73 @@ def test_fused_inverse_add_matches_two_kernels_and_float64(case):
         assert float((add_f - add_r).abs().max()) < 2e-5 * float(add_r.abs().max())
 
 
+# Several row tiles per wave and per image.  The census (test_hip_dft2d_instances.py) has no case where one wave walks several row
+# tiles of an image (NW == 1: the partial 128-byte line at the end of a tile is carried into the next one), and CASES above reach five
+# of K3-A's 84 instantiations, all at model size.  Geometry (waves per image NW) from inv_ft_geometry at 256 CUs.
+ROW_TILE_CASES = [
+    # (n_img, Hs, Ws, H, W, m1, m2, adjoint), (KS, KSK, NWTM) of the fused kernel
+    ((2, 10, 98, 21, 197, 3, 5, False), (2, 1, 7)),         # 2 row tiles (last has 5 rows), NW = 2
+    ((2, 10, 98, 21, 197, 3, 5, True), (2, 1, 7)),          # the same, adjoint tables
+    ((1100, 10, 98, 37, 197, 3, 5, False), (2, 1, 7)),      # 3 row tiles (last has 5 rows), NW = 1: chained, the line is carried twice
+    ((3, 10, 111, 21, 223, 2, 17, False), (5, 1, 7)),       # requests during the column loop (EARLY); 2 row tiles, NW = 2
+    ((2, 18, 209, 37, 419, 9, 21, False), (6, 3, 14)),      # 14 column tiles; 3 row tiles, NW = 2
+    ((1100, 16, 209, 33, 419, 5, 5, False), (2, 2, 14)),    # 3 row tiles (last has 1 row), NW = 1: chained
+    ((2, 40, 221, 81, 443, 27, 24, False), (6, 7, 14)),     # the largest instantiation; 6 row tiles, NW = 4
+]
+
+
+@pytest.mark.parametrize("case,inst", ROW_TILE_CASES)
+def test_fused_and_plain_inverse_over_several_row_tiles(case, inst, monkeypatch):
+    """K3-A and the full-tile K3 of the same geometry: which kernels run, guard bands, the plain inverse against float64 as the census
+    checks it, the addend against float64 and the fused result against the two-kernel form as the test above checks them."""
+    import dft2d_instances as di
+    from conftest import rel_err
+    from test_hip_dft2d_instances import TOL, _profiled
+    from test_hip_redzone import RedZone
+    from uno_amd import _native
+    from uno_amd import resample as rs
+    n, Hs, Ws, H, W, m1, m2, adjoint = case
+    KS, KSK, NWTM = inst
+    dev = _dev()
+    assert _native.dft2d_inverse_add_applies(n, H, W, m1, m2, Hs, Ws), "the fused kernel should cover this shape"
+    tabs = rs.upsample_add_tables(Hs, Ws, H, W, str(dev), adjoint)
+    assert tabs is not None
+    plain_name = f"uno::dft2d_inv_ft_kernel<{KS}, {(2 * m1 + 15) // 16}>"
+    entry = {"name": plain_name, "dir": "inv", "shape": [n, H, W, m1, m2], "dtype": "f32"}
+    O = di.inverse_input(entry)                                          # (n, 1, 2 m1, m2)
+    spec = torch.from_numpy(O).to(dev)
+    t = torch.randn(n, 1, Hs, Ws, generator=torch.Generator().manual_seed(7)).to(dev)
+
+    zone = RedZone(monkeypatch)
+    fused, ran_fused = _profiled(lambda: _native.dft2d_inverse(spec, H, W, di.INV_SCALE, True, True, addend=(t, tabs)))
+    plain, ran_plain = _profiled(lambda: _native.dft2d_inverse(spec, H, W, di.INV_SCALE, True, True))
+    assert zone.check(str(case)) == 2
+    assert ran_plain == [plain_name], ran_plain
+    assert ran_fused == [f"uno::dft2d_inv_ft_add_kernel<{KS}, {KSK}, {NWTM}>"], ran_fused
+    assert torch.isfinite(fused).all() and torch.isfinite(plain).all()
+
+    ref, bound = di.inverse_reference(entry, O)
+    got = plain.cpu().numpy()
+    err, excess = rel_err(got, ref), di.worst_excess(got, ref, bound)
+    print(f"{case}: plain rel L2 {err:.3g}, worst |got - ref| / bound {excess:.3g}")
+    assert err < TOL
+    assert excess <= 1.0
+
+    two = plain.clone()
+    if adjoint:
+        rs.resample_adjoint(t.view(1, n, Hs, Ws), H, W, out=two.view(1, n, H, W))
+        Rh, Rw = rs._matrix(H, Hs).t(), rs._matrix(W, Ws).t()
+    else:
+        rs.resample_forward(t.view(1, n, Hs, Ws), H, W, out=two.view(1, n, H, W))
+        Rh, Rw = rs._matrix(Hs, H), rs._matrix(Ws, W)
+    add_r = torch.einsum("hu,nuv,wv->nhw", Rh.double().to(dev), t.view(n, Hs, Ws).double(), Rw.double().to(dev))
+    add_f = (fused.double() - plain.double()).view(n, H, W)
+    worst = float((add_f - add_r).abs().max()) / float(add_r.abs().max())
+    print(f"{case}: addend worst / largest {worst:.3g}, fused against two kernels {_rel(fused, two):.3g}")
+    assert worst < 2e-5
+    assert _rel(fused, two) < 2e-6
+
+
 def test_fused_inverse_add_reads_nothing_outside_the_addend():
     """the addend between two runs of NaN: the result is finite and bit-equal to the run on an ordinary tensor"""
     from uno_amd import _native

@@ -17,7 +17,7 @@ LAUNCHERS = {
     ("dft2d_fwd_ft_kernel.h", "SWEEP_K1", 0): ["k1_ft"],
     ("dft2d_fwd_ht_kernel.h", "SWEEP_K1", 0): ["k1_ht"],
     ("dft2d_inv_kernel.h", "SWEEP_K3", 0): ["k3", "k3_bf16"],                 # launch_inv_k
-    ("dft2d_inv_kernel.h", "SWEEP_K3", 1): ["k3_ft"],                         # launch_inv_ft
+    ("dft2d_inv_kernel.h", "SWEEP_K3", 1): ["k3_ft"],                         # launch_inv_t: the full-tile form
     ("dft2d_inv_add_kernel.h", "SWEEP_K3", 0): ["k3a_inverse_add"],
     ("resample2d.hip", "SWEEP_K7", 0): ["k7_down", "k7_up", "k7_accumulate", "k7_down_bf16", "k7_up_bf16", "k7_accumulate_bf16"],
     ("channel_mix.hip", "SWEEP_K8", 0): ["k8_generic", "k8_generic_act_in", "k8_wide128", "k8_split", "k8_split_bf16",

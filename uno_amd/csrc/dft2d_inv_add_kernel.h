@@ -43,44 +43,23 @@ template <int KS, int KSK, int NWTM>
 __global__ __launch_bounds__(256, ((NWTM <= 7 && KS <= 4) ? 2 : 1)) void dft2d_inv_ft_add_kernel(Dft2dParams p) {
     constexpr int NT = (KS + 3) / 4;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int H = p.H, W = p.W, m1 = p.m1, m2 = p.m2;
-    const int tid = threadIdx.x;
-    const int nthreads = blockDim.x;
-    const int NWT = nthreads >> 6;
-    const int NW = p.nw;
-    const int Wh = W >> 1;
-    constexpr int nwt = NWTM;                                              // == (Wh + 16) >> 4 (launcher): the column loop is straight-line code
-    float2* sTabA = reinterpret_cast<float2*>(smem);                      // [nwt][KS][64]
-    float2* sTwH = sTabA + nwt * KS * 64;
-    float* sTile = reinterpret_cast<float*>(sTwH + ((H + 1) & ~1));
-    const int tile_stride = (16 * W + 32 + 64 + 3) & ~3;
-
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int lane = tid & 63;
-    const int r16 = lane & 15;
-    const int kk = lane >> 4;
+    UNO_INV_GRID_LOCALS();
+    constexpr int nwt = NWTM;                                              // == inv_col_tiles(W) (launcher): the column loop is straight-line code
+    UNO_INV_FT_LDS();
+    UNO_INV_LANE_LOCALS();
     const unsigned H8 = 8u * H;
 
-    for (int n = tid; n < H; n += nthreads) sTwH[n] = p.twH[n];
-    for (int e = tid; e < nwt * KS * 64; e += nthreads) {
-        const int ln = e & 63, q = e >> 6;
-        const int sp = q % KS, wt = q / KS;
-        const unsigned l = (unsigned)min(4 * sp + (ln >> 4), m2 - 1);
-        const unsigned w = (unsigned)(16 * wt + (ln & 15));
-        sTabA[e] = p.twW[(l * w) % (unsigned)W];
-    }
+    UNO_INV_FILL_ROW_TWIDDLES();
+    UNO_INV_BUILD_OPERAND_TABLE()
     __syncthreads();
 
-    const int slot = wave / NW, wsub = wave - slot * NW;
-    const int image = sweep_x(p.rev) * (NWT / NW) + slot;
-    if (image >= p.n_img) return;               // no barrier below
-
+    UNO_INV_WAVE_IMAGE();
     const int ko = p.exp & 0xff;                 // development knock-outs: 1 no addend loads, 2 no spectrum reload, 4 no stores, 8 no stage 1', 16 no stage 2'
     // KSK == (m1 + 4) >> 2 k-steps of the column stage exactly (K3 compiles 2 JT + 1 >= that and skips the rest at run time: here every
     // register counts)
     constexpr int ksk = KSK;
     constexpr bool EARLY = !(NWTM <= 7 && KS <= 4);      // one wave per SIMD: operands requested DURING the tile's column loop; two waves per SIMD: after it
-    const float2* O = reinterpret_cast<const float2*>(p.in) + spectrum_index(p, image) * 2 * m1 * m2;
+    const float2* O = UNO_INV_SPECTRUM(image);
 
     // ---- the addend's loop-invariant operands: column operator, B operand of stage 1' (lane (k-slot kk, column n = r16))
     const int Hs = p.add_Hs, Ws = p.add_Ws;
@@ -100,53 +79,12 @@ __global__ __launch_bounds__(256, ((NWTM <= 7 && KS <= 4) ? 2 : 1)) void dft2d_i
 
     float* img = p.out + (size_t)image * H * W;
     const int nrt = (H + 15) >> 4;
-    float* buf = sTile + (size_t)wave * tile_stride;
-    const int dump = 16 * W + 32 + lane;
-    const float2* tabLane = sTabA + lane;
-    const int wfast_hi = W - Wh - 1;
-    const bool chain = NW == 1;
+    UNO_INV_FT_WAVE_TILE();
 
-    // column stage's A operand: P_k = O[+k] + O[-k], M_k = O[+k] - O[-k] (dft2d_inv_kernel.h), once per image
-    float Pr[NT][KSK], Pi[NT][KSK], Mr[NT][KSK], Mi[NT][KSK];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        const int l = 16 * t + 4 * (r16 & 3) + (r16 >> 2);
-        const float cs = p.scale * ((p.herm && l < m2) ? herm_weight(l, W) : 1.0f);
-#pragma unroll
-        for (int ks = 0; ks < KSK; ++ks) {
-            const int k = 4 * ks + kk;
-            float2 vp = make_float2(0.f, 0.f), vm = make_float2(0.f, 0.f);
-            if (!(ko & 2) && l < m2 && k < m1 && !(p.mask && !row_survives(k, m1, H))) vp = O[(size_t)k * m2 + l];
-            if (!(ko & 2) && l < m2 && k >= 1 && k <= m1) vm = O[(size_t)(2 * m1 - k) * m2 + l];
-            Pr[t][ks] = (vp.x + vm.x) * cs; Pi[t][ks] = (vp.y + vm.y) * cs;
-            Mr[t][ks] = (vp.x - vm.x) * cs; Mi[t][ks] = (vp.y - vm.y) * cs;
-        }
-    }
+    // column stage's A operand, once per image
+    UNO_INV_COLUMN_OPERAND(!(ko & 2))
     f32x4 Ur[NT], Ui[NT];
-    auto stage_b = [&](int rt) {
-        const unsigned hB = (unsigned)min(16 * rt + r16, H - 1);
-        const unsigned a4 = 8u * ((4u * hB) % (unsigned)H);
-        unsigned aj = 8u * (((unsigned)kk * hB) % (unsigned)H);
-#pragma unroll
-        for (int t = 0; t < NT; ++t) { Ur[t] = f32x4{0, 0, 0, 0}; Ui[t] = f32x4{0, 0, 0, 0}; }
-        float2 twb = lds_tw(sTwH, aj);
-#pragma unroll
-        for (int ks = 0; ks < KSK; ++ks) {
-            aj = wrap_add(aj, a4, H8);
-            const float2 twn = lds_tw(sTwH, aj);
-            if (ks < ksk) {
-                const float ns = -twb.y;
-#pragma unroll
-                for (int t = 0; t < NT; ++t) {
-                    Ur[t] = mfma16(Pr[t][ks], twb.x, Ur[t]);
-                    Ui[t] = mfma16(Pi[t][ks], twb.x, Ui[t]);
-                    Ur[t] = mfma16(Mi[t][ks], ns, Ur[t]);
-                    Ui[t] = mfma16(Mr[t][ks], twb.y, Ui[t]);
-                }
-            }
-            twb = twn;
-        }
-    };
+    auto stage_b = [&](int rt) { UNO_INV_STAGE_B(rt, (void)0) };
     // the addend of row tile rt, first half: operands requested (request), stage 1' of every column tile (reduce) -> Ct
     float rowB[ADD_KE], rowN[ADD_KE];           // row operator of the tile (B operand of stage 2') and of the next one
     f32x3 piece[NWTM][2];
@@ -210,12 +148,8 @@ __global__ __launch_bounds__(256, ((NWTM <= 7 && KS <= 4) ? 2 : 1)) void dft2d_i
     if (wsub < nrt) { request(wsub); stage_b(wsub); reduce(); }
 
     for (int rt = wsub; rt < nrt; rt += NW) {
-        float* tile = img + (size_t)rt * 16 * W;
-        const int rows = min(16, H - 16 * rt);
-        const int phase = (int)((reinterpret_cast<uintptr_t>(tile) >> 2) & 31);
-        const int rowbase = phase + r16 * W;
-        const bool row_ok = r16 < rows;
-        const int nfast = rows == 16 ? max(1, min(nwt, (wfast_hi + 1) >> 4)) : 1;
+        UNO_INV_FT_TILE(rt);
+        const int nfast = inv_ft_fast_tiles(rows, nwt, wfast_hi);
         const bool more = rt + NW < nrt;
         // the NEXT tile's addend operands are requested now, straight behind the previous tile's stores: they land while this tile's
         // column loop runs (that is also the time those stores have to drain - loads and stores share one in-order counter)
@@ -231,43 +165,15 @@ __global__ __launch_bounds__(256, ((NWTM <= 7 && KS <= 4) ? 2 : 1)) void dft2d_i
 #pragma unroll
             for (int sp = 0; sp < KS; ++sp) tw[0][sp] = tabLane[sp * 64];
             auto stage = [&](int wt, bool fast, const f32x4& E, const f32x4& D, const f32x4& al, const f32x4& ar) {
-                const int w0 = 16 * wt + 4 * kk;
-                const f32x4 yl = E - D + al;
-                const f32x4 yr = E + D + ar;
-                if (fast) {                                                    // (uniform) interior tile of a full row tile
-                    float* pl = buf + rowbase + w0;
-                    float* pr = buf + rowbase + W - w0 - 3;
-                    pl[0] = yl[0]; pl[1] = yl[1]; pl[2] = yl[2]; pl[3] = yl[3];
-                    pr[3] = yr[0]; pr[2] = yr[1]; pr[1] = yr[2]; pr[0] = yr[3];
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const int w = w0 + e;
-                        buf[(row_ok && w <= Wh) ? rowbase + w : dump] = yl[e];
-                        buf[(row_ok && w >= 1 && w <= wfast_hi) ? rowbase + W - w : dump] = yr[e];
-                    }
-                }
+                UNO_INV_FT_STAGE(wt, fast, E - D + al, E + D + ar)
             };
             auto is_fast = [&](int wt) { return FULL && wt >= 1 && (wt < NWTM - 1 || wt < nfast); };
 #pragma unroll
             for (int wt = 0; wt < NWTM; ++wt) {
                 const int cur = wt & 1, nx = cur ^ 1;
-                const float2* nxt = tabLane + (size_t)(wt + 1 < NWTM ? wt + 1 : wt) * (KS * 64);
-#pragma unroll
-                for (int sp = 0; sp < KS; ++sp) tw[nx][sp] = nxt[sp * 64];
-                __builtin_amdgcn_sched_barrier(0);
-                f32x4 E = f32x4{0, 0, 0, 0}, D = f32x4{0, 0, 0, 0}, al = f32x4{0, 0, 0, 0}, ar = f32x4{0, 0, 0, 0};
-#pragma unroll
-                for (int sp = 0; sp < (KS > ADD_KE ? KS : ADD_KE); ++sp) {
-                    if (sp < KS) {
-                        E = mfma16(tw[cur][sp].x, Ur[sp >> 2][sp & 3], E);
-                        D = mfma16(tw[cur][sp].y, Ui[sp >> 2][sp & 3], D);
-                    }
-                    if (sp < ADD_KE && !(ko & 16)) {
-                        al = mfma16(Ct[wt][0][sp], rowB[sp], al);
-                        ar = mfma16(Ct[wt][1][sp], rowB[sp], ar);
-                    }
-                }
+                f32x4 E, D, al = f32x4{0, 0, 0, 0}, ar = f32x4{0, 0, 0, 0};
+                UNO_INV_ROW_CHAIN(wt + 1 < NWTM ? wt + 1 : wt, tw[cur], tw[nx], E, D, KS > ADD_KE ? KS : ADD_KE,
+                                  if (sp < ADD_KE && !(ko & 16)) { al = mfma16(Ct[wt][0][sp], rowB[sp], al); ar = mfma16(Ct[wt][1][sp], rowB[sp], ar); })
                 Ey[cur] = E; Dy[cur] = D; aL[cur] = al; aR[cur] = ar;
                 // the NEXT row tile's pieces of this column tile, spread over the column loop: the previous tile's stores are still
                 // draining through the same path, two loads at a time slip in between them (all 28 at the top of the tile: 343 us)
@@ -285,82 +191,32 @@ __global__ __launch_bounds__(256, ((NWTM <= 7 && KS <= 4) ? 2 : 1)) void dft2d_i
             reduce();
         }
 
-        // ---- the tile goes out as whole 128-byte lines: LDS index i <-> memory gbase[i]
-        float* gbase = tile - phase;
-        const int total = phase + rows * W;
-        const bool first = !chain || rt == 0, last = !chain || !more;
-        const int lo = first ? phase : 0;
-        const int hi = last ? total : (total & ~31);
-        auto store_guarded = [&](int i) {
-            if (i >= hi) return;
-            if (i >= lo && i + 3 < hi) {
-                *reinterpret_cast<f32x4*>(gbase + i) = *reinterpret_cast<const f32x4*>(buf + i);
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (i + e >= lo && i + e < hi) gbase[i + e] = buf[i + e];
-            }
-        };
-        const int nfull = (ko & 4) ? 0 : (hi >> 8);
-        if (!(ko & 4)) store_guarded(4 * lane);
-        int it = 1;
-        for (; it + 4 <= nfull; it += 4) {
-            const float* src = buf + 256 * it + 4 * lane;
-            float* dst = gbase + 256 * it + 4 * lane;
-            const f32x4 v0 = *reinterpret_cast<const f32x4*>(src);
-            const f32x4 v1 = *reinterpret_cast<const f32x4*>(src + 256);
-            const f32x4 v2 = *reinterpret_cast<const f32x4*>(src + 512);
-            const f32x4 v3 = *reinterpret_cast<const f32x4*>(src + 768);
-            *reinterpret_cast<f32x4*>(dst) = v0;
-            *reinterpret_cast<f32x4*>(dst + 256) = v1;
-            *reinterpret_cast<f32x4*>(dst + 512) = v2;
-            *reinterpret_cast<f32x4*>(dst + 768) = v3;
-        }
-        for (; it < nfull; ++it)
-            *reinterpret_cast<f32x4*>(gbase + 256 * it + 4 * lane) = *reinterpret_cast<const f32x4*>(buf + 256 * it + 4 * lane);
-        if (nfull >= 1) store_guarded(256 * nfull + 4 * lane);
-        if (!last) {
-            const int rem = total & 31;
-            float v = 0.f;
-            if (lane < rem) v = buf[(total & ~31) + lane];
-            if (lane < rem) buf[lane] = v;
-        }
+        UNO_INV_FT_STORE_TILE(more, !(ko & 4), (void)0)
     }
 }
 
 // ---- launcher side: the form applies where K3-FT does (same LDS geometry), the column tiles fit the unrolled loop and the operand
 // tables are given
 static bool inv_add_shape_ok(const Dft2dParams& p) {
-    const int nwt = ((p.W >> 1) + 16) >> 4;
+    const int nwt = inv_col_tiles(p.W);
     const int KS = (p.m2 + 3) / 4, KSK = (p.m1 + 4) >> 2;
     // (the unrolled column loop is compiled for 7 and 14 column tiles: rows of 192 .. 223 and 416 .. 447 elements)
     return (nwt == 7 || nwt == 14) && KS <= 6 && KSK >= 1 && KSK <= 7 && !p.bf16 && p.add_Ws >= 4 * ADD_KE && p.add_Hs >= 1;
 }
 
 template <int KS, int KSK, int NWTM>
-static int launch_inv_add(Dft2dParams p, const InvGeometry& g, hipStream_t s) {
-    auto k = dft2d_inv_ft_add_kernel<KS, KSK, NWTM>;
-    static int lds_slot[64];
-    if (!ensure_dynamic_lds(reinterpret_cast<const void*>(k), g.lds, lds_slot)) { set_error("dft2d_inv_add: cannot raise dynamic LDS to %zu", g.lds); return -4; }
-    p.nw = g.nw;
-    p.rev = next_sweep_reversed(SWEEP_K3);
+static int launch_inv_add(const Dft2dParams& p, const InvGeometry& g, hipStream_t s) {
     char name[64];
     snprintf(name, sizeof(name), "uno::dft2d_inv_ft_add_kernel<%d, %d, %d>", KS, KSK, NWTM);
-    {
-        ProfScope prof(name, (double)p.n_img * ((double)p.H * p.W * 4.0 + (double)p.add_Hs * p.add_Ws * 4.0 + 2.0 * p.m1 * p.m2 * 8.0), s);
-        hipLaunchKernelGGL(k, dim3((p.n_img + g.g - 1) / g.g), dim3(64 * g.nw * g.g), g.lds, s, p);
-    }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("dft2d_inv_add launch: %s", hipGetErrorString(e)); return -5; }
-    return 0;
+    const double bytes = (double)p.n_img * ((double)p.H * p.W * 4.0 + (double)p.add_Hs * p.add_Ws * 4.0 + 2.0 * p.m1 * p.m2 * 8.0);
+    return launch_inv<dft2d_inv_ft_add_kernel<KS, KSK, NWTM>>(name, bytes, "dft2d_inv_add", p, g, next_sweep_reversed(SWEEP_K3), s);
 }
 
 template <int KS, int KSK>
 static int launch_inv_add_t(const Dft2dParams& p, hipStream_t s) {
     InvGeometry ft;
     if (!inv_ft_geometry(p, KS, &ft)) { set_error("dft2d_inv_add: the full-tile form does not apply to %dx%d", p.H, p.W); return -3; }
-    const int nwt = ((p.W >> 1) + 16) >> 4;
-    if (nwt == 7) return launch_inv_add<KS, KSK, 7>(p, ft, s);
+    if (inv_col_tiles(p.W) == 7) return launch_inv_add<KS, KSK, 7>(p, ft, s);
     return launch_inv_add<KS, KSK, 14>(p, ft, s);
 }
 
