@@ -406,6 +406,20 @@ long long uno_rel_l2_steps_ws_bytes(int B, long long P, int T);
 int uno_rel_l2_steps(const float* pred, const float* target, float* sums, float* rel, float* totals, void* ws, int B, long long P, int T,
                      void* stream);
 
+/* The gradient of the two totals of uno_rel_l2_steps at pred, one launch (additive: the ABI version stays 14) - the NS-3D training
+ * step takes its loss (totals[1]) and its per-step metric (totals[0]) from ONE forward pass over (out, y) with it.
+ * pred, target: the forward call's inputs; sums (B, T, 2): as the forward call wrote it; g_full, g_step: the upstream gradients of
+ * totals[1] and totals[0], one float32 each ON THE DEVICE (never read by the host), either may be NULL (= 0); gx (B, P, T): written,
+ *   gx[b][p][t] = (pred - target)[b][p][t] * (cf[b] + cs[b][t])
+ *   cf[b]       = g_full / (sqrt(sum_t num) * sqrt(sum_t den)),   cs[b][t] = g_step / (sqrt(num[b][t]) * sqrt(den[b][t]))
+ * with (num, den) = sums[b][t] and the whole-trajectory sums formed as the forward call's finish launch forms them.  A coefficient
+ * whose num is 0 is 0 (the backward of torch.linalg.vector_norm, uno_rel_l2_backward's rule); den is not clamped.  No gradient for target.
+ * Limits as the forward call: 1 <= T <= 256, P >= 1, 64-bit offsets, B == 0 returns 0 without touching the device.  No atomics; the
+ * launch is sized by the device's compute units less uno_reserve_cus, and every element is one product, so the result does not depend
+ * on that size.  16-byte loads and stores where T % 4 == 0 and pred, target and gx are 16-byte aligned, 4-byte ones otherwise. */
+int uno_rel_l2_steps_backward(const float* pred, const float* target, const float* sums, const float* g_full, const float* g_step, float* gx,
+                              int B, long long P, int T, void* stream);
+
 /* The relative L2 TRAINING loss and its gradient (additive: the ABI version stays 14).  The reference's three training loops call
  * `LpLoss(size_average=False)(x.view(B, -1), y.view(B, -1))` (utilities3.py:86-100; train_darcy.py:53, ns_train_2d.py:55,
  * ns_train_3d.py:58-64) - about six small launches forward and eight backward as stock ops, 40 times per NS-2D roll-out.

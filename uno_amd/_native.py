@@ -101,6 +101,7 @@ _SIGNATURES = {
     "uno_gelu_project2_backward": (C.c_int, [_fp] * 9 + [_i, _i, _i, C.c_longlong, _i, _fp]),
     "uno_rel_l2_steps_ws_bytes": (C.c_longlong, [_i, C.c_longlong, _i]),
     "uno_rel_l2_steps": (C.c_int, [_fp] * 6 + [_i, C.c_longlong, _i, _fp]),
+    "uno_rel_l2_steps_backward": (C.c_int, [_fp] * 6 + [_i, C.c_longlong, _i, _fp]),
     "uno_rel_l2_ws_bytes": (C.c_longlong, [_i, C.c_longlong]),
     "uno_rel_l2_forward": (C.c_int, [_fp, C.c_longlong, C.c_longlong] * 2 + [_fp] * 4 + [_i, C.c_longlong, _fp]),
     "uno_rel_l2_backward": (C.c_int, [_fp, C.c_longlong, C.c_longlong] * 2 + [_fp, _fp, _i, C.c_float, _fp, _i, C.c_longlong, _fp]),
@@ -1394,6 +1395,33 @@ def rel_l2_steps(pred, target):
         rc = L.uno_rel_l2_steps(_ptr(pred), _ptr(target), _ptr(sums), _ptr(rel), _ptr(totals), _ptr(ws), B, P, T, _stream(pred))
     _check(rc, "uno_rel_l2_steps")
     return sums, rel, totals
+
+
+def rel_l2_steps_backward(pred, target, sums, g_full=None, g_step=None):
+    """The gradient of rel_l2_steps' totals at pred, dense like pred (uno_rel_l2_steps_backward, K17-B: one launch): g_full is the
+    upstream gradient of totals[1] (the whole-trajectory loss), g_step that of totals[0] (the per-step sum) - one f32 element each on
+    the device, never read by the host; None counts as 0.  sums: (B, T, 2) of the forward call.  A term whose num is 0 is 0."""
+    _require(pred, torch.float32, "pred")
+    _require(target, torch.float32, "target")
+    _require(sums, torch.float32, "sums")
+    if pred.shape != target.shape or pred.device != target.device or pred.dim() < 2:
+        raise RuntimeError(f"uno_amd: pred {tuple(pred.shape)} on {pred.device} and target {tuple(target.shape)} on {target.device} must be "
+                           f"equal (batch, ..., time) tensors on one device")
+    B, T = pred.shape[0], pred.shape[-1]
+    P = _count(pred.shape[1:-1])
+    if sums.shape != (B, T, 2) or sums.device != pred.device:
+        raise RuntimeError(f"uno_amd: sums {tuple(sums.shape)} on {sums.device} is not the (B, T, 2) = ({B}, {T}, 2) sums of the forward call "
+                           f"on {pred.device}")
+    for name, g in (("g_full", g_full), ("g_step", g_step)):
+        if g is not None:
+            _require(g, torch.float32, name)
+            if g.numel() != 1 or g.device != pred.device:
+                raise RuntimeError(f"uno_amd: {name} {tuple(g.shape)} on {g.device} must be one element on {pred.device}")
+    with torch.cuda.device(pred.device):
+        gx = torch.empty_like(pred)
+        rc = lib().uno_rel_l2_steps_backward(_ptr(pred), _ptr(target), _ptr(sums), _opt(g_full), _opt(g_step), _ptr(gx), B, P, T, _stream(pred))
+    _check(rc, "uno_rel_l2_steps_backward")
+    return gx
 
 
 def _rel_l2_operands(x, y):

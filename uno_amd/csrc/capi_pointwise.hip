@@ -541,6 +541,14 @@ int uno_rel_l2_steps(const float* pred, const float* target, float* sums, float*
     return launch_rel_l2_steps(pred, target, sums, rel, totals, (float*)ws, B, P, T, (hipStream_t)stream);
 }
 
+int uno_rel_l2_steps_backward(const float* pred, const float* target, const float* sums, const float* g_full, const float* g_step, float* gx,
+                              int B, long long P, int T, void* stream) {
+    if (!rel_l2_steps_sizes("uno_rel_l2_steps_backward", B, P, T)) return -1;
+    if (B == 0) return 0;
+    if (!pred || !target || !sums || !gx) { set_error("uno_rel_l2_steps_backward: null pointer"); return -1; }
+    return launch_rel_l2_steps_backward(pred, target, sums, g_full, g_step, gx, B, P, T, (hipStream_t)stream);
+}
+
 // K20: the relative L2 training loss and its gradient, float32 (B, N) views with a row stride and an element stride each
 static bool rel_l2_sizes(const char* who, int B, long long N, long long xrs, long long xes, long long yrs, long long yes) {
     if (B < 0 || N < 1) { set_error("%s: bad sizes B=%d N=%lld", who, B, N); return false; }

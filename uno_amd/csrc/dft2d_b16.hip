@@ -63,16 +63,7 @@ __device__ __forceinline__ unsigned long long b16_clock() { return __builtin_rea
 constexpr int B16_WAVES = 8;            // waves per workgroup (two per SIMD)
 constexpr int B16_KSC = 8;              // forward: k-steps (of 32 columns) per chunk = per table
 
-static int b16_cu_count() {
-    static int cus[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (cus[dev] == 0) {
-        hipDeviceProp_t prop;
-        cus[dev] = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-    }
-    return usable_cus(cus[dev]);
-}
+static int b16_cu_count() { return current_usable_cus(); }
 
 static int b16_exp(const char* name, int dflt) {
     const char* e = getenv(name);

@@ -1,4 +1,4 @@
-// K17 - the per-time-step relative L2 error of the NS-3D loop in one pass over pred and target (forward only):
+// K17 - the per-time-step relative L2 error of the NS-3D loop in one pass over pred and target (its gradient: K17-B, at the end):
 //
 //   sums[b][t]  = [ sum_p (pred[b][p][t] - target[b][p][t])^2,  sum_p target[b][p][t]^2 ]
 //   rel[b][t]   = sqrt(num) / sqrt(den) for t < T;  rel[b][T] = sqrt(sum_t num) / sqrt(sum_t den)
@@ -17,6 +17,7 @@
 // consecutive addresses.  The loads are scalar (4 bytes per lane): a batch entry starts b * P * T floats into the tensor, which is
 // not 16-byte aligned when P * T is odd, and a 16-byte lane would carry four different t.  Threads with equal t are combined
 // through LDS in ascending thread order.
+#include <cstdint>
 #include "uno_common.h"
 
 namespace uno {
@@ -159,6 +160,95 @@ int launch_rel_l2_steps(const float* pred, const float* target, float* sums, flo
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_error("rel_l2_steps partial launch: %s", hipGetErrorString(e)); return -5; }
     return launch_rel_l2_steps_finish(ws, sums, rel, totals, B, T, nc, s);
+}
+
+// K17-B - the gradient of totals[1] (whole-trajectory loss, upstream g_full) and totals[0] (per-step sum, upstream g_step) at pred:
+//
+//   gx[b][p][t] = (pred - target)[b][p][t] * (cf[b] + cs[b][t])
+//   cf[b]       = g_full / (sqrt(sum_t num) * sqrt(sum_t den)),   cs[b][t] = g_step / (sqrt(num[b][t]) * sqrt(den[b][t]))
+//
+// with (num, den) = sums[b][t] of the forward call and the whole-trajectory sums formed as the finish kernel forms them (lanes over t
+// in double, xor-shuffle wave sum, rounded once).  A coefficient whose num is 0 is 0 (K20's rule, the backward of
+// torch.linalg.vector_norm); den is not clamped.  Every element is its own product, so the result does not depend on how the elements
+// are spread over workgroups: the launch is sized by the device (usable_cus) and W workgroups share one batch entry, each loading that
+// entry's T + 1 coefficients into LDS once.  V = 4: T % 4 == 0 and the three bases 16-byte aligned - a lane's four elements then lie in
+// one pixel (no wrap of t) and every batch entry starts aligned.  The host reads neither g_full nor g_step.
+template <int V>
+__global__ __launch_bounds__(RL2_THREADS) void rel_l2_steps_backward_kernel(const float* __restrict__ pred, const float* __restrict__ target,
+                                                                            const float* __restrict__ sums, const float* __restrict__ g_full,
+                                                                            const float* __restrict__ g_step, float* __restrict__ gx,
+                                                                            long long P, int T, int W) {
+    __shared__ float s_c[RL2_THREADS + 1];                      // cs[t] for t < T, cf at [T]
+    const int tid = threadIdx.x;
+    const long long b = blockIdx.x / (unsigned)W;
+    const int w = (int)(blockIdx.x % (unsigned)W);
+    if (tid < 64) {
+        const float gs = g_step ? g_step[0] : 0.f;
+        double num_b = 0.0, den_b = 0.0;
+        for (int t = tid; t < T; t += 64) {
+            const size_t o = (size_t)b * T + t;
+            const float fn = sums[2 * o], fd = sums[2 * o + 1];
+            s_c[t] = fn == 0.f ? 0.f : gs / (sqrtf(fn) * sqrtf(fd));
+            num_b += (double)fn; den_b += (double)fd;
+        }
+        num_b = rl2_wave_sum(num_b);
+        den_b = rl2_wave_sum(den_b);
+        if (tid == 0) {
+            const float fn = (float)num_b, fd = (float)den_b;
+            s_c[T] = fn == 0.f ? 0.f : (g_full ? g_full[0] : 0.f) / (sqrtf(fn) * sqrtf(fd));
+        }
+    }
+    __syncthreads();
+    const float cf = s_c[T];
+    const long long n = P * T;                                  // elements of a batch entry
+    const size_t base = (size_t)b * (size_t)n;
+    const long long stride = (long long)W * RL2_THREADS * V;
+    long long e = ((long long)w * RL2_THREADS + tid) * V;
+    int t = (int)(e % T);
+    const int dt = (int)(stride % T);
+    if (V == 4) {
+        for (; e < n; e += stride) {                            // n % 4 == 0: a whole group of four or nothing
+            const float4 x = *reinterpret_cast<const float4*>(pred + base + e);
+            const float4 y = *reinterpret_cast<const float4*>(target + base + e);
+            *reinterpret_cast<float4*>(gx + base + e) = make_float4((x.x - y.x) * (cf + s_c[t]), (x.y - y.y) * (cf + s_c[t + 1]),
+                                                                    (x.z - y.z) * (cf + s_c[t + 2]), (x.w - y.w) * (cf + s_c[t + 3]));
+            t += dt;
+            if (t >= T) t -= T;
+        }
+    } else {
+        for (; e < n; e += stride) {
+            gx[base + e] = (pred[base + e] - target[base + e]) * (cf + s_c[t]);
+            t += dt;
+            if (t >= T) t -= T;
+        }
+    }
+}
+
+static bool rl2_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+int launch_rel_l2_steps_backward(const float* pred, const float* target, const float* sums, const float* g_full, const float* g_step, float* gx,
+                                 int B, long long P, int T, hipStream_t s) {
+    const bool wide = T % 4 == 0 && rl2_aligned16(pred) && rl2_aligned16(target) && rl2_aligned16(gx);
+    const long long per_wg = (long long)RL2_THREADS * (wide ? 4 : 1);
+    const long long n = P * T;
+    // workgroups per batch entry: eight per usable CU over the whole launch, never more than the entry has work for
+    long long W = ((long long)current_usable_cus() * 8 + B - 1) / B;
+    const long long most = (n + per_wg - 1) / per_wg;
+    if (W > most) W = most;
+    if (W < 1) W = 1;
+    if (W * B > 0x7fffffffLL) { set_error("rel_l2_steps_backward: %lld workgroups x %d batch entries exceed the grid limit", W, B); return -2; }
+    {
+        ProfScope prof("uno::rel_l2_steps_backward_kernel", 12.0 * B * (double)P * T, s);
+        if (wide)
+            hipLaunchKernelGGL(rel_l2_steps_backward_kernel<4>, dim3((unsigned)(W * B)), dim3(RL2_THREADS), 0, s, pred, target, sums, g_full, g_step,
+                               gx, P, T, (int)W);
+        else
+            hipLaunchKernelGGL(rel_l2_steps_backward_kernel<1>, dim3((unsigned)(W * B)), dim3(RL2_THREADS), 0, s, pred, target, sums, g_full, g_step,
+                               gx, P, T, (int)W);
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { set_error("rel_l2_steps_backward launch: %s", hipGetErrorString(e)); return -5; }
+    return 0;
 }
 
 }  // namespace uno

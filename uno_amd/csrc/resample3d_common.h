@@ -14,21 +14,10 @@ constexpr int RA_THREADS = 256;
 __host__ __device__ __forceinline__ unsigned ra_magic(int N) { return 0xFFFFFFFFu / (unsigned)N + 1u; }
 __device__ __forceinline__ int ra_mod(int f, int N) { f %= N; return f < 0 ? f + N : f; }       // table entries are the caller's: keep every twiddle index inside the table
 
-static int ra_cus() {
-    static int cus[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!cus[dev]) {
-        hipDeviceProp_t prop;
-        cus[dev] = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-    }
-    return usable_cus(cus[dev]);
-}
-
 // persistent grid: the usable CUs x the workgroups of RA_THREADS threads a CU holds beside each other at this LDS size (at most 8)
 static int ra_grid(long long n_items, size_t lds) {
     const long long per_cu = std::max<long long>(1, std::min<long long>(8, (160 * 1024) / (long long)std::max<size_t>(lds, 1)));
-    return (int)std::max<long long>(1, std::min<long long>(n_items, (long long)ra_cus() * per_cu));
+    return (int)std::max<long long>(1, std::min<long long>(n_items, (long long)current_usable_cus() * per_cu));
 }
 
 static int ra_check(const char* who) {

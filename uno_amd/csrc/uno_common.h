@@ -304,6 +304,17 @@ int reserved_cus();
 int next_sweep_reversed(int family);       // family: SWEEP_* bit (uno_sweep_alternation takes a mask of them; 1 = all)
 enum { SWEEP_K1 = 1, SWEEP_K3 = 2, SWEEP_K7 = 4, SWEEP_K8 = 8, SWEEP_K9 = 16, SWEEP_NORM = 32, SWEEP_PROJ = 64, SWEEP_LIFT = 128 };
 inline int usable_cus(int device_cus) { const int r = reserved_cus(); return device_cus - r >= 8 ? device_cus - r : (device_cus < 8 ? device_cus : 8); }
+// usable_cus of the current device; its compute-unit count is asked for once per device (256 where the query fails)
+inline int current_usable_cus() {
+    static int cus[64] = {0};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+    if (!cus[dev]) {
+        hipDeviceProp_t prop;
+        cus[dev] = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
+    }
+    return usable_cus(cus[dev]);
+}
 
 // RAII timing scope around one kernel launch (no-op unless uno_profile_begin() is active).
 struct ProfScope {
@@ -440,6 +451,9 @@ long long rel_l2_steps_ws_floats(int B, long long P, int T);
 int launch_rel_l2_steps(const float* pred, const float* target, float* sums, float* rel, float* totals, float* ws, int B, long long P, int T,
                         hipStream_t s);
 int launch_rel_l2_steps_finish(const float* ws, float* sums, float* rel, float* totals, int B, int T, long long nc, hipStream_t s);
+// K17-B: the gradient of totals[1] (g_full) and totals[0] (g_step) at pred; g_full / g_step: device scalars, NULL = 0
+int launch_rel_l2_steps_backward(const float* pred, const float* target, const float* sums, const float* g_full, const float* g_step, float* gx,
+                                 int B, long long P, int T, hipStream_t s);
 // rollout.hip (K18): one step of the NS-2D evaluation roll-out - chunk partials of step t into ws (K17's layout), pred[b][t] = frame, the
 // window's frames moved up by one in place; ws: rollout_ws_floats() floats
 long long rollout_chunks(long long P, long long* chunk_pixels);       // chunk count: a function of P alone

@@ -1,0 +1,433 @@
+"""Epoch runners: the reference's three training loops (train_darcy.py:35-100, ns_train_2d.py:34-168, ns_train_3d.py:34-147) restated
+epoch for epoch on this package's pieces, and a command line around them:
+
+    python -m uno_amd.harness.fit {darcy,ns2d,ns3d} --data FILE ...
+
+Kept from each loop: Adam(lr, weight_decay) with StepLR(step, gamma) stepped where that loop steps it (after the training batches for
+Darcy and NS-3D; after the validation pass - hence on even epochs only - for NS-2D), the figures it prints (both Navier-Stokes loops
+validate on even epochs only), the best validation figure selecting the saved state_dict, and the test pass on those best weights.
+
+Left out - host-side habits only, the arithmetic of an epoch is the reference's:
+  * `x.cuda()` from pageable memory per batch: a DeviceDataset keeps a split on the device (any iterable of (x, y) batches is taken too;
+    its batches are moved to the model's device where they are not there already, in the order the iterable gives them);
+  * `loss.item()` per batch: batch losses are summed on the device, ONE read-back per phase (training, validation, test) and epoch;
+  * `gc.collect()` per batch and `torch.cuda.empty_cache()` per epoch;
+  * T_f + 1 loss calls per NS-3D batch: `ns3d_loss(native=True)` takes loss and step error from one pass (K17 / K17-B).
+Device tensors take the native loss paths (K20 through LpLoss for Darcy, the native roll-out for NS-2D, step_losses for NS-3D);
+`native=False` switches each back to stock ops.  graph=True replays every full-size training batch through a GraphedStep whose
+optimiser update is inside the graph (and NS-2D's evaluation roll-outs through a GraphedRollout); a short last batch runs eagerly.
+
+The runners take any model with the reference's call convention and import nothing from the oracle."""
+from __future__ import annotations
+
+import argparse
+import time
+from dataclasses import dataclass, field
+from typing import List, Optional, Tuple
+
+import torch
+
+from .data import DeviceDataset, load_darcy, load_ns
+from .losses import LpLoss, _step_errors_stock, lp_loss_rel_sum, step_errors
+from .optim import ComplexAdam
+from .train import GraphedRollout, GraphedStep, ns2d_rollout_errors, ns2d_rollout_loss, ns3d_evaluate, ns3d_loss
+
+
+@dataclass
+class EpochRecord:
+    epoch: int
+    lr: float                       # the learning rate the epoch's updates ran with
+    seconds: float
+    train: float
+    val: Optional[float]            # None: the loop does not validate in this epoch
+
+
+@dataclass
+class FitRecord:
+    """What a runner returns: one EpochRecord per epoch, the best validation figure and its epoch, the test figures on the best
+    weights (Darcy: (test_l2,); NS-2D: (per-step, whole trajectory); NS-3D: (whole trajectory, per-step) - each loop's own print
+    order), and the best state_dict where no weight_path was given."""
+    epochs: List[EpochRecord] = field(default_factory=list)
+    best_epoch: int = -1
+    best_val: float = 100000.0
+    test: Tuple[float, ...] = ()
+    state_dict: Optional[dict] = None
+
+
+def _device_of(model):
+    return next(model.parameters()).device
+
+
+def _batches(data, batch_size, shuffle, generator, device):
+    """one pass over a split: a DeviceDataset's own batches, or the iterable's in its order, on `device`"""
+    if isinstance(data, DeviceDataset):
+        if batch_size is None:
+            raise ValueError("a DeviceDataset split needs batch_size")
+        yield from data.batches(batch_size, shuffle=shuffle, generator=generator)
+        return
+    for x, y in data:
+        yield (x if x.device == device else x.to(device, non_blocking=True)), (y if y.device == device else y.to(device, non_blocking=True))
+
+
+class _Counted:
+    """an iterable of batches that counts the samples it hands out"""
+
+    def __init__(self, batches):
+        self.batches, self.samples = batches, 0
+
+    def __iter__(self):
+        for x, y in self.batches:
+            self.samples += int(x.shape[0])
+            yield x, y
+
+
+class _Sum:
+    """batch figures summed on the device; read() is the phase's one read-back"""
+
+    def __init__(self):
+        self.total, self.count = None, 0
+
+    def add(self, value, n):
+        value = value.detach()
+        self.total = value if self.total is None else self.total + value
+        self.count += int(n)
+
+    def read(self):
+        """-> the sums as a list of floats (one device read for all of them)"""
+        if self.total is None:
+            raise ValueError("an empty split: no batch to train or evaluate on")
+        return self.total.reshape(-1).tolist()
+
+
+class _Trainer:
+    """optimiser + scheduler + the training step of one runner, eager or replayed"""
+
+    def __init__(self, model, loss_fn, lr, weight_decay, scheduler_step, scheduler_gamma, graph):
+        self.model, self.loss_fn = model, loss_fn
+        self.graph = bool(graph) and _device_of(model).type == "cuda"
+        if graph and not self.graph:
+            raise RuntimeError("graph=True needs the model on the GPU (HIP graph capture)")
+        self.opt = ComplexAdam(model.parameters(), lr=lr, weight_decay=weight_decay, capturable=self.graph)
+        self.scheduler = torch.optim.lr_scheduler.StepLR(self.opt, step_size=scheduler_step, gamma=scheduler_gamma)
+        self.extra = None           # a second figure of the step (NS-3D: the step error), set by loss_fn
+        self._graphed, self._shapes, self._extra_static = None, None, None
+
+    def lr(self):
+        return float(self.opt.param_groups[0]["lr"])
+
+    def _eager(self, x, y):
+        self.opt.zero_grad(set_to_none=True)
+        loss = self.loss_fn(x, y)
+        loss.backward()
+        self.opt.step()
+        return loss.detach()
+
+    def step(self, x, y):
+        """-> the batch's loss (device tensor, detached); self.extra holds loss_fn's second figure where it has one"""
+        if not self.graph:
+            return self._eager(x, y)
+        if self._graphed is None:
+            self._graphed, self._shapes = GraphedStep(self.model, self.opt, self.loss_fn, (x, y)), (x.shape, y.shape)
+            self._extra_static = self.extra         # graph-owned: rewritten by every replay
+        if (x.shape, y.shape) == self._shapes:
+            loss = self._graphed.step(x, y)
+            self.extra = None if self._extra_static is None else self._extra_static.clone()
+            return loss
+        # a short last batch: eagerly, with the captured gradients set aside (the graph's update reads them where they lie)
+        params = [p for g in self.opt.param_groups for p in g["params"]]
+        kept = [p.grad for p in params]
+        for p in params:
+            p.grad = None
+        loss = self._eager(x, y)
+        for p, g in zip(params, kept):
+            p.grad = g
+        return loss
+
+
+class _Best:
+    """the weights of the best validation epoch: saved to a path (as the reference does) or kept in memory"""
+
+    def __init__(self, model, weight_path, record, epochs):
+        if epochs < 1:
+            raise ValueError(f"epochs = {epochs}: a run needs at least one epoch (epoch 0 is the first that validates)")
+        self.model, self.path, self.record = model, weight_path, record
+
+    def offer(self, val, epoch, log, announce):
+        if self.record.best_val > val:
+            log(announce, self.record.best_val - val)
+            self.record.best_val, self.record.best_epoch = val, epoch
+            if self.path is not None:
+                torch.save(self.model.state_dict(), self.path)
+            else:
+                self.record.state_dict = {k: v.detach().clone() for k, v in self.model.state_dict().items()}
+
+    def restore(self):
+        if self.record.best_epoch < 0:
+            raise RuntimeError(f"no validation figure was below the starting value {self.record.best_val} (a NaN or inf loss?): no weights "
+                               "were kept, so there is nothing to run the test pass on")
+        self.model.load_state_dict(torch.load(self.path, map_location=_device_of(self.model)) if self.path is not None
+                                   else self.record.state_dict)
+
+
+def _evaluate(model, batches, figures):
+    """eval mode, no_grad: figures(model, x, y) -> 1-D device tensor per batch, summed -> (list of floats, sample count); one read-back"""
+    was_training = model.training
+    model.eval()
+    total = _Sum()
+    try:
+        with torch.no_grad():
+            for x, y in batches:
+                total.add(figures(model, x, y), x.shape[0])
+    finally:
+        model.train(was_training)
+    return total.read(), total.count
+
+
+def fit_darcy(model, train, val, test, batch_size=None, epochs=150, lr=1e-4, scheduler_step=50, scheduler_gamma=0.5, weight_decay=1e-3,
+              weight_path=None, native=True, graph=False, generator=None, log=print) -> FitRecord:
+    """train_darcy.py:35-100.  train / val / test: a DeviceDataset (batch_size then applies, training batches shuffled) or an iterable
+    of (x (B, s, s, 1), y (B, s, s)) batches.  Figures: sums of per-sample relative L2 errors over the split's sample count."""
+    device = _device_of(model)
+    myloss = LpLoss(size_average=False) if native else lp_loss_rel_sum
+
+    def loss_fn(x, y):
+        B = x.shape[0]
+        return myloss(model(x).reshape(B, -1), y.reshape(B, -1))
+
+    trainer = _Trainer(model, loss_fn, lr, weight_decay, scheduler_step, scheduler_gamma, graph)
+    record = FitRecord()
+    best = _Best(model, weight_path, record, epochs)
+    t1 = time.perf_counter()
+    for ep in range(epochs):
+        model.train()
+        t1 = time.perf_counter()
+        lr_now = trainer.lr()
+        total = _Sum()
+        for x, y in _batches(train, batch_size, True, generator, device):
+            total.add(trainer.step(x, y), x.shape[0])
+        trainer.scheduler.step()
+        train_l2 = total.read()[0] / total.count
+        (v,), nval = _evaluate(model, _batches(val, batch_size, False, None, device), lambda m, x, y: loss_fn(x, y).reshape(1))
+        val_l2 = v / nval
+        t2 = time.perf_counter()
+        best.offer(val_l2, ep, log, "..Saving Model..")
+        log(ep, t2 - t1, train_l2, val_l2)
+        record.epochs.append(EpochRecord(ep, lr_now, t2 - t1, train_l2, val_l2))
+    best.restore()
+    (t,), ntest = _evaluate(model, _batches(test, batch_size, False, None, device), lambda m, x, y: loss_fn(x, y).reshape(1))
+    record.test = (t / ntest,)
+    log(epochs - 1, time.perf_counter() - t1, "Test Error", record.test[0])
+    return record
+
+
+def fit_ns2d(model, train, val, test, T_f=10, step=1, batch_size=None, epochs=150, lr=1e-4, scheduler_step=100, scheduler_gamma=0.5,
+             weight_decay=1e-3, weight_path=None, native=True, graph=False, generator=None, log=print) -> FitRecord:
+    """ns_train_2d.py:34-168.  Batches: xx (B, S, S, T_in), yy (B, S, S, T_f).  Odd epochs train only; even epochs validate, step the
+    scheduler and offer their weights.  native: the cat-free training roll-out (ns2d_rollout_loss(native=True)) and the native
+    evaluation roll-out; native=False: the reference's window-by-window forms.  graph=True needs the native evaluation roll-out's
+    conditions (GraphedRollout) and step == 1."""
+    device = _device_of(model)
+    per = T_f / step
+
+    def loss_fn(xx, yy):
+        return ns2d_rollout_loss(model, xx, yy, T_f, step, native=native)
+
+    def errors(m, xx, yy):
+        if native:
+            e = ns2d_rollout_errors(m, xx, yy, T_f, step).errors
+            return torch.stack((e.step_sum, e.full_sum))
+        # the reference's own evaluation: the loss of every group of `step` frames, and the whole trajectory
+        B, loss, pred = yy.shape[0], 0, None
+        for t in range(0, T_f, step):
+            im = m(xx)
+            loss = loss + lp_loss_rel_sum(im.reshape(B, -1), yy[..., t:t + step].reshape(B, -1))
+            pred = im if pred is None else torch.cat((pred, im), -1)
+            xx = torch.cat((xx[..., step:], im), dim=-1)
+        return torch.stack((loss, lp_loss_rel_sum(pred.reshape(B, -1), yy.reshape(B, -1))))
+
+    trainer = _Trainer(model, loss_fn, lr, weight_decay, scheduler_step, scheduler_gamma, graph)
+    rollout = {}                    # graph=True: the captured evaluation roll-out, by batch shape
+
+    def errors_graphed(m, xx, yy):
+        key = (tuple(xx.shape), tuple(yy.shape))
+        if not rollout:
+            rollout[key] = GraphedRollout(m, T_f, (xx, yy))         # (called under eval mode: the captured one)
+        if key not in rollout:
+            return errors(m, xx, yy)
+        e = rollout[key].errors(xx, yy).errors
+        return torch.stack((e.step_sum, e.full_sum))
+
+    figures = errors_graphed if trainer.graph and native and step == 1 else errors
+    record = FitRecord()
+    best = _Best(model, weight_path, record, epochs)
+    for ep in range(epochs):
+        model.train()
+        t1 = time.perf_counter()
+        lr_now = trainer.lr()
+        total = _Sum()
+        for xx, yy in _batches(train, batch_size, True, generator, device):
+            total.add(trainer.step(xx, yy), yy.shape[0])
+        train_loss = total.read()[0] / total.count / per
+        if ep % 2 == 1:
+            t2 = time.perf_counter()
+            log("epochs", ep, "time", t2 - t1, "train_loss", train_loss)
+            record.epochs.append(EpochRecord(ep, lr_now, t2 - t1, train_loss, None))
+            continue
+        (v, _), nval = _evaluate(model, _batches(val, batch_size, False, None, device), figures)
+        val_loss = v / nval / per
+        t2 = time.perf_counter()
+        trainer.scheduler.step()
+        best.offer(val_loss, ep, log, "model saved")
+        log("epochs", ep, "time", t2 - t1, "train_loss ", train_loss, "val_loss", val_loss)
+        record.epochs.append(EpochRecord(ep, lr_now, t2 - t1, train_loss, val_loss))
+    log("Traning Ended")
+    best.restore()
+    (s, f), ntest = _evaluate(model, _batches(test, batch_size, False, None, device), figures)
+    record.test = (s / ntest / per, f / ntest)
+    log("Test set Evaluation ", "Test_loss", record.test[0], record.test[1])
+    return record
+
+
+def fit_ns3d(model, train, val, test, T_f=10, batch_size=None, epochs=150, lr=1e-4, scheduler_step=50, scheduler_gamma=0.5,
+             weight_decay=1e-3, weight_path=None, native=True, graph=False, generator=None, log=print) -> FitRecord:
+    """ns_train_3d.py:34-147.  Batches: x (B, S, S, T_in, 1), y (B, S, S, T_f).  The training figure is the per-step error of every
+    batch's own forward pass; validation (per-step error) runs on even epochs only; the test pass reports the whole-trajectory and the
+    per-step error.  native: loss and step error of a training batch from ONE step_losses call; native=False: lp_loss_rel_sum and the
+    slice-by-slice metric."""
+    device = _device_of(model)
+
+    def loss_fn(x, y):
+        loss, trainer.extra = ns3d_loss(model, x, y, with_step_error=True, native=native)
+        return loss
+
+    def figures(m, x, y):
+        B, S = x.shape[0], x.shape[1]
+        e = (step_errors if native else _step_errors_stock)(m(x).view(B, S, S, T_f), y.reshape(B, S, S, T_f))
+        return torch.stack((e.full_sum, e.step_sum))
+
+    trainer = _Trainer(model, loss_fn, lr, weight_decay, scheduler_step, scheduler_gamma, graph)
+    record = FitRecord()
+    best = _Best(model, weight_path, record, epochs)
+    for ep in range(epochs):
+        t1 = time.perf_counter()
+        lr_now = trainer.lr()
+        model.train()
+        total = _Sum()
+        for x, y in _batches(train, batch_size, True, generator, device):
+            trainer.step(x, y)
+            total.add(trainer.extra, x.shape[0])
+        trainer.scheduler.step()
+        train_loss = total.read()[0] / (total.count * T_f)
+        if ep % 2 == 1:
+            t2 = time.perf_counter()
+            log("epochs", ep, "time", t2 - t1, "train_loss ", train_loss)
+            record.epochs.append(EpochRecord(ep, lr_now, t2 - t1, train_loss, None))
+            continue
+        if native:
+            counted = _Counted(_batches(val, batch_size, False, None, device))
+            val_loss = ns3d_evaluate(model, counted).item() / (counted.samples * T_f)
+        else:
+            (_, v), nval = _evaluate(model, _batches(val, batch_size, False, None, device), figures)
+            val_loss = v / (nval * T_f)
+        t2 = time.perf_counter()
+        log("epochs", ep, "time", t2 - t1, "train_loss ", train_loss, "Val_loss  ", val_loss)
+        best.offer(val_loss, ep, log, "model saved")
+        record.epochs.append(EpochRecord(ep, lr_now, t2 - t1, train_loss, val_loss))
+    log("Traning Ended")
+    best.restore()
+    (f, s), ntest = _evaluate(model, _batches(test, batch_size, False, None, device), figures)
+    record.test = (f / ntest, s / (ntest * T_f))
+    log("*** Test error: ", record.test[0], record.test[1])
+    return record
+
+
+# ---------------------------------------------------------------------------------------------------------------------- command line
+def _split(a, u, ntrain, nval, ntest, seed):
+    """shuffle once, then [train | val | test] as the reference's main scripts cut them (darcy_flow_main.py, ns_uno*_main.py)"""
+    n = a.shape[0]
+    if ntrain + nval + ntest > n:
+        raise SystemExit(f"--ntrain {ntrain} + --nval {nval} + --ntest {ntest} exceed the {n} samples read")
+    order = torch.randperm(n, generator=torch.Generator().manual_seed(seed))
+    cuts = (order[:ntrain], order[ntrain:ntrain + nval], order[ntrain + nval:ntrain + nval + ntest])
+    return [(a[i], u[i]) for i in cuts]
+
+
+def _model(args, default_cls):
+    from . import models
+    name = args.model or default_cls
+    if not hasattr(models, name):
+        raise SystemExit(f"model {name}: no such class in uno_amd.harness.models (the 3-D classes are per output length: --t-f 9, 10, 20 or 40, "
+                         "or name one with --model)")
+    kw = {}
+    if args.pad is not None:
+        kw["pad"] = args.pad
+    if args.factor is not None:
+        kw["factor"] = args.factor
+    return getattr(models, name)(args.in_width, args.width, **kw)
+
+
+def main(argv=None) -> FitRecord:
+    ap = argparse.ArgumentParser(prog="python -m uno_amd.harness.fit", description="Train a U-NO model from a dataset file (.mat)")
+    ap.add_argument("loop", choices=("darcy", "ns2d", "ns3d"))
+    ap.add_argument("--data", required=True, help="the file harness.darcy_datagen (darcy) or harness.datagen (ns2d, ns3d) wrote")
+    ap.add_argument("--model", default=None, help="class of uno_amd.harness.models (default: UNO_9 / UNO / Uno3D_T<t-f>)")
+    ap.add_argument("--in-width", type=int, default=None, help="input channels incl. positional features (default: 3 / T_in + 2 / 6)")
+    ap.add_argument("--width", type=int, default=32)
+    ap.add_argument("--pad", type=int, default=None)
+    ap.add_argument("--factor", type=float, default=None)
+    ap.add_argument("--ntrain", type=int, required=True)
+    ap.add_argument("--nval", type=int, required=True)
+    ap.add_argument("--ntest", type=int, required=True)
+    ap.add_argument("--sub", type=int, default=1, help="darcy: keep every sub-th grid point")
+    ap.add_argument("--size", type=int, default=64, help="ns2d / ns3d: resize the frames to size x size")
+    ap.add_argument("--samples", type=int, default=None, help="ns2d / ns3d: samples in the file (default: ntrain + nval + ntest)")
+    ap.add_argument("--gen-batch", type=int, default=20, help="ns2d / ns3d: the generator's batch size (samples per field of the file)")
+    ap.add_argument("--t-in", type=int, default=10)
+    ap.add_argument("--t-f", type=int, default=10)
+    ap.add_argument("--batch-size", type=int, default=16)
+    ap.add_argument("--epochs", type=int, default=150)
+    ap.add_argument("--lr", type=float, default=1e-3)
+    ap.add_argument("--scheduler-step", type=int, default=None, help="default: the loop's own (50 / 100 / 50)")
+    ap.add_argument("--scheduler-gamma", type=float, default=0.5)
+    ap.add_argument("--weight-decay", type=float, default=1e-3)
+    ap.add_argument("--graph", action="store_true", help="replay full-size training batches from a HIP graph")
+    ap.add_argument("--stock-loss", action="store_true", help="the stock-op loss paths instead of the native ones")
+    ap.add_argument("--seed", type=int, default=10001, help="of the weights, the split and the batch order")
+    ap.add_argument("--device", default=None)
+    ap.add_argument("--out", required=True, help="where the best state_dict goes")
+    a = ap.parse_args(argv)
+
+    device = torch.device(a.device if a.device else ("cuda" if torch.cuda.is_available() else "cpu"))
+    total = a.ntrain + a.nval + a.ntest
+    if a.loop == "darcy":
+        x, y, _, _ = load_darcy(a.data, a.sub, total, 1)            # the file's first `total` samples; _split cuts them
+        default_cls, a.in_width = "UNO_9", 3 if a.in_width is None else a.in_width
+    else:
+        samples = total if a.samples is None else a.samples
+        xa, ya, xb, yb = load_ns(a.data, samples, 0, sample_num=samples, batch=a.gen_batch, T_in=a.t_in, T=a.t_f, size=a.size)
+        x, y = xa, ya
+        if x is None:
+            raise SystemExit(f"{samples} samples hold no whole generation batch of --gen-batch {a.gen_batch}: nothing was read from {a.data}")
+        if y.shape[-1] != a.t_f:
+            raise SystemExit(f"{a.data} holds {x.shape[-1] + y.shape[-1]} frames per sample: fewer than --t-in {a.t_in} + --t-f {a.t_f}")
+        if a.loop == "ns3d":
+            x = x.reshape(*x.shape, 1)
+        default_cls = "UNO" if a.loop == "ns2d" else f"Uno3D_T{a.t_f}"         # the 3-D classes are per output length: T9, T10, T20, T40
+        a.in_width = (a.t_in + 2 if a.loop == "ns2d" else 6) if a.in_width is None else a.in_width
+    parts = [DeviceDataset(p, q, device) for p, q in _split(x, y, a.ntrain, a.nval, a.ntest, a.seed)]
+    torch.manual_seed(a.seed)
+    model = _model(a, default_cls).to(device)
+    gen = torch.Generator(device=device).manual_seed(a.seed)
+    common = dict(batch_size=a.batch_size, epochs=a.epochs, lr=a.lr, scheduler_gamma=a.scheduler_gamma, weight_decay=a.weight_decay,
+                  weight_path=a.out, native=not a.stock_loss, graph=a.graph, generator=gen)
+    if a.scheduler_step is not None:
+        common["scheduler_step"] = a.scheduler_step
+    if a.loop == "darcy":
+        return fit_darcy(model, *parts, **common)
+    if a.loop == "ns2d":
+        return fit_ns2d(model, *parts, T_f=a.t_f, **common)
+    return fit_ns3d(model, *parts, T_f=a.t_f, **common)
+
+
+if __name__ == "__main__":
+    main()

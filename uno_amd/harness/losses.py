@@ -155,3 +155,43 @@ def step_errors(pred: torch.Tensor, target: torch.Tensor) -> StepErrors:
     sums, rel, totals = _native.rel_l2_steps(pred.contiguous(), target.contiguous())
     T = pred.shape[-1]
     return StepErrors(sums, rel[:, :T], rel[:, T], totals[0], totals[1])
+
+
+class _StepLossesFn(torch.autograd.Function):
+    """(pred, target) dense (B, ..., T) -> (sums, rel, step_sum, full_sum): uno_rel_l2_steps forward (K17), uno_rel_l2_steps_backward
+    (K17-B) for the gradients of the two sums.  The upstream gradients stay on the device."""
+
+    @staticmethod
+    def forward(ctx, pred, target):
+        from .. import _native
+        sums, rel, totals = _native.rel_l2_steps(pred, target)
+        ctx.save_for_backward(pred, target, sums)
+        ctx.mark_non_differentiable(sums, rel)
+        ctx.set_materialize_grads(False)                # a sum nobody used arrives as None: NULL for the kernel, no zero fill
+        return sums, rel, totals[0], totals[1]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, _g_sums, _g_rel, g_step, g_full):
+        from .. import _native
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        pred, target, sums = ctx.saved_tensors
+        g_step, g_full = (None if g is None else g.to(torch.float32).reshape(1).contiguous() for g in (g_step, g_full))
+        return _native.rel_l2_steps_backward(pred, target, sums, g_full, g_step), None
+
+
+def step_losses(pred: torch.Tensor, target: torch.Tensor) -> StepErrors:
+    """step_errors whose `full_sum` (the NS-3D training loss, LpLoss(size_average=False) of the whole trajectory) and `step_sum` (the
+    per-step metric) carry gradient to pred: ONE pass over (pred, target) gives both, one more launch their gradient (K17 / K17-B) -
+    the reference's loop computes the two in T + 1 separate loss calls (ns_train_3d.py:55-64).  The other fields carry no gradient.
+    Same fall-back rule as step_errors: CPU tensors, other dtypes, T > 256 and empty tensors take the stock slice-by-slice form, through
+    which autograd differentiates all five fields.  No gradient reaches target on the native path (it is detached)."""
+    if pred.shape != target.shape or pred.dim() < 2:
+        raise RuntimeError(f"step_losses: pred {tuple(pred.shape)} and target {tuple(target.shape)} must be equal (B, ..., T) shapes")
+    if not (pred.is_cuda and target.is_cuda and pred.dtype == torch.float32 and target.dtype == torch.float32
+            and 1 <= pred.shape[-1] <= NATIVE_STEP_ERRORS_MAX_T and pred.shape[0] > 0 and pred[0].numel() > 0):
+        return _step_errors_stock(pred, target)
+    sums, rel, step_sum, full_sum = _StepLossesFn.apply(pred.contiguous(), target.detach().contiguous())
+    T = pred.shape[-1]
+    return StepErrors(sums, rel[:, :T], rel[:, T], step_sum, full_sum)

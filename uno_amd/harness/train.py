@@ -17,7 +17,7 @@ import torch
 import torch.distributed as dist
 from torch.autograd.function import once_differentiable
 
-from .losses import NATIVE_STEP_ERRORS_MAX_T, RolloutErrors, StepErrors, _step_errors_stock, lp_loss_rel_sum, step_errors
+from .losses import NATIVE_STEP_ERRORS_MAX_T, RolloutErrors, StepErrors, _step_errors_stock, lp_loss_rel_sum, step_errors, step_losses
 from .optim import ComplexAdam
 
 
@@ -507,11 +507,15 @@ def ns3d_step_error(out, y):
     return step_errors(out, y).step_sum
 
 
-def ns3d_loss(model, x, y, with_step_error=False):
+def ns3d_loss(model, x, y, with_step_error=False, native=False):
     """Space-time loss of the NS-3D training step (reference ns_train_3d.py:53,64): one forward, global relative L2.
-    with_step_error=True: -> (loss, step error), the latter from the same forward's detached output under no_grad (:55-62)."""
+    with_step_error=True: -> (loss, step error), the latter from the same forward's detached output under no_grad (:55-62).
+    native=True (opt-in): loss and step error come from ONE step_losses call - two launches forward, one backward on device tensors."""
     B, S, T_f = x.shape[0], x.shape[1], y.shape[-1]
     out = model(x).view(B, S, S, T_f)
+    if native:
+        e = step_losses(out, y.reshape(B, S, S, T_f))
+        return (e.full_sum, e.step_sum.detach()) if with_step_error else e.full_sum
     loss = lp_loss_rel_sum(out.reshape(B, -1), y.reshape(B, -1))
     if not with_step_error:
         return loss
