@@ -456,6 +456,9 @@ int uno_rel_l2_backward(const float* x, long long x_row, long long x_elem, const
  *   pred[b][t][:] = frame[b][:] if pred is given;  if shift != 0 the window moves IN PLACE: window[b][k][:] = window[b][k + 1][:] for
  *   k < T_in - 1, then window[b][T_in - 1][:] = frame[b][:] (one thread moves a pixel's whole column in ascending k: no second buffer).
  *   frame, target, pred and ws must not overlap the window or each other.
+ *   Without ground truth (a free-running roll-out): target == NULL together with ws == NULL makes the same pass with no sums - only
+ *   pred[b][t][:] = frame[b][:] and the shift, of which at least one must be asked for.  T is then pred's time length and nothing else:
+ *   any T >= 1 (the cap of 256 belongs to the finish kernel's workspace).  One of target / ws without the other is refused.
  * uno_rollout_finish, after the last step (every t of 0 ... T - 1 written): the finish launch of uno_rel_l2_steps on ws -
  *   sums (B, T, 2), rel (B, T + 1), totals (2) with the meaning they have there; rel[b][T] = sqrt(sum_t num) / sqrt(sum_t den) is the
  *   whole-trajectory error, so the prediction never has to be assembled for it.

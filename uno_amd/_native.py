@@ -1510,29 +1510,41 @@ def rollout_advance(window, frame, target, pred, ws, T_in, t, shift):
     """One step of the NS-2D evaluation roll-out (uno_rollout_advance, K18), all dense f32 on one device: window (B, C, ...) channels-first
     with the frames in channels [0, T_in); frame: the model's prediction, B x P values (P = the window's pixels per channel); target
     (B, T, ...) time-major; pred like target, or None; ws from rollout_ws.  Writes the chunk sums of step t into ws, pred[:, t] = frame,
-    and with `shift` moves the window's frames up by one IN PLACE with `frame` as the newest.  Launches on the current stream."""
-    for x, name in ((window, "window"), (frame, "frame"), (target, "target")) + (((pred, "pred"),) if pred is not None else ()):
+    and with `shift` moves the window's frames up by one IN PLACE with `frame` as the newest.  Launches on the current stream.
+
+    target = None together with ws = None (a free-running roll-out): the same pass with no sums - pred[:, t] = frame and the shift, of
+    which at least one must be asked for.  pred's time length is then free (no cap of 256 steps: that is the workspace's)."""
+    if (target is None) != (ws is None):
+        raise RuntimeError("uno_amd: rollout_advance takes target and ws together, or neither (the pass without sums): got "
+                           + ("a workspace without a target" if target is None else "a target without a workspace"))
+    if target is None and pred is None and not shift:
+        raise RuntimeError("uno_amd: rollout_advance without a target has nothing to do: neither pred nor shift asks for anything")
+    layout = target if target is not None else pred         # the (B, T, ...) time-major tensor that sets T; None: shift only
+    named = [(window, "window"), (frame, "frame")] + [(x, n) for x, n in ((target, "target"), (pred, "pred")) if x is not None]
+    for x, name in named:
         _require(x, torch.float32, name)
         if x.device != window.device:
             raise RuntimeError(f"uno_amd: {name} lives on {x.device}, the window on {window.device}")
-    if window.dim() < 3 or target.dim() < 3:
+    if window.dim() < 3 or (layout is not None and layout.dim() < 3):
         raise RuntimeError(f"uno_amd: the roll-out takes a (batch, channels, ...) window and a (batch, time, ...) target "
-                           f"(got {tuple(window.shape)} and {tuple(target.shape)})")
+                           f"(got {tuple(window.shape)} and {tuple(layout.shape)})")
     B, Cw = window.shape[0], window.shape[1]
     P = _count(window.shape[2:])
-    T = target.shape[1]
+    T = layout.shape[1] if layout is not None else int(t) + 1
     if frame.dim() < 2 or frame.shape[0] != B or frame.numel() != B * P:
         raise RuntimeError(f"uno_amd: frame {tuple(frame.shape)} does not hold one value per pixel of the window {tuple(window.shape)}")
-    if target.shape[0] != B or _count(target.shape[2:]) != P:
-        raise RuntimeError(f"uno_amd: target {tuple(target.shape)} does not match the window {tuple(window.shape)}")
-    if pred is not None and pred.shape != target.shape:
+    if layout is not None and (layout.shape[0] != B or _count(layout.shape[2:]) != P):
+        raise RuntimeError(f"uno_amd: {'target' if target is not None else 'pred'} {tuple(layout.shape)} does not match the window "
+                           f"{tuple(window.shape)}")
+    if pred is not None and target is not None and pred.shape != target.shape:
         raise RuntimeError(f"uno_amd: pred {tuple(pred.shape)} and target {tuple(target.shape)} differ")
     L = lib()
-    if ws.device != window.device:
-        raise RuntimeError(f"uno_amd: ws lives on {ws.device}, the window on {window.device}")
-    _rollout_ws_check(ws, B, P, T)
+    if ws is not None:
+        if ws.device != window.device:
+            raise RuntimeError(f"uno_amd: ws lives on {ws.device}, the window on {window.device}")
+        _rollout_ws_check(ws, B, P, T)
     with torch.cuda.device(window.device):
-        rc = L.uno_rollout_advance(_ptr(window), _ptr(frame), _ptr(target), _opt(pred), _ptr(ws), B, Cw, int(T_in), P, T, int(t),
+        rc = L.uno_rollout_advance(_ptr(window), _ptr(frame), _opt(target), _opt(pred), _opt(ws), B, Cw, int(T_in), P, T, int(t),
                                    1 if shift else 0, _stream(window))
     _check(rc, "uno_rollout_advance")
 

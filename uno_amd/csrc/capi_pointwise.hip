@@ -595,13 +595,22 @@ long long uno_rollout_ws_bytes(int B, long long P, int T) {
 
 int uno_rollout_advance(float* window, const float* frame, const float* target, float* pred, void* ws, int B, int C, int T_in, long long P,
                         int T, int t, int shift, void* stream) {
-    if (!rollout_sizes("uno_rollout_advance", B, P, T)) return -1;
+    // target == NULL together with ws == NULL: the pass without sums (a free-running roll-out); T is then pred's time length only and
+    // the finish kernel's cap of 256 steps does not apply to it
+    if (!target != !ws) {
+        set_error("uno_rollout_advance: null %s beside %s (target and ws go together: both, or neither for the pass without sums)",
+                  target ? "ws" : "target", target ? "a target" : "a workspace");
+        return -1;
+    }
+    if (target) { if (!rollout_sizes("uno_rollout_advance", B, P, T)) return -1; }
+    else if (B < 0 || P < 1 || T < 1) { set_error("uno_rollout_advance: bad sizes B=%d P=%lld T=%d", B, P, T); return -1; }
     if (C < 1 || T_in < 1 || T_in > C || t < 0 || t >= T) {
         set_error("uno_rollout_advance: bad sizes C=%d T_in=%d (1 ... C) t=%d (0 ... T - 1 = %d)", C, T_in, t, T - 1);
         return -1;
     }
+    if (!target && !pred && !shift) { set_error("uno_rollout_advance: without a target, pred or shift must ask for something"); return -1; }
     if (B == 0) return 0;
-    if (!window || !frame || !target || !ws) { set_error("uno_rollout_advance: null pointer"); return -1; }
+    if (!window || !frame) { set_error("uno_rollout_advance: null pointer"); return -1; }
     return launch_rollout_advance(window, frame, target, pred, (float*)ws, B, C, T_in, P, T, t, shift, (hipStream_t)stream);
 }
 

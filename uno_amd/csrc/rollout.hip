@@ -4,6 +4,9 @@
 //   pred[b][t][p]     = frame[b][p]                                   (if pred is given)
 //   window[b][k][p]   = window[b][k + 1][p]  for k < T_in - 1,  window[b][T_in - 1][p] = frame[b][p]      (if shift)
 //
+// Without ground truth (target and ws both null: a free-running roll-out, harness.predict) the same pass runs with no sums - the second
+// and third line only.  T is then nothing but pred's time length (the 256-step cap belongs to the finish kernel's workspace).
+//
 // The reference's loops (ns_train_2d.py:94-107, 141-157) spend per step one `cat` for the window, a strided slice of the target, six
 // launches of LpLoss and a `cat` that rebuilds the whole prediction.  Here the window (B, C, P) is channels-first and moves IN PLACE:
 // its first T_in channels are the frames, the other C - T_in the model's positional features, which are never touched.  target and
@@ -71,8 +74,8 @@ __device__ __forceinline__ float ro_wave_sum(float v) {
 
 // grid: NC * B workgroups, workgroup g = b * NC + c owns pixels [c * CP, min((c + 1) * CP, P)) of batch entry b.  V = 4 needs P % 4 == 0
 // (CP is a multiple of 4 always).  window is read and written through one pointer on purpose: a thread's loads of frame k + 1 precede
-// its store of frame k in program order.
-template <int V>
+// its store of frame k in program order.  SUMS = false: no target, no ws - neither is read or written, nothing is reduced.
+template <int V, bool SUMS>
 __global__ __launch_bounds__(RO_THREADS) void rollout_advance_kernel(float* window, const float* __restrict__ frame, const float* __restrict__ target,
                                                                      float* __restrict__ pred, float2* __restrict__ ws, long long P, int C,
                                                                      int T_in, int T, int t, int shift, long long CP, int NC) {
@@ -87,14 +90,16 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_advance_kernel(float* wind
     const long long p1 = p0 + CP < P ? p0 + CP : P;
     const size_t sP = (size_t)P;
     const float* __restrict__ fr = frame + b * sP;
-    const float* __restrict__ tg = target + (b * (size_t)T + (size_t)t) * sP;
+    const float* __restrict__ tg = SUMS ? target + (b * (size_t)T + (size_t)t) * sP : nullptr;
     float* __restrict__ pr = pred ? pred + (b * (size_t)T + (size_t)t) * sP : nullptr;
     float* wn = window + b * (size_t)C * sP;
     float num = 0.f, den = 0.f;
     for (long long p = p0 + (long long)tid * V; p < p1; p += (long long)RO_THREADS * V) {
         const vec f = R::ld(fr + p);
-        const vec y = R::ld(tg + p);
-        R::acc(f, y, num, den);
+        if (SUMS) {
+            const vec y = R::ld(tg + p);
+            R::acc(f, y, num, den);
+        }
         if (pr) R::st(pr + p, f);
         if (shift) {
             float* col = wn + p;
@@ -116,6 +121,7 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_advance_kernel(float* wind
             R::st(col + (size_t)(T_in - 1) * sP, f);
         }
     }
+    if (!SUMS) return;
     num = ro_wave_sum(num);
     den = ro_wave_sum(den);
     if ((tid & 63) == 0) { s_num[tid >> 6] = num; s_den[tid >> 6] = den; }
@@ -134,14 +140,15 @@ int launch_rollout_advance(float* window, const float* frame, const float* targe
     const long long nc = rollout_chunks(P, &cp);
     if (nc * B > 0x7fffffffLL) { set_error("rollout_advance: %lld chunks x %d batch entries exceed the grid limit", nc, B); return -2; }
     {
-        const double moved = 4.0 * B * (double)P * (2 + (pred ? 1 : 0) + (shift ? 2.0 * T_in - 1 : 0));
+        // frame read (+ target read where there is one), pred written, the shift's T_in - 1 reads and T_in writes
+        const double moved = 4.0 * B * (double)P * (1 + (target ? 1 : 0) + (pred ? 1 : 0) + (shift ? 2.0 * T_in - 1 : 0));
         ProfScope prof("uno::rollout_advance_kernel", moved, s);
-        if (P % 4 == 0)
-            hipLaunchKernelGGL(rollout_advance_kernel<4>, dim3((unsigned)(nc * B)), dim3(RO_THREADS), 0, s, window, frame, target, pred, (float2*)ws, P, C,
-                               T_in, T, t, shift, cp, (int)nc);
-        else
-            hipLaunchKernelGGL(rollout_advance_kernel<1>, dim3((unsigned)(nc * B)), dim3(RO_THREADS), 0, s, window, frame, target, pred, (float2*)ws, P, C,
-                               T_in, T, t, shift, cp, (int)nc);
+#define UNO_RO_LAUNCH(V, SUMS)                                                                                                                  \
+        hipLaunchKernelGGL((rollout_advance_kernel<V, SUMS>), dim3((unsigned)(nc * B)), dim3(RO_THREADS), 0, s, window, frame, target, pred,      \
+                           (float2*)ws, P, C, T_in, T, t, shift, cp, (int)nc)
+        if (target) { if (P % 4 == 0) UNO_RO_LAUNCH(4, true); else UNO_RO_LAUNCH(1, true); }
+        else        { if (P % 4 == 0) UNO_RO_LAUNCH(4, false); else UNO_RO_LAUNCH(1, false); }
+#undef UNO_RO_LAUNCH
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_error("rollout_advance launch: %s", hipGetErrorString(e)); return -5; }

@@ -455,7 +455,7 @@ int launch_rel_l2_steps_finish(const float* ws, float* sums, float* rel, float* 
 int launch_rel_l2_steps_backward(const float* pred, const float* target, const float* sums, const float* g_full, const float* g_step, float* gx,
                                  int B, long long P, int T, hipStream_t s);
 // rollout.hip (K18): one step of the NS-2D evaluation roll-out - chunk partials of step t into ws (K17's layout), pred[b][t] = frame, the
-// window's frames moved up by one in place; ws: rollout_ws_floats() floats
+// window's frames moved up by one in place; ws: rollout_ws_floats() floats.  target == ws == NULL: the same pass without the partials
 long long rollout_chunks(long long P, long long* chunk_pixels);       // chunk count: a function of P alone
 long long rollout_ws_floats(int B, long long P, int T);
 int launch_rollout_advance(float* window, const float* frame, const float* target, float* pred, float* ws, int B, int C, int T_in, long long P,

@@ -14,11 +14,16 @@ from .darcy_datagen import darcy_grf, generate_darcy_dataset, solve_gwf, spline_
 from . import workloads  # noqa: F401,E402
 
 _FIT = ("EpochRecord", "FitRecord", "fit_darcy", "fit_ns2d", "fit_ns3d")
+_PREDICT = ("LayerPlan", "Prediction", "Predictor", "check_resolution", "load_model", "read_record")
 
 
 def __getattr__(name):
-    """the epoch runners on first use: `python -m uno_amd.harness.fit` runs that module as a script, which must not be imported before"""
+    """the epoch runners and the predict stage on first use: `python -m uno_amd.harness.fit` (`... .predict`) runs that module as a
+    script, which must not be imported before"""
     if name in _FIT:
         from . import fit
         return getattr(fit, name)
+    if name in _PREDICT:
+        from . import predict
+        return getattr(predict, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -1,7 +1,10 @@
 """Epoch runners: the reference's three training loops (train_darcy.py:35-100, ns_train_2d.py:34-168, ns_train_3d.py:34-147) restated
 epoch for epoch on this package's pieces, and a command line around them:
 
-    python -m uno_amd.harness.fit {darcy,ns2d,ns3d} --data FILE ...
+    python -m uno_amd.harness.fit {darcy,ns2d,ns3d} --data FILE ... --out W.pt
+
+The command line saves the best state_dict bare, as the reference does (its loops load the file unchanged), and beside it W.pt.json: the
+model class, its constructor arguments, the data settings, the split and the run's figures - what harness.predict needs to use the file.
 
 Kept from each loop: Adam(lr, weight_decay) with StepLR(step, gamma) stepped where that loop steps it (after the training batches for
 Darcy and NS-3D; after the validation pass - hence on even epochs only - for NS-2D), the figures it prints (both Navier-Stokes loops
@@ -21,6 +24,7 @@ The runners take any model with the reference's call convention and import nothi
 from __future__ import annotations
 
 import argparse
+import json
 import time
 from dataclasses import dataclass, field
 from typing import List, Optional, Tuple
@@ -342,14 +346,22 @@ def fit_ns3d(model, train, val, test, T_f=10, batch_size=None, epochs=150, lr=1e
 
 
 # ---------------------------------------------------------------------------------------------------------------------- command line
+RECORD_FORMAT = 1           # of the settings file main() writes beside the weights (<out>.json)
+
+
+def _split_cuts(n, ntrain, nval, ntest, seed):
+    """the sample indices of [train | val | test] among n samples: one shuffle under `seed`, then three cuts (harness.predict
+    re-creates a run's split from its record through this)"""
+    order = torch.randperm(n, generator=torch.Generator().manual_seed(seed))
+    return order[:ntrain], order[ntrain:ntrain + nval], order[ntrain + nval:ntrain + nval + ntest]
+
+
 def _split(a, u, ntrain, nval, ntest, seed):
     """shuffle once, then [train | val | test] as the reference's main scripts cut them (darcy_flow_main.py, ns_uno*_main.py)"""
     n = a.shape[0]
     if ntrain + nval + ntest > n:
         raise SystemExit(f"--ntrain {ntrain} + --nval {nval} + --ntest {ntest} exceed the {n} samples read")
-    order = torch.randperm(n, generator=torch.Generator().manual_seed(seed))
-    cuts = (order[:ntrain], order[ntrain:ntrain + nval], order[ntrain + nval:ntrain + nval + ntest])
-    return [(a[i], u[i]) for i in cuts]
+    return [(a[i], u[i]) for i in _split_cuts(n, ntrain, nval, ntest, seed)]
 
 
 def _model(args, default_cls):
@@ -366,12 +378,32 @@ def _model(args, default_cls):
     return getattr(models, name)(args.in_width, args.width, **kw)
 
 
+def checkpoint_record(a, model, record) -> dict:
+    """What the bare state_dict does not say (settings only): the loop, the model's class and constructor arguments as they were passed,
+    how the data were read and split, and the run's figures.  harness.predict builds the model and re-creates the split from it."""
+    ctor = {"in_width": int(a.in_width), "width": int(a.width)}
+    if a.pad is not None:
+        ctor["pad"] = int(a.pad)
+    if a.factor is not None:
+        ctor["factor"] = float(a.factor)
+    data = {"sub": int(a.sub)} if a.loop == "darcy" else {"size": int(a.size), "samples": a.samples, "gen_batch": int(a.gen_batch)}
+    return {"format": RECORD_FORMAT, "loop": a.loop, "model": type(model).__name__, "ctor": ctor, "t_in": int(a.t_in), "t_f": int(a.t_f), **data,
+            "ntrain": int(a.ntrain), "nval": int(a.nval), "ntest": int(a.ntest), "seed": int(a.seed),
+            "best_epoch": int(record.best_epoch), "best_val": float(record.best_val), "test": [float(v) for v in record.test]}
+
+
+def write_record(path, rec):
+    with open(path, "w") as f:
+        json.dump(rec, f, indent=1, sort_keys=True)
+        f.write("\n")
+
+
 def main(argv=None) -> FitRecord:
     ap = argparse.ArgumentParser(prog="python -m uno_amd.harness.fit", description="Train a U-NO model from a dataset file (.mat)")
     ap.add_argument("loop", choices=("darcy", "ns2d", "ns3d"))
     ap.add_argument("--data", required=True, help="the file harness.darcy_datagen (darcy) or harness.datagen (ns2d, ns3d) wrote")
     ap.add_argument("--model", default=None, help="class of uno_amd.harness.models (default: UNO_9 / UNO / Uno3D_T<t-f>)")
-    ap.add_argument("--in-width", type=int, default=None, help="input channels incl. positional features (default: 3 / T_in + 2 / 6)")
+    ap.add_argument("--in-width", type=int, default=None, help="input channels incl. positional features (default: 3 / T_in + 4 / 6)")
     ap.add_argument("--width", type=int, default=32)
     ap.add_argument("--pad", type=int, default=None)
     ap.add_argument("--factor", type=float, default=None)
@@ -413,7 +445,8 @@ def main(argv=None) -> FitRecord:
         if a.loop == "ns3d":
             x = x.reshape(*x.shape, 1)
         default_cls = "UNO" if a.loop == "ns2d" else f"Uno3D_T{a.t_f}"         # the 3-D classes are per output length: T9, T10, T20, T40
-        a.in_width = (a.t_in + 2 if a.loop == "ns2d" else 6) if a.in_width is None else a.in_width
+        # (the 2-D family's get_grid appends FOUR features - sin and cos of both coordinates)
+        a.in_width = (a.t_in + 4 if a.loop == "ns2d" else 6) if a.in_width is None else a.in_width
     parts = [DeviceDataset(p, q, device) for p, q in _split(x, y, a.ntrain, a.nval, a.ntest, a.seed)]
     torch.manual_seed(a.seed)
     model = _model(a, default_cls).to(device)
@@ -423,10 +456,13 @@ def main(argv=None) -> FitRecord:
     if a.scheduler_step is not None:
         common["scheduler_step"] = a.scheduler_step
     if a.loop == "darcy":
-        return fit_darcy(model, *parts, **common)
-    if a.loop == "ns2d":
-        return fit_ns2d(model, *parts, T_f=a.t_f, **common)
-    return fit_ns3d(model, *parts, T_f=a.t_f, **common)
+        record = fit_darcy(model, *parts, **common)
+    elif a.loop == "ns2d":
+        record = fit_ns2d(model, *parts, T_f=a.t_f, **common)
+    else:
+        record = fit_ns3d(model, *parts, T_f=a.t_f, **common)
+    write_record(a.out + ".json", checkpoint_record(a, model, record))
+    return record
 
 
 if __name__ == "__main__":
