@@ -444,6 +444,29 @@ int uno_rel_l2_forward(const float* x, long long x_row, long long x_elem, const 
 int uno_rel_l2_backward(const float* x, long long x_row, long long x_elem, const float* y, long long y_row, long long y_elem,
                         const float* sums, const float* g, int g_per_row, float scale, float* gx, int B, long long N, void* stream);
 
+/* K24 (additive: the ABI version stays 14; no reference counterpart): the shell-binned energy spectrum of real frames, the figure a
+ * turbulence surrogate is judged by next to its relative L2 error.  For a frame u of H x W samples: U = fft2(u) / (H W) with integer
+ * wavenumbers in fftfreq order, shell s(ky, kx) = round(hypot(ky, kx)) decided in integers ((2k - 1)^2 <= 4 (ky^2 + kx^2) < (2k + 1)^2),
+ * K = round(hypot(H / 2, W / 2)) + 1 shells (integer halves), E(k) = sum over BOTH Hermitian halves of |U|^2 on shell k: sum_k E(k) = mean(u^2).
+ * x: float32, B * T frames; sample b, frame t, row h, column w lies x_batch * b + x_frame * t + x_row * h + x_elem * w ELEMENTS from x:
+ *   (B, S, S, T) time-innermost is (S S T, 1, S T, T), (B, T, S, S) is (T S S, S S, S, 1), a [::r, ::r] view multiplies row and element
+ *   strides by r.  Strides are >= 0; nothing is copied.  y: an optional target (NULL: none) with strides of its own.
+ * spec, written dense: (B, T, 1, K) without y; (B, T, 3, K) = [E_x, E_y, E_{x - y}] with y - two transforms per frame pair, the third
+ *   spectrum from the difference of the two in registers, so sum_k E_{x-y} / sum_k E_y = (relative L2 error)^2.
+ * Two launches: one workgroup per (frame, band of 16 half-spectrum columns) - both DFT axes as dense sums on the f32 MFMA, |.|^2 with the
+ * Hermitian weight (2 for 0 < kx < W / 2, else 1), each shell's modes of the band added by one thread in a fixed order - then the bands
+ * added in ascending order.  The complex spectrum is never written to memory.  No atomics; the decomposition is a function of (H, W)
+ * and of whether y is given, not of B, the CU count or uno_reserve_cus: two calls, a call under uno_reserve_cus and a graph replay give
+ * the same bits, and a sample's spectrum does not depend on its batch.  No synchronisation, allocation or read-back; twiddle tables
+ * and the sorted shell lists are built on the host (float64 / integers) once per (device, H, W) and uploaded as uno_upload_table does
+ * (safe under graph capture).  8 <= H, W <= 512 (odd sizes included), T >= 1, B >= 0, B * T * ceil((W / 2 + 1) / 16) < 2^31; 64-bit
+ * offsets; B == 0 returns 0 without touching the device.  ws: scratch of uno_shell_spectrum_ws_bytes() bytes (0 for bad sizes), need
+ * not be initialised.  Errors (-1, before any launch): null x / spec / ws, sizes out of range, a negative stride. */
+long long uno_shell_spectrum_ws_bytes(int B, int T, int H, int W, int with_target);
+int uno_shell_spectrum(const float* x, long long x_batch, long long x_frame, long long x_row, long long x_elem, const float* y,
+                       long long y_batch, long long y_frame, long long y_row, long long y_elem, float* spec, void* ws, int B, int T, int H,
+                       int W, void* stream);
+
 /* One step of the NS-2D evaluation roll-out in one launch (additive: the ABI version stays 14).  The reference's validation and test
  * loops (ns_train_2d.py:94-107, 141-157) run the model T_f times under no_grad, feed each prediction back into the input window and
  * report the sum of the per-step relative L2 errors and the error of the whole trajectory; between two forward passes they spend a

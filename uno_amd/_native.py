@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import math
 import os
 import threading
 
@@ -105,6 +106,8 @@ _SIGNATURES = {
     "uno_rel_l2_ws_bytes": (C.c_longlong, [_i, C.c_longlong]),
     "uno_rel_l2_forward": (C.c_int, [_fp, C.c_longlong, C.c_longlong] * 2 + [_fp] * 4 + [_i, C.c_longlong, _fp]),
     "uno_rel_l2_backward": (C.c_int, [_fp, C.c_longlong, C.c_longlong] * 2 + [_fp, _fp, _i, C.c_float, _fp, _i, C.c_longlong, _fp]),
+    "uno_shell_spectrum_ws_bytes": (C.c_longlong, [_i] * 5),
+    "uno_shell_spectrum": (C.c_int, [_fp] + [C.c_longlong] * 4 + [_fp] + [C.c_longlong] * 4 + [_fp, _fp, _i, _i, _i, _i, _fp]),
     "uno_rollout_ws_bytes": (C.c_longlong, [_i, C.c_longlong, _i]),
     "uno_rollout_advance": (C.c_int, [_fp] * 5 + [_i, _i, _i, C.c_longlong, _i, _i, _i, _fp]),
     "uno_rollout_finish": (C.c_int, [_fp] * 4 + [_i, C.c_longlong, _i, _fp]),
@@ -1491,6 +1494,57 @@ def rel_l2_backward(x, y, sums, g, scale=1.0):
                                        float(scale), _ptr(gx), B, N, _raw_stream(x))
     _check(rc, "uno_rel_l2_backward")
     return gx
+
+
+SHELL_SPECTRUM_MIN, SHELL_SPECTRUM_MAX = 8, 512
+
+
+def shell_spectrum_ws_floats(B, T, H, W, with_target) -> int:
+    """floats of scratch one shell_spectrum call of these sizes needs (uno_shell_spectrum_ws_bytes; 0 for sizes out of range)"""
+    return int(lib().uno_shell_spectrum_ws_bytes(int(B), int(T), int(H), int(W), 1 if with_target else 0)) // 4
+
+
+def shell_spectrum(x, y=None, out=None, ws=None):
+    """x [, y]: f32 device tensors seen as (B, T, H, W) frames through any four non-negative strides (permuted and sub-sampled views
+    are read where they lie), 8 <= H, W <= 512 -> shell-binned energy spectra (B, T, 1, K), or (B, T, 3, K) = [E_x, E_y, E_{x - y}] with
+    y (uno_shell_spectrum, K24: two launches, fixed summation order).  out: a dense f32 tensor of that shape to write; ws: f32 scratch
+    of at least shell_spectrum_ws_floats() elements.  Forward only; launches on the current stream and allocates through torch, so it
+    can be captured into a hipGraph."""
+    _require(x, torch.float32, "x", dense=False)
+    if x.dim() != 4:
+        raise RuntimeError(f"uno_amd: the shell spectrum takes (B, T, H, W) views (got {tuple(x.shape)})")
+    if y is not None:
+        _require(y, torch.float32, "y", dense=False)
+        if y.shape != x.shape or y.device != x.device:
+            raise RuntimeError(f"uno_amd: x {tuple(x.shape)} on {x.device} and y {tuple(y.shape)} on {y.device} differ")
+    B, T, H, W = x.shape
+    if not (SHELL_SPECTRUM_MIN <= H <= SHELL_SPECTRUM_MAX and SHELL_SPECTRUM_MIN <= W <= SHELL_SPECTRUM_MAX) or T < 1:
+        raise RuntimeError(f"uno_amd: the shell spectrum takes T >= 1 frames of {SHELL_SPECTRUM_MIN} ... {SHELL_SPECTRUM_MAX} points per axis "
+                           f"(got {tuple(x.shape)})")
+    for name, t in (("x", x), ("y", y)):
+        if t is not None and min(t.stride()) < 0:
+            raise RuntimeError(f"uno_amd: {name} has a negative stride {t.stride()}")
+    K = (math.isqrt(4 * ((H // 2) ** 2 + (W // 2) ** 2)) + 1) // 2 + 1          # round(hypot(H // 2, W // 2)) + 1, in integers
+    nspec = 1 if y is None else 3
+    L = lib()
+    need = shell_spectrum_ws_floats(B, T, H, W, y is not None)
+    with _on_device(x.device):
+        if out is None:
+            out = torch.empty((B, T, nspec, K), dtype=torch.float32, device=x.device)
+        else:
+            _require(out, torch.float32, "out")
+            if out.shape != (B, T, nspec, K) or out.device != x.device:
+                raise RuntimeError(f"uno_amd: out {tuple(out.shape)} on {out.device} is not ({B}, {T}, {nspec}, {K}) on {x.device}")
+        if ws is None:
+            ws = torch.empty((max(1, need),), dtype=torch.float32, device=x.device)
+        else:
+            _require(ws, torch.float32, "ws")
+            if ws.numel() < need or ws.device != x.device:
+                raise RuntimeError(f"uno_amd: ws holds {ws.numel()} floats on {ws.device}, the call needs {need} on {x.device}")
+        ys = (0, 0, 0, 0) if y is None else y.stride()
+        rc = L.uno_shell_spectrum(_ptr(x), *x.stride(), _opt(y), *ys, _ptr(out), _ptr(ws), B, T, H, W, _raw_stream(x))
+    _check(rc, "uno_shell_spectrum")
+    return out
 
 
 def rollout_ws(B, P, T, device):

@@ -581,6 +581,32 @@ int uno_rel_l2_backward(const float* x, long long x_row, long long x_elem, const
     return launch_rel_l2_backward(x, x_row, x_elem, y, y_row, y_elem, sums, g, g_per_row, scale, gx, B, N, (hipStream_t)stream);
 }
 
+// K24: shell-binned energy spectra of strided float32 frames (forward only)
+static bool shell_spectrum_sizes(int B, int T, int H, int W) { return B >= 0 && T >= 1 && H >= 8 && H <= 512 && W >= 8 && W <= 512; }
+
+long long uno_shell_spectrum_ws_bytes(int B, int T, int H, int W, int with_target) {
+    if (!shell_spectrum_sizes(B, T, H, W) || B < 1) return 0;
+    return 4LL * shell_spectrum_ws_floats(B, T, H, W, with_target);
+}
+
+int uno_shell_spectrum(const float* x, long long x_batch, long long x_frame, long long x_row, long long x_elem, const float* y, long long y_batch,
+                       long long y_frame, long long y_row, long long y_elem, float* spec, void* ws, int B, int T, int H, int W, void* stream) {
+    if (!shell_spectrum_sizes(B, T, H, W)) {
+        set_error("uno_shell_spectrum: bad sizes B=%d T=%d H=%d W=%d (B >= 0, T >= 1, 8 <= H, W <= 512)", B, T, H, W);
+        return -1;
+    }
+    const long long xs[4] = {x_batch, x_frame, x_row, x_elem}, ys[4] = {y_batch, y_frame, y_row, y_elem};
+    for (int i = 0; i < 4; ++i)
+        if (xs[i] < 0 || (y && ys[i] < 0)) {
+            set_error("uno_shell_spectrum: bad strides x (%lld, %lld, %lld, %lld) y (%lld, %lld, %lld, %lld): none may be negative", xs[0], xs[1],
+                      xs[2], xs[3], ys[0], ys[1], ys[2], ys[3]);
+            return -1;
+        }
+    if (B == 0) return 0;
+    if (!x || !spec || !ws) { set_error("uno_shell_spectrum: null pointer"); return -1; }
+    return launch_shell_spectrum(x, xs, y, ys, spec, (float*)ws, B, T, H, W, (hipStream_t)stream);
+}
+
 // K18: one step of the NS-2D evaluation roll-out (forward only), dense float32; the finish launch is K17's
 static bool rollout_sizes(const char* who, int B, long long P, int T) {
     if (B < 0 || P < 1 || T < 1) { set_error("%s: bad sizes B=%d P=%lld T=%d", who, B, P, T); return false; }

@@ -479,5 +479,13 @@ int launch_rel_l2_forward(const float* x, long long xrs, long long xes, const fl
                           float* total, float* ws, int B, long long N, hipStream_t s);
 int launch_rel_l2_backward(const float* x, long long xrs, long long xes, const float* y, long long yrs, long long yes, const float* sums,
                            const float* g, int per_row, float scale, float* gx, int B, long long N, hipStream_t s);
+// shell_spectrum.hip (K24): shell-binned energy spectra of B * T real H x W frames addressed by (batch, frame, row, element) strides, 8 <= H, W <=
+// 512 (arguments validated by the caller); y: optional target - spec (B, T, 3, K) = [E_x, E_y, E_{x - y}], else (B, T, 1, K); ws:
+// shell_spectrum_ws_floats() floats
+int shell_spectrum_shells(int H, int W);       // K = round(hypot(H / 2, W / 2)) + 1
+int shell_spectrum_bands(int W);               // column bands per frame: a function of W alone
+long long shell_spectrum_ws_floats(int B, int T, int H, int W, int with_target);
+int launch_shell_spectrum(const float* x, const long long xs[4], const float* y, const long long ys[4], float* spec, float* ws, int B, int T,
+                          int H, int W, hipStream_t s);
 
 }  // namespace uno

@@ -11,6 +11,7 @@ from .mixed import MixedDarcyTrainer  # noqa: F401
 from .train import DarcyTrainer, GraphedRollout, GraphedStep, ns2d_evaluate, ns2d_rollout_errors, ns2d_rollout_loss, ns3d_evaluate, ns3d_loss, ns3d_step_error, synthetic_darcy_batch  # noqa: F401
 from .datagen import GaussianRF, generate_ns_dataset, navier_stokes_2d  # noqa: F401
 from .darcy_datagen import darcy_grf, generate_darcy_dataset, solve_gwf, spline_matrix, threshold  # noqa: F401
+from .spectra import SpectralErrors, energy_spectrum, n_shells, shell_index, spectral_errors  # noqa: F401
 from . import workloads  # noqa: F401,E402
 
 _FIT = ("EpochRecord", "FitRecord", "fit_darcy", "fit_ns2d", "fit_ns3d")

@@ -3,7 +3,7 @@ resolution the model's modes fit and for any horizon, with a command line around
 
     python -m uno_amd.harness.predict {darcy,ns2d,ns3d} --weights W.pt [--record W.pt.json | --model ... --in-width ... --width ...]
            --data FILE [--split test|val|train|all] [--sub r | --size S] [--t-in n] [--horizon H | --calls k] [--batch-size b] [--graph]
-           [--out PRED.mat] [--no-pred]
+           [--out PRED.mat] [--no-pred] [--spectra]
 
   load_model        builds the class a checkpoint record names (harness.fit writes one beside the weights) or the caller names - weights
                     the reference's own scripts saved have no record - loads the state_dict strictly and leaves the model in eval mode;
@@ -16,7 +16,9 @@ resolution the model's modes fit and for any horizon, with a command line around
                     per-sample relative L2 errors, taken from what the native loss kernels write per row (K20 `ratio`, K17 / K18
                     `rel`); ONE read-back per call.  ns2d is the free-running roll-out: the channels-first window moves in place and
                     the frames are recorded time-major, one K18 launch per step, with or without ground truth and past T_f.  ns3d(calls=k)
-                    chains k calls: a call's last T_in output frames are the next call's input.
+                    chains k calls: a call's last T_in output frames are the next call's input.  spectra=True adds the shell-binned
+                    energy spectra (harness.spectra, K24) of every predicted frame and, where there are targets, of the true frames and
+                    of the difference, computed per batch on the device into the same flat buffer as the predictions.
 
 The runners import nothing from the oracle; `block_cls` lets a caller build a model on other blocks (the CPU tests do)."""
 from __future__ import annotations
@@ -34,6 +36,7 @@ from ..spectral3d import _resample3d_pruned_applies, resample3d_any_applies, res
 from . import models
 from .data import DeviceDataset, load_darcy, load_ns
 from .losses import NATIVE_STEP_ERRORS_MAX_T, _step_errors_stock, rel_l2, step_errors
+from .spectra import _spectra, n_shells
 
 MODEL_CLASSES = ("UNO_9", "UNO", "UNO_P", "UNO_S256", "Uno3D_T20", "Uno3D_T10", "Uno3D_T9", "Uno3D_T40", "Uno3D_T20_256", "Uno3D_T10_256")
 _CTOR_KEYS = ("in_width", "width", "pad", "factor", "pad_both")
@@ -223,6 +226,9 @@ class Prediction(NamedTuple):
     err: Optional[torch.Tensor] = None          # darcy: (n,)
     err_step: Optional[torch.Tensor] = None     # ns2d / ns3d: (n, T) per time step of the T frames that have a target
     err_full: Optional[torch.Tensor] = None     # ns2d / ns3d: (n,) over those T frames as one trajectory
+    spec_pred: Optional[torch.Tensor] = None    # spectra=True: E(k) of every predicted frame, darcy (n, K); ns2d / ns3d (n, frames, K)
+    spec_true: Optional[torch.Tensor] = None    # ... of the target frames, darcy (n, K); ns2d / ns3d (n, T, K)
+    spec_err: Optional[torch.Tensor] = None     # ... of prediction - target on those frames
 
 
 class _Replay:
@@ -254,10 +260,24 @@ def _ns2d_native_applies(model, xx, yy):
             and xx.shape[0] > 0 and xx[0].numel() > 0 and (yy is None or (yy.is_cuda and yy.dtype == torch.float32)))
 
 
-def _ns2d_native(model, xx, yy, H):
+def _frame_spectra(pred, target):
+    """pred (B, F, H, W), target (B, T, H, W) with T <= F or None, views of any strides -> (B, (F + 2 T) K): per sample the spectra of
+    the F predicted frames, then of the T target frames, then of the difference on those T frames (K24 where it applies: the measured
+    frames in one call with the target, the frames past it in one without)"""
+    B, F = pred.shape[:2]
+    T = 0 if target is None else target.shape[1]
+    if not T:
+        return _spectra(pred, None, None, "Predictor").reshape(B, -1)
+    e = _spectra(pred[:, :T], target, None, "Predictor")
+    sp = e[:, :, 0] if F == T else torch.cat((e[:, :, 0], _spectra(pred[:, T:], None, None, "Predictor")[:, :, 0]), dim=1)
+    return torch.cat((sp.reshape(B, -1), e[:, :, 1].reshape(B, -1), e[:, :, 2].reshape(B, -1)), dim=1)
+
+
+def _ns2d_native(model, xx, yy, H, spectra=False):
     """The free-running roll-out of one batch (call under no_grad): xx (B, S, S, T_in), yy (B, S, S, T) with T <= min(H, 256) or None ->
     (pred (B, H, S, S) time-major, rel (B, T + 1) or None).  ns2d_rollout_errors' native form, which stops at the ground truth's end:
-    here the steps that have a target take K18 with it, the others K18 without (no sums); every step but the last moves the window."""
+    here the steps that have a target take K18 with it, the others K18 without (no sums); every step but the last moves the window.
+    spectra=True: a third result, _frame_spectra of the time-major pred and target as they lie."""
     from .. import _native
     B, S1, S2, T_in = xx.shape
     P = S1 * S2
@@ -279,11 +299,11 @@ def _ns2d_native(model, xx, yy, H):
         else:
             _native.rollout_advance(z, im, None, pred, None, T_in, t, t + 1 < H)
     if not T:
-        return pred, None
+        return (pred, None, _frame_spectra(pred, None)) if spectra else (pred, None)
     if measured is not pred:
         pred[:, :T].copy_(measured)
     _, rel, _ = _native.rollout_finish(ws, B, P, T)
-    return pred, rel
+    return (pred, rel, _frame_spectra(pred, target)) if spectra else (pred, rel)
 
 
 def _ns2d_stock(model, xx, yy, H):
@@ -333,14 +353,16 @@ class Predictor:
             raise ValueError("Predictor: no sample to predict")
         return x, y
 
-    def _run(self, kind, x, y, per_pred, per_err, batch_fn, extra=()):
-        """batch_fn(xb, yb) -> (prediction (B, *per_pred), errors (B, per_err) or None) per batch into ONE flat device buffer
-        [predictions | errors]; -> its host copy as (pred (n, *per_pred), err (n, per_err) or None)"""
+    def _run(self, kind, x, y, per_pred, per_err, batch_fn, extra=(), per_spec=0):
+        """batch_fn(xb, yb) -> (prediction (B, *per_pred), errors (B, per_err) or None[, spectra (B, per_spec)]) per batch into ONE flat
+        device buffer [predictions | errors | spectra]; -> its host copy as (pred (n, *per_pred), err (n, per_err) or None, spectra
+        (n, per_spec) or None)"""
         n, dev = x.shape[0], self.device
         np_ = math.prod(per_pred)
-        flat = torch.empty((n * (np_ + per_err),), dtype=torch.float32, device=dev)
+        flat = torch.empty((n * (np_ + per_err + per_spec),), dtype=torch.float32, device=dev)
         pred = flat[:n * np_].view(n, *per_pred)
-        err = flat[n * np_:].view(n, per_err) if per_err else None
+        err = flat[n * np_:n * (np_ + per_err)].view(n, per_err) if per_err else None
+        spec = flat[n * (np_ + per_err):].view(n, per_spec) if per_spec else None
         was_training = self.model.training
         self.model.eval()
         try:
@@ -350,24 +372,40 @@ class Predictor:
                     xb = x[lo:hi].to(dev, dtype=torch.float32, non_blocking=True)
                     yb = None if y is None else y[lo:hi].to(dev, dtype=torch.float32, non_blocking=True)
                     if self.graph and hi - lo == self.batch_size:
-                        key = (kind, tuple(xb.shape), None if yb is None else tuple(yb.shape), *extra)
+                        key = (kind, tuple(xb.shape), None if yb is None else tuple(yb.shape), *extra, *(("spectra",) if per_spec else ()))
                         ins = (xb,) if yb is None else (xb, yb)
                         if key not in self._replays:
                             self._replays[key] = _Replay((lambda a, b=None: batch_fn(a, b)), ins)
-                        p, e = self._replays[key].run(*ins)
+                        res = self._replays[key].run(*ins)
                     else:
-                        p, e = batch_fn(xb, yb)
-                    pred[lo:hi].copy_(p.reshape(hi - lo, *per_pred))
+                        res = batch_fn(xb, yb)
+                    pred[lo:hi].copy_(res[0].reshape(hi - lo, *per_pred))
                     if err is not None:
-                        err[lo:hi].copy_(e.reshape(hi - lo, per_err))
+                        err[lo:hi].copy_(res[1].reshape(hi - lo, per_err))
+                    if spec is not None:
+                        spec[lo:hi].copy_(res[2].reshape(hi - lo, per_spec))
         finally:
             self.model.train(was_training)
         host = flat.cpu()                                       # the call's one read-back
-        return host[:n * np_].view(n, *per_pred), (host[n * np_:].view(n, per_err) if per_err else None)
+        return (host[:n * np_].view(n, *per_pred), (host[n * np_:n * (np_ + per_err)].view(n, per_err) if per_err else None),
+                (host[n * (np_ + per_err):].view(n, per_spec) if per_spec else None))
+
+    @staticmethod
+    def _spec_fields(spec, F, T, K):
+        """the three spectra fields of a Prediction from _frame_spectra's rows: F predicted frames, T of them measured"""
+        if spec is None:
+            return {}
+        n = spec.shape[0]
+        out = {"spec_pred": spec[:, :F * K].view(n, F, K)}
+        if T:
+            out["spec_true"] = spec[:, F * K:(F + T) * K].view(n, T, K)
+            out["spec_err"] = spec[:, (F + T) * K:].view(n, T, K)
+        return out
 
     # ---- the three loops
-    def darcy(self, x, y=None) -> Prediction:
-        """x (n, s, s, 1) [, y (n, s, s)] -> pred (n, s, s), err (n,): the error is K20's `ratio` on device tensors"""
+    def darcy(self, x, y=None, spectra=False) -> Prediction:
+        """x (n, s, s, 1) [, y (n, s, s)] -> pred (n, s, s), err (n,): the error is K20's `ratio` on device tensors.  spectra=True:
+        spec_pred (n, K) and, with y, spec_true and spec_err"""
         x, y = self._inputs(x, y)
         if x.dim() != 4 or x.shape[-1] != 1:
             raise ValueError(f"Predictor.darcy: x {tuple(x.shape)} is not (n, s, s, 1)")
@@ -377,16 +415,23 @@ class Predictor:
         def batch(xb, yb):
             B = xb.shape[0]
             out = self.model(xb).reshape(B, s1, s2)
-            return out, (None if yb is None else rel_l2(out.reshape(B, -1), yb.reshape(B, -1)))
+            err = None if yb is None else rel_l2(out.reshape(B, -1), yb.reshape(B, -1))
+            if not spectra:
+                return out, err
+            return out, err, _frame_spectra(out.unsqueeze(1), None if yb is None else yb.reshape(B, 1, s1, s2))
 
-        pred, err = self._run("darcy", x, y, (s1, s2), 0 if y is None else 1, batch)
-        return Prediction(pred, err=None if err is None else err[:, 0])
+        K = n_shells(s1, s2)
+        pred, err, spec = self._run("darcy", x, y, (s1, s2), 0 if y is None else 1, batch,
+                                    per_spec=(K * (1 if y is None else 3)) if spectra else 0)
+        fields = {k: v[:, 0] for k, v in self._spec_fields(spec, 1, 0 if y is None else 1, K).items()}
+        return Prediction(pred, err=None if err is None else err[:, 0], **fields)
 
-    def ns2d(self, xx, horizon=None, yy=None) -> Prediction:
+    def ns2d(self, xx, horizon=None, yy=None, spectra=False) -> Prediction:
         """The free-running roll-out: xx (n, S, S, T_in) -> pred (n, S, S, horizon), any horizon >= 1 (default: yy's length).  yy
         (n, S, S, T): the first min(T, horizon) predicted frames are measured against it - err_step (n, T), err_full (n,) from K18's
         `rel` - and the roll-out goes on past them.  float32 on a device model with forward_cf takes the native form (one K18 launch per
-        step, at most 256 measured steps); CPU models, models without forward_cf or with more than one output frame the stock loop."""
+        step, at most 256 measured steps); CPU models, models without forward_cf or with more than one output frame the stock loop.
+        spectra=True: spec_pred (n, horizon, K) and, with yy, spec_true and spec_err (n, T, K)."""
         xx, yy = self._inputs(xx, yy)
         if xx.dim() != 4:
             raise ValueError(f"Predictor.ns2d: xx {tuple(xx.shape)} is not (n, S, S, T_in)")
@@ -409,18 +454,23 @@ class Predictor:
 
         def batch(xb, yb):
             if native and _ns2d_native_applies(self.model, xb, yb):
-                return _ns2d_native(self.model, xb, yb if T else None, H)
+                return _ns2d_native(self.model, xb, yb if T else None, H, spectra)
             p, rel = _ns2d_stock(self.model, xb, yb if T else None, H)
-            return p[..., :H].permute(0, 3, 1, 2), rel
+            p = p[..., :H].permute(0, 3, 1, 2)
+            return (p, rel, _frame_spectra(p, yb.permute(0, 3, 1, 2) if T else None)) if spectra else (p, rel)
 
-        pred, rel = self._run("ns2d", xx, yy if T else None, (H, S1, S2), T + 1 if T else 0, batch, extra=(H,))
+        K = n_shells(S1, S2)
+        pred, rel, spec = self._run("ns2d", xx, yy if T else None, (H, S1, S2), T + 1 if T else 0, batch, extra=(H,),
+                                    per_spec=(H + 2 * T) * K if spectra else 0)
         pred = pred.permute(0, 2, 3, 1)                         # the reference's layout, a view of the time-major frames
-        return Prediction(pred) if rel is None else Prediction(pred, err_step=rel[:, :T], err_full=rel[:, T])
+        fields = self._spec_fields(spec, H, T, K)
+        return Prediction(pred, **fields) if rel is None else Prediction(pred, err_step=rel[:, :T], err_full=rel[:, T], **fields)
 
-    def ns3d(self, x, calls=1, y=None) -> Prediction:
+    def ns3d(self, x, calls=1, y=None, spectra=False) -> Prediction:
         """x (n, S, S, T_in[, 1]) -> pred (n, S, S, calls * T_out).  calls > 1 chains the model: a call's last T_in output frames are
         the next call's input (plain slices).  y (n, S, S, T) with T <= calls * T_out: the first T frames are measured - err_step
-        (n, T), err_full (n,), K17's `rel` on device tensors."""
+        (n, T), err_full (n,), K17's `rel` on device tensors.  spectra=True: spec_pred (n, calls * T_out, K) and, with y, spec_true and
+        spec_err (n, T, K), from the (B, S, S, frames) tensors as they lie."""
         x, y = self._inputs(x, y)
         if x.dim() == 4:
             x = x.reshape(*x.shape, 1)
@@ -447,26 +497,34 @@ class Predictor:
                 xb = out[..., T_out - T_in:].reshape(B, S1, S2, T_in, 1)
             out = outs[0] if calls == 1 else torch.cat(outs, dim=-1)
             if yb is None:
-                return out, None
-            e = step_errors(out if T == total else out[..., :T], yb.reshape(B, S1, S2, T))
-            return out, torch.cat((e.per_step, e.full.reshape(-1, 1)), dim=1)
+                return (out, None, _frame_spectra(out.permute(0, 3, 1, 2), None)) if spectra else (out, None)
+            yb = yb.reshape(B, S1, S2, T)
+            e = step_errors(out if T == total else out[..., :T], yb)
+            rel = torch.cat((e.per_step, e.full.reshape(-1, 1)), dim=1)
+            return (out, rel, _frame_spectra(out.permute(0, 3, 1, 2), yb.permute(0, 3, 1, 2))) if spectra else (out, rel)
 
-        pred, rel = self._run("ns3d", x, y, (S1, S2, total), T + 1 if T else 0, batch, extra=(calls,))
-        return Prediction(pred) if rel is None else Prediction(pred, err_step=rel[:, :T], err_full=rel[:, T])
+        K = n_shells(S1, S2)
+        pred, rel, spec = self._run("ns3d", x, y, (S1, S2, total), T + 1 if T else 0, batch, extra=(calls,),
+                                    per_spec=(total + 2 * T) * K if spectra else 0)
+        fields = self._spec_fields(spec, total, T, K)
+        return Prediction(pred, **fields) if rel is None else Prediction(pred, err_step=rel[:, :T], err_full=rel[:, T], **fields)
 
 
 # ---------------------------------------------------------------------------------------------------------------------- command line
 def write_mat(path, result: Prediction, index, with_pred=True):
-    """`pred` (unless with_pred is False), `err` or `err_step` / `err_full`, and `index` (the samples' places in the file's order) as a
-    MATLAB v5 file: harness.data.MatReader reads it back"""
+    """`pred` (unless with_pred is False), `err` or `err_step` / `err_full`, the spectra a spectra=True call added (`spec_pred`, `spec_true`,
+    `spec_err` and their wavenumbers `k`) and `index` (the samples' places in the file's order) as a MATLAB v5 file:
+    harness.data.MatReader reads it back"""
     import scipy.io
     fields = {"index": torch.as_tensor(index).to(torch.int64).numpy()}
     if with_pred:
         fields["pred"] = result.pred.contiguous().numpy()
-    for key in ("err", "err_step", "err_full"):
+    for key in ("err", "err_step", "err_full", "spec_pred", "spec_true", "spec_err"):
         v = getattr(result, key)
         if v is not None:
             fields[key] = v.contiguous().numpy()
+    if result.spec_pred is not None:
+        fields["k"] = torch.arange(result.spec_pred.shape[-1], dtype=torch.int64).numpy()
     scipy.io.savemat(path, fields)
 
 
@@ -499,6 +557,7 @@ def _parser():
     ap.add_argument("--graph", action="store_true", help="replay full-size batches from a HIP graph")
     ap.add_argument("--out", default=None, help="a .mat file for pred, err (err_step, err_full) and index")
     ap.add_argument("--no-pred", action="store_true", help="leave the predictions out of --out")
+    ap.add_argument("--spectra", action="store_true", help="also the shell-binned energy spectra: spec_pred, spec_true, spec_err and k in --out")
     ap.add_argument("--device", default=None)
     return ap
 
@@ -576,13 +635,13 @@ def main(argv=None) -> dict:
     predictor = Predictor(model, batch_size=a.batch_size, graph=a.graph)
     try:
         if a.loop == "darcy":
-            result = predictor.darcy(x, y)
+            result = predictor.darcy(x, y, spectra=a.spectra)
         elif a.loop == "ns2d":
-            result = predictor.ns2d(x, frames, y if y.shape[-1] else None)
+            result = predictor.ns2d(x, frames, y if y.shape[-1] else None, spectra=a.spectra)
         else:
             T_out = _layers(model, int(x.shape[2]), t_in)[1] * a.calls
             y = y[..., :T_out]
-            result = predictor.ns3d(x, a.calls, y if y.shape[-1] else None)
+            result = predictor.ns3d(x, a.calls, y if y.shape[-1] else None, spectra=a.spectra)
     except ValueError as e:
         raise SystemExit(str(e))
     summary = {"loop": a.loop, "model": type(model).__name__, "split": a.split, "n": int(index.numel()), **where}
@@ -593,6 +652,8 @@ def main(argv=None) -> dict:
     if result.err_step is not None:
         summary["measured_frames"] = int(result.err_step.shape[1])
         summary["err_step"], summary["err_full"] = float(result.err_step.double().mean()), float(result.err_full.double().mean())
+    if result.spec_pred is not None:
+        summary["spectra"] = int(result.spec_pred.shape[-1])
     if a.out is not None:
         write_mat(a.out, result, index, with_pred=not a.no_pred)
         summary["out"] = a.out
