@@ -467,6 +467,35 @@ int uno_shell_spectrum(const float* x, long long x_batch, long long x_frame, lon
                        long long y_batch, long long y_frame, long long y_row, long long y_elem, float* spec, void* ws, int B, int T, int H,
                        int W, void* stream);
 
+/* The relative Sobolev (H^s) loss of real frames and its gradient (K25, sobolev_loss.hip; additive: the ABI version stays 14).  With
+ * X = fft2(x) / (H W), integer wavenumbers in fftfreq order and a weight table w2 (H / 2 + 1, W / 2 + 1), float32 on the device, read at
+ * (|ky|, |kx|):
+ *   sums (B, T, 2) = [ sum_k w2 |X - Y|^2, sum_k w2 |Y|^2 ] over both Hermitian halves, per frame;
+ *   per_frame = 1: ratio (B, T) = sqrt(num) / sqrt(den);  per_frame = 0: ratio (B) from the sums over a sample's frames;
+ *   total (1) = sum of ratio.
+ * x, y: float32 frames addressed as uno_shell_spectrum's, four element strides >= 0 each; nothing is copied.  z: NULL, or a buffer of
+ * B * T * H * (W / 2 + 1) complex64 that receives Z = w2 (X - Y) per frame for the backward call; with NULL no spectrum leaves the
+ * compute unit.  Two launches: one workgroup per (frame, band of 16 half-spectrum columns), both DFT axes dense sums on the f32 MFMA,
+ * herm(kx) w2 |.|^2 reduced per band in a fixed order, then one workgroup adds the bands in ascending order and forms ratio and total.
+ * uno_sobolev_backward: gx[b][t] = g * scale * f / (H W sqrt(num den)), f = the unnormalised inverse real 2-D DFT of Z (one launch: one
+ * workgroup per (frame, band of 16 output columns), Z from memory, the half-transformed band in LDS), 0 where num == 0; num, den: the
+ * frame's sums (per_frame = 1) or the sample's; g: float32 on the device, never read by the host - one value (g_per_row = 0) or one per
+ * row of the grouping; gx is written through its own four element strides >= 0 (a (B, S, S, T) gradient where it lies).  No gradient
+ * for y.  No clamping: a zero target gives inf / NaN as the stock form does.
+ * No atomics; the decomposition is a function of (H, W) only, every sum has a fixed order and a frame's arithmetic does not depend on its
+ * batch: two calls, a call under uno_reserve_cus and a graph replay give the same bits.  No synchronisation, allocation or read-back;
+ * twiddle tables are uploaded as uno_upload_table does (safe under graph capture).  float32 only; 8 <= H, W <= 512 (odd sizes included,
+ * both kernels hold 512 points a side in LDS), T >= 1, B >= 0, 64-bit offsets; B == 0 returns 0 without touching the device.  ws:
+ * scratch of uno_sobolev_ws_bytes() bytes (0 for bad sizes), 8-byte aligned, need not be initialised.  Errors (-1, before any launch):
+ * a null pointer (z excepted), sizes out of range, a negative stride, per_frame / g_per_row not 0 or 1. */
+long long uno_sobolev_ws_bytes(int B, int T, int H, int W);
+int uno_sobolev_forward(const float* x, long long x_batch, long long x_frame, long long x_row, long long x_elem, const float* y,
+                        long long y_batch, long long y_frame, long long y_row, long long y_elem, const float* w2, float* sums, float* ratio,
+                        float* total, void* z, void* ws, int B, int T, int H, int W, int per_frame, void* stream);
+int uno_sobolev_backward(const void* z, const float* sums, const float* g, int g_per_row, float scale, int per_frame, float* gx,
+                         long long gx_batch, long long gx_frame, long long gx_row, long long gx_elem, int B, int T, int H, int W,
+                         void* stream);
+
 /* One step of the NS-2D evaluation roll-out in one launch (additive: the ABI version stays 14).  The reference's validation and test
  * loops (ns_train_2d.py:94-107, 141-157) run the model T_f times under no_grad, feed each prediction back into the input window and
  * report the sum of the per-step relative L2 errors and the error of the whole trajectory; between two forward passes they spend a

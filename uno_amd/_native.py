@@ -108,6 +108,9 @@ _SIGNATURES = {
     "uno_rel_l2_backward": (C.c_int, [_fp, C.c_longlong, C.c_longlong] * 2 + [_fp, _fp, _i, C.c_float, _fp, _i, C.c_longlong, _fp]),
     "uno_shell_spectrum_ws_bytes": (C.c_longlong, [_i] * 5),
     "uno_shell_spectrum": (C.c_int, [_fp] + [C.c_longlong] * 4 + [_fp] + [C.c_longlong] * 4 + [_fp, _fp, _i, _i, _i, _i, _fp]),
+    "uno_sobolev_ws_bytes": (C.c_longlong, [_i] * 4),
+    "uno_sobolev_forward": (C.c_int, [_fp] + [C.c_longlong] * 4 + [_fp] + [C.c_longlong] * 4 + [_fp] * 6 + [_i] * 5 + [_fp]),
+    "uno_sobolev_backward": (C.c_int, [_fp, _fp, _fp, _i, C.c_float, _i, _fp] + [C.c_longlong] * 4 + [_i] * 4 + [_fp]),
     "uno_rollout_ws_bytes": (C.c_longlong, [_i, C.c_longlong, _i]),
     "uno_rollout_advance": (C.c_int, [_fp] * 5 + [_i, _i, _i, C.c_longlong, _i, _i, _i, _fp]),
     "uno_rollout_finish": (C.c_int, [_fp] * 4 + [_i, C.c_longlong, _i, _fp]),
@@ -1545,6 +1548,85 @@ def shell_spectrum(x, y=None, out=None, ws=None):
         rc = L.uno_shell_spectrum(_ptr(x), *x.stride(), _opt(y), *ys, _ptr(out), _ptr(ws), B, T, H, W, _raw_stream(x))
     _check(rc, "uno_shell_spectrum")
     return out
+
+
+SOBOLEV_MIN, SOBOLEV_MAX = 8, 512
+
+
+def sobolev_ws_floats(B, T, H, W) -> int:
+    """floats of scratch one sobolev_forward call of these sizes needs (uno_sobolev_ws_bytes; 0 for sizes out of range)"""
+    return int(lib().uno_sobolev_ws_bytes(int(B), int(T), int(H), int(W))) // 4
+
+
+def sobolev_views(record, B, T, per_frame):
+    """-> sums (B, T, 2), ratio (B,) or (B, T), total (1,): views of a sobolev_forward record"""
+    n, r = B * T, (B * T if per_frame else B)
+    return record[:2 * n].view(B, T, 2), (record[2 * n:2 * n + r].view(B, T) if per_frame else record[2 * n:2 * n + r]), \
+        record[2 * n + r:2 * n + r + 1]
+
+
+def _sobolev_frames(t, name):
+    _require(t, torch.float32, name, dense=False)
+    if t.dim() != 4:
+        raise RuntimeError(f"uno_amd: the Sobolev loss takes (B, T, H, W) views (got {name} {tuple(t.shape)})")
+    if min(t.stride()) < 0:
+        raise RuntimeError(f"uno_amd: {name} has a negative stride {t.stride()}")
+
+
+def sobolev_forward(x, y, w2, per_frame=False, want_z=False):
+    """x, y: f32 device tensors seen as (B, T, H, W) frames through any four non-negative strides, 8 <= H, W <= 512; w2: the f32 device
+    weight table (H // 2 + 1, W // 2 + 1) -> (record, z): ONE flat f32 record [sums (B, T, 2) | ratio | total (1) | workspace]
+    (sobolev_views) and, with want_z, the weighted difference spectrum (B, T, H, W // 2 + 1, 2) the backward call reads - else None
+    (uno_sobolev_forward, K25: two launches, fixed summation order).  Launches on the current stream and allocates through torch, so it
+    can be captured into a hipGraph."""
+    _sobolev_frames(x, "x")
+    _sobolev_frames(y, "y")
+    _require(w2, torch.float32, "w2")
+    B, T, H, W = x.shape
+    if y.shape != x.shape or y.device != x.device or w2.device != x.device:
+        raise RuntimeError(f"uno_amd: x {tuple(x.shape)} on {x.device}, y {tuple(y.shape)} on {y.device} and w2 on {w2.device} differ")
+    if not (SOBOLEV_MIN <= H <= SOBOLEV_MAX and SOBOLEV_MIN <= W <= SOBOLEV_MAX) or T < 1:
+        raise RuntimeError(f"uno_amd: the Sobolev loss takes T >= 1 frames of {SOBOLEV_MIN} ... {SOBOLEV_MAX} points per axis "
+                           f"(got {tuple(x.shape)})")
+    if w2.shape != (H // 2 + 1, W // 2 + 1):
+        raise RuntimeError(f"uno_amd: w2 {tuple(w2.shape)} is not the ({H // 2 + 1}, {W // 2 + 1}) table of {H} x {W} frames")
+    L = lib()
+    rows = B * T if per_frame else B
+    head = (2 * B * T + rows + 1 + 1) // 2 * 2          # the workspace holds float2: an even offset
+    with _on_device(x.device):
+        record = torch.empty((head + sobolev_ws_floats(B, T, H, W),), dtype=torch.float32, device=x.device)
+        z = torch.empty((B, T, H, W // 2 + 1, 2), dtype=torch.float32, device=x.device) if want_z else None
+        if B == 0:
+            record.zero_()
+        base = record.data_ptr()
+        rc = L.uno_sobolev_forward(_ptr(x), *x.stride(), _ptr(y), *y.stride(), _ptr(w2), base, base + 8 * B * T, base + 8 * B * T + 4 * rows,
+                                   _opt(z), base + 4 * head, B, T, H, W, 1 if per_frame else 0, _raw_stream(x))
+    _check(rc, "uno_sobolev_forward")
+    return record, z
+
+
+def sobolev_backward(z, sums, g, like, per_frame=False, scale=1.0):
+    """The gradient of sobolev_forward's ratio (or total) at x: g * scale * irfft2-of-z / (H W sqrt(num den)) per row of the grouping, zero
+    where num == 0 (uno_sobolev_backward, K25: one launch).  z: from the forward call; sums: its (B, T, 2) sums or its whole record (which
+    begins with them); g: f32 on the device, one value or one per row of the grouping, never read by the host; like: the (B, T, H, W)
+    view whose gradient this is - the result has its layout (torch.empty_like) and is written through its four strides."""
+    _require(z, torch.float32, "z")
+    _require(sums, torch.float32, "sums")
+    _require(g, torch.float32, "g")
+    B, T, H, W = like.shape
+    if z.shape != (B, T, H, W // 2 + 1, 2) or z.device != like.device or sums.device != like.device or g.device != like.device:
+        raise RuntimeError(f"uno_amd: z {tuple(z.shape)} on {z.device} is not the spectrum of {tuple(like.shape)} frames on {like.device}")
+    if sums.numel() < 2 * B * T:
+        raise RuntimeError(f"uno_amd: sums {tuple(sums.shape)} holds fewer than (B, T, 2) = ({B}, {T}, 2) values")
+    rows = B * T if per_frame else B
+    if g.numel() != 1 and g.numel() != rows:
+        raise RuntimeError(f"uno_amd: g {tuple(g.shape)} holds neither one value nor one per row ({rows})")
+    with _on_device(like.device):
+        gx = torch.empty_like(like)
+        rc = lib().uno_sobolev_backward(_ptr(z), _ptr(sums), _ptr(g), 0 if g.numel() == 1 else 1, float(scale), 1 if per_frame else 0,
+                                        _ptr(gx), *gx.stride(), B, T, H, W, _raw_stream(like))
+    _check(rc, "uno_sobolev_backward")
+    return gx
 
 
 def rollout_ws(B, P, T, device):

@@ -20,7 +20,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libuno_spectral.so")
 STAMP = os.path.join(LIBDIR, "libuno_spectral.stamp")
-SOURCES = ["capi.hip", "capi_spectral.hip", "capi_pointwise.hip", "capi_ns2d.hip", "capi_darcy.hip", "dft2d_fwd.hip", "dft2d_fwd_r4.hip", "dft2d_fwd_fd.hip", "spectrum_crop.hip", "dft2d_inv.hip", "dft2d_inv_b.hip", "dft2d_inv_c.hip", "dft2d_inv_add.hip", "dft2d_plane.hip", "dft2d_b16.hip", "mode_gemm.hip", "cdft_axis.hip", "dft3d_volume.hip", "dft_generic.hip", "resample3d_any.hip", "resample3d_wide.hip", "resample2d.hip", "channel_mix.hip", "channel_mix_rows.hip", "channel_wgrad.hip", "adam.hip", "pointwise_fused.hip", "instnorm.hip", "lift_bwd.hip", "rel_l2_steps.hip", "rel_l2_loss.hip", "shell_spectrum.hip", "rollout.hip", "rollout_train.hip", "ns2d_solver.hip", "darcy_solver.hip"]
+SOURCES = ["capi.hip", "capi_spectral.hip", "capi_pointwise.hip", "capi_ns2d.hip", "capi_darcy.hip", "dft2d_fwd.hip", "dft2d_fwd_r4.hip", "dft2d_fwd_fd.hip", "spectrum_crop.hip", "dft2d_inv.hip", "dft2d_inv_b.hip", "dft2d_inv_c.hip", "dft2d_inv_add.hip", "dft2d_plane.hip", "dft2d_b16.hip", "mode_gemm.hip", "cdft_axis.hip", "dft3d_volume.hip", "dft_generic.hip", "resample3d_any.hip", "resample3d_wide.hip", "resample2d.hip", "channel_mix.hip", "channel_mix_rows.hip", "channel_wgrad.hip", "adam.hip", "pointwise_fused.hip", "instnorm.hip", "lift_bwd.hip", "rel_l2_steps.hip", "rel_l2_loss.hip", "shell_spectrum.hip", "sobolev_loss.hip", "rollout.hip", "rollout_train.hip", "ns2d_solver.hip", "darcy_solver.hip"]
 HEADERS = ["uno_common.h", "channel_mix_common.h", "dft2d_fwd_common.h", "dft2d_fwd_kernel.h", "dft2d_fwd_ft_kernel.h", "dft2d_fwd_ht_kernel.h", "dft2d_fwd_fd_kernel.h", "dft2d_inv_common.h", "dft2d_inv_kernel.h", "dft2d_inv_add_kernel.h", "resample3d_common.h", "resample3d_planes.h", os.path.join("..", "..", "include", "uno_spectral.h")]
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]

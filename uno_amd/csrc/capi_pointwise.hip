@@ -607,6 +607,51 @@ int uno_shell_spectrum(const float* x, long long x_batch, long long x_frame, lon
     return launch_shell_spectrum(x, xs, y, ys, spec, (float*)ws, B, T, H, W, (hipStream_t)stream);
 }
 
+// K25: the relative Sobolev loss of strided float32 frames and its gradient
+static bool sobolev_sizes(const char* who, int B, int T, int H, int W) {
+    if (B >= 0 && T >= 1 && H >= 8 && H <= 512 && W >= 8 && W <= 512) return true;
+    set_error("%s: bad sizes B=%d T=%d H=%d W=%d (B >= 0, T >= 1, 8 <= H, W <= 512)", who, B, T, H, W);
+    return false;
+}
+
+long long uno_sobolev_ws_bytes(int B, int T, int H, int W) {
+    if (B < 1 || T < 1 || H < 8 || H > 512 || W < 8 || W > 512) return 0;
+    return 4LL * sobolev_ws_floats(B, T, W);
+}
+
+int uno_sobolev_forward(const float* x, long long x_batch, long long x_frame, long long x_row, long long x_elem, const float* y, long long y_batch,
+                        long long y_frame, long long y_row, long long y_elem, const float* w2, float* sums, float* ratio, float* total, void* z,
+                        void* ws, int B, int T, int H, int W, int per_frame, void* stream) {
+    if (!sobolev_sizes("uno_sobolev_forward", B, T, H, W)) return -1;
+    if (per_frame != 0 && per_frame != 1) { set_error("uno_sobolev_forward: per_frame = %d, 0 (one ratio per sample) or 1 (one per frame)", per_frame); return -1; }
+    const long long xs[4] = {x_batch, x_frame, x_row, x_elem}, ys[4] = {y_batch, y_frame, y_row, y_elem};
+    for (int i = 0; i < 4; ++i)
+        if (xs[i] < 0 || ys[i] < 0) {
+            set_error("uno_sobolev_forward: bad strides x (%lld, %lld, %lld, %lld) y (%lld, %lld, %lld, %lld): none may be negative", xs[0], xs[1],
+                      xs[2], xs[3], ys[0], ys[1], ys[2], ys[3]);
+            return -1;
+        }
+    if (B == 0) return 0;
+    if (!x || !y || !w2 || !sums || !ratio || !total || !ws) { set_error("uno_sobolev_forward: null pointer"); return -1; }
+    return launch_sobolev_forward(x, xs, y, ys, w2, sums, ratio, total, (float*)z, (float*)ws, B, T, H, W, per_frame, (hipStream_t)stream);
+}
+
+int uno_sobolev_backward(const void* z, const float* sums, const float* g, int g_per_row, float scale, int per_frame, float* gx, long long gx_batch,
+                         long long gx_frame, long long gx_row, long long gx_elem, int B, int T, int H, int W, void* stream) {
+    if (!sobolev_sizes("uno_sobolev_backward", B, T, H, W)) return -1;
+    if (g_per_row != 0 && g_per_row != 1) { set_error("uno_sobolev_backward: g_per_row = %d, 0 (one scalar) or 1 (one per row)", g_per_row); return -1; }
+    if (per_frame != 0 && per_frame != 1) { set_error("uno_sobolev_backward: per_frame = %d, 0 (one ratio per sample) or 1 (one per frame)", per_frame); return -1; }
+    const long long gs[4] = {gx_batch, gx_frame, gx_row, gx_elem};
+    for (int i = 0; i < 4; ++i)
+        if (gs[i] < 0) {
+            set_error("uno_sobolev_backward: bad strides gx (%lld, %lld, %lld, %lld): none may be negative", gs[0], gs[1], gs[2], gs[3]);
+            return -1;
+        }
+    if (B == 0) return 0;
+    if (!z || !sums || !g || !gx) { set_error("uno_sobolev_backward: null pointer"); return -1; }
+    return launch_sobolev_backward((const float*)z, sums, g, g_per_row, scale, per_frame, gx, gs, B, T, H, W, (hipStream_t)stream);
+}
+
 // K18: one step of the NS-2D evaluation roll-out (forward only), dense float32; the finish launch is K17's
 static bool rollout_sizes(const char* who, int B, long long P, int T) {
     if (B < 0 || P < 1 || T < 1) { set_error("%s: bad sizes B=%d P=%lld T=%d", who, B, P, T); return false; }

@@ -487,5 +487,13 @@ int shell_spectrum_bands(int W);               // column bands per frame: a func
 long long shell_spectrum_ws_floats(int B, int T, int H, int W, int with_target);
 int launch_shell_spectrum(const float* x, const long long xs[4], const float* y, const long long ys[4], float* spec, float* ws, int B, int T,
                           int H, int W, hipStream_t s);
+// sobolev_loss.hip (K25): the relative Sobolev loss of B * T frame pairs addressed as K24's, 8 <= H, W <= 512 (arguments validated by the
+// caller); w2: device table (H / 2 + 1, W / 2 + 1); z: (B, T, H, W / 2 + 1) complex for the backward pass, or nullptr; ws:
+// sobolev_ws_floats() floats.  Backward: gx through four element strides, g one value or one per row of the grouping
+long long sobolev_ws_floats(int B, int T, int W);
+int launch_sobolev_forward(const float* x, const long long xs[4], const float* y, const long long ys[4], const float* w2, float* sums, float* ratio,
+                           float* total, float* z, float* ws, int B, int T, int H, int W, int per_frame, hipStream_t s);
+int launch_sobolev_backward(const float* z, const float* sums, const float* g, int g_per_row, float scale, int per_frame, float* gx,
+                            const long long gs[4], int B, int T, int H, int W, hipStream_t s);
 
 }  // namespace uno

@@ -17,7 +17,9 @@ Left out - host-side habits only, the arithmetic of an epoch is the reference's:
   * `gc.collect()` per batch and `torch.cuda.empty_cache()` per epoch;
   * T_f + 1 loss calls per NS-3D batch: `ns3d_loss(native=True)` takes loss and step error from one pass (K17 / K17-B).
 Device tensors take the native loss paths (K20 through LpLoss for Darcy, the native roll-out for NS-2D, step_losses for NS-3D);
-`native=False` switches each back to stock ops.  graph=True replays every full-size training batch through a GraphedStep whose
+`native=False` switches each back to stock ops.  loss=HsLoss(...) (command line: --loss h1 / h2) replaces the TRAINING objective of a
+loop by the relative Sobolev loss (losses.HsLoss, K25 on device tensors); validation and test figures stay the reference's relative
+L2, so records stay comparable.  graph=True replays every full-size training batch through a GraphedStep whose
 optimiser update is inside the graph (and NS-2D's evaluation roll-outs through a GraphedRollout); a short last batch runs eagerly.
 
 The runners take any model with the reference's call convention and import nothing from the oracle."""
@@ -32,9 +34,9 @@ from typing import List, Optional, Tuple
 import torch
 
 from .data import DeviceDataset, load_darcy, load_ns
-from .losses import LpLoss, _step_errors_stock, lp_loss_rel_sum, step_errors
+from .losses import HsLoss, LpLoss, _step_errors_stock, lp_loss_rel_sum, step_errors
 from .optim import ComplexAdam
-from .train import GraphedRollout, GraphedStep, ns2d_rollout_errors, ns2d_rollout_loss, ns3d_evaluate, ns3d_loss
+from .train import GraphedRollout, GraphedStep, ns2d_rollout_errors, ns2d_rollout_loss, ns3d_evaluate, ns3d_loss, ns3d_step_error
 
 
 @dataclass
@@ -188,9 +190,11 @@ def _evaluate(model, batches, figures):
 
 
 def fit_darcy(model, train, val, test, batch_size=None, epochs=150, lr=1e-4, scheduler_step=50, scheduler_gamma=0.5, weight_decay=1e-3,
-              weight_path=None, native=True, graph=False, generator=None, log=print) -> FitRecord:
+              weight_path=None, native=True, graph=False, generator=None, log=print, loss=None) -> FitRecord:
     """train_darcy.py:35-100.  train / val / test: a DeviceDataset (batch_size then applies, training batches shuffled) or an iterable
-    of (x (B, s, s, 1), y (B, s, s)) batches.  Figures: sums of per-sample relative L2 errors over the split's sample count."""
+    of (x (B, s, s, 1), y (B, s, s)) batches.  Figures: sums of per-sample relative L2 errors over the split's sample count.  loss: an
+    HsLoss of layout "bhw" the training batches are scored with instead (called on (B, s, s) prediction and target; the training
+    figure is then its sum over the sample count); validation and test stay relative L2."""
     device = _device_of(model)
     myloss = LpLoss(size_average=False) if native else lp_loss_rel_sum
 
@@ -198,7 +202,10 @@ def fit_darcy(model, train, val, test, batch_size=None, epochs=150, lr=1e-4, sch
         B = x.shape[0]
         return myloss(model(x).reshape(B, -1), y.reshape(B, -1))
 
-    trainer = _Trainer(model, loss_fn, lr, weight_decay, scheduler_step, scheduler_gamma, graph)
+    def train_fn(x, y):
+        return loss(model(x).reshape(y.shape), y)
+
+    trainer = _Trainer(model, loss_fn if loss is None else train_fn, lr, weight_decay, scheduler_step, scheduler_gamma, graph)
     record = FitRecord()
     best = _Best(model, weight_path, record, epochs)
     t1 = time.perf_counter()
@@ -225,15 +232,19 @@ def fit_darcy(model, train, val, test, batch_size=None, epochs=150, lr=1e-4, sch
 
 
 def fit_ns2d(model, train, val, test, T_f=10, step=1, batch_size=None, epochs=150, lr=1e-4, scheduler_step=100, scheduler_gamma=0.5,
-             weight_decay=1e-3, weight_path=None, native=True, graph=False, generator=None, log=print) -> FitRecord:
+             weight_decay=1e-3, weight_path=None, native=True, graph=False, generator=None, log=print, loss=None) -> FitRecord:
     """ns_train_2d.py:34-168.  Batches: xx (B, S, S, T_in), yy (B, S, S, T_f).  Odd epochs train only; even epochs validate, step the
     scheduler and offer their weights.  native: the cat-free training roll-out (ns2d_rollout_loss(native=True)) and the native
     evaluation roll-out; native=False: the reference's window-by-window forms.  graph=True needs the native evaluation roll-out's
-    conditions (GraphedRollout) and step == 1."""
+    conditions (GraphedRollout) and step == 1.  loss: an HsLoss of layout "bhwt" every training step's frames are scored with instead,
+through the window-by-window roll-out (the native training roll-out has its own fused relative-L2 step loss); the evaluation
+roll-outs stay as `native` says, in relative L2."""
     device = _device_of(model)
     per = T_f / step
 
     def loss_fn(xx, yy):
+        if loss is not None:
+            return ns2d_rollout_loss(model, xx, yy, T_f, step, native=False, loss=loss)
         return ns2d_rollout_loss(model, xx, yy, T_f, step, native=native)
 
     def errors(m, xx, yy):
@@ -293,16 +304,23 @@ def fit_ns2d(model, train, val, test, T_f=10, step=1, batch_size=None, epochs=15
 
 
 def fit_ns3d(model, train, val, test, T_f=10, batch_size=None, epochs=150, lr=1e-4, scheduler_step=50, scheduler_gamma=0.5,
-             weight_decay=1e-3, weight_path=None, native=True, graph=False, generator=None, log=print) -> FitRecord:
+             weight_decay=1e-3, weight_path=None, native=True, graph=False, generator=None, log=print, loss=None) -> FitRecord:
     """ns_train_3d.py:34-147.  Batches: x (B, S, S, T_in, 1), y (B, S, S, T_f).  The training figure is the per-step error of every
     batch's own forward pass; validation (per-step error) runs on even epochs only; the test pass reports the whole-trajectory and the
     per-step error.  native: loss and step error of a training batch from ONE step_losses call; native=False: lp_loss_rel_sum and the
-    slice-by-slice metric."""
+    slice-by-slice metric.  loss: an HsLoss of layout "bhwt" the training batches are scored with instead (called on the (B, S, S, T_f)
+prediction and target); the training figure stays the per-step relative L2 error of the same forward pass."""
     device = _device_of(model)
 
     def loss_fn(x, y):
-        loss, trainer.extra = ns3d_loss(model, x, y, with_step_error=True, native=native)
-        return loss
+        if loss is not None:
+            B, S = x.shape[0], x.shape[1]
+            out, yv = model(x).view(B, S, S, T_f), y.reshape(B, S, S, T_f)
+            with torch.no_grad():
+                trainer.extra = step_errors(out.detach(), yv).step_sum if native else ns3d_step_error(out.detach(), yv)
+            return loss(out, yv)
+        value, trainer.extra = ns3d_loss(model, x, y, with_step_error=True, native=native)
+        return value
 
     def figures(m, x, y):
         B, S = x.shape[0], x.shape[1]
@@ -389,7 +407,30 @@ def checkpoint_record(a, model, record) -> dict:
     data = {"sub": int(a.sub)} if a.loop == "darcy" else {"size": int(a.size), "samples": a.samples, "gen_batch": int(a.gen_batch)}
     return {"format": RECORD_FORMAT, "loop": a.loop, "model": type(model).__name__, "ctor": ctor, "t_in": int(a.t_in), "t_f": int(a.t_f), **data,
             "ntrain": int(a.ntrain), "nval": int(a.nval), "ntest": int(a.ntest), "seed": int(a.seed),
+            **_loss_record(a),
             "best_epoch": int(record.best_epoch), "best_val": float(record.best_val), "test": [float(v) for v in record.test]}
+
+
+LOSSES = {"l2": 0, "h1": 1, "h2": 2}       # --loss: the order k of the training objective (0: the loop's own relative L2)
+
+
+def _loss_record(a) -> dict:
+    """the training objective as the record holds it (harness.predict ignores it)"""
+    name = getattr(a, "loss", "l2")
+    hs_a = getattr(a, "hs_a", None)
+    return {"loss": name, **({"hs_a": [float(v) for v in hs_a]} if name != "l2" and hs_a else {})}
+
+
+def _hs_loss(a):
+    """None for --loss l2, else the HsLoss of the loop's layout, summed over the batch as the loops sum their losses"""
+    k = LOSSES[a.loss]
+    if k == 0:
+        if a.hs_a:
+            raise SystemExit("--hs-a goes with --loss h1 or h2")
+        return None
+    if a.hs_a is not None and len(a.hs_a) != k:
+        raise SystemExit(f"--loss {a.loss} takes {k} coefficient{'s' if k > 1 else ''} (--hs-a got {len(a.hs_a)})")
+    return HsLoss(k=k, a=a.hs_a, layout="bhw" if a.loop == "darcy" else "bhwt", size_average=False, native=False if a.stock_loss else None)
 
 
 def write_record(path, rec):
@@ -424,6 +465,9 @@ def main(argv=None) -> FitRecord:
     ap.add_argument("--weight-decay", type=float, default=1e-3)
     ap.add_argument("--graph", action="store_true", help="replay full-size training batches from a HIP graph")
     ap.add_argument("--stock-loss", action="store_true", help="the stock-op loss paths instead of the native ones")
+    ap.add_argument("--loss", choices=tuple(LOSSES), default="l2", help="the training objective: relative L2 (the reference's), or the relative "
+                    "Sobolev loss H^1 / H^2; validation and test figures stay relative L2")
+    ap.add_argument("--hs-a", type=float, nargs="+", default=None, metavar="A", help="--loss h1 / h2: the coefficients a_1 [a_2] (default 1)")
     ap.add_argument("--seed", type=int, default=10001, help="of the weights, the split and the batch order")
     ap.add_argument("--device", default=None)
     ap.add_argument("--out", required=True, help="where the best state_dict goes")
@@ -453,6 +497,9 @@ def main(argv=None) -> FitRecord:
     gen = torch.Generator(device=device).manual_seed(a.seed)
     common = dict(batch_size=a.batch_size, epochs=a.epochs, lr=a.lr, scheduler_gamma=a.scheduler_gamma, weight_decay=a.weight_decay,
                   weight_path=a.out, native=not a.stock_loss, graph=a.graph, generator=gen)
+    hs = _hs_loss(a)
+    if hs is not None:
+        common["loss"] = hs
     if a.scheduler_step is not None:
         common["scheduler_step"] = a.scheduler_step
     if a.loop == "darcy":

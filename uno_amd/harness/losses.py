@@ -104,6 +104,201 @@ class LpLoss(object):
         return self.rel(x, y)
 
 
+SOBOLEV_LAYOUTS = ("bhw", "bhwt", "bthw")
+_HALF_WEIGHTS = {}
+
+
+def _sobolev_views(x, y, layout, who):
+    """-> the (B, T, H, W) views of x and y"""
+    if layout not in SOBOLEV_LAYOUTS:
+        raise ValueError(f"layout {layout!r}: one of {', '.join(SOBOLEV_LAYOUTS)}")
+    for name, t in (("x", x), ("y", y)):
+        if t.dim() != len(layout):
+            raise ValueError(f"{who}: {name} {tuple(t.shape)} is not a {layout!r} tensor of {len(layout)} axes")
+        if not t.is_floating_point():
+            raise ValueError(f"{who}: {name} must be a real floating-point tensor (got {t.dtype})")
+    if x.shape != y.shape:
+        raise ValueError(f"{who}: prediction {tuple(x.shape)} and target {tuple(y.shape)} differ")
+    if layout == "bhwt":
+        return x.permute(0, 3, 1, 2), y.permute(0, 3, 1, 2)
+    return (x, y) if layout == "bthw" else (x.unsqueeze(1), y.unsqueeze(1))
+
+
+def _sobolev_refusal(x, y):
+    """None where K25 takes these (B, T, H, W) views, or why it does not"""
+    from .. import _native
+    lo, hi = _native.SOBOLEV_MIN, _native.SOBOLEV_MAX
+    for name, t in (("the input", x), ("the target", y)):
+        if not t.is_cuda:
+            return f"{name} is on {t.device}, the kernel runs on the GPU"
+        if t.dtype != torch.float32:
+            return f"{name} is {t.dtype}, the kernel takes float32"
+        if min(t.stride()) < 0:
+            return f"{name} has a negative stride {t.stride()}"
+    if y.device != x.device:
+        return f"input on {x.device}, target on {y.device}"
+    if y.requires_grad and torch.is_grad_enabled():
+        return "the target requires grad, the kernel has no gradient for it"
+    H, W = x.shape[2:]
+    if not (lo <= H <= hi and lo <= W <= hi):
+        return f"frames of {H} x {W}: the kernel takes {lo} ... {hi} points per axis"
+    if x.shape[1] < 1:
+        return "no frame per sample"
+    return None
+
+
+def _half_weights(H, W, k, a, device, dtype):
+    """(H, W // 2 + 1) on `device`: the weight of every mode of the half spectrum rfft2 returns - the table's row |ky| in fftfreq order,
+    times the Hermitian weight, over (H W)^2; built in float64, cached per (H, W, k, a, device, dtype)"""
+    from .spectra import _sobolev_a, sobolev_weights
+    key = (H, W, int(k), _sobolev_a(k, a), str(device), dtype)
+    if key not in _HALF_WEIGHTS:
+        from .. import _native
+        r = torch.arange(H)
+        wt = sobolev_weights(H, W, k, a)[torch.minimum(r, H - r)] * 2.0
+        wt[:, 0] *= 0.5
+        if W % 2 == 0:
+            wt[:, W // 2] *= 0.5
+        _HALF_WEIGHTS[key] = _native.table_to_device((wt / (float(H) * W) ** 2).to(dtype), device)
+    return _HALF_WEIGHTS[key]
+
+
+def _sobolev_stock(x, y, k, a, per_frame):
+    """(B, T, H, W) views of any float dtype and device -> the ratios by the definition, on rfft2; differentiable by autograd"""
+    B, T, H, W = x.shape
+    wt = _half_weights(H, W, k, a, x.device, x.dtype)
+    D, Y = torch.fft.rfft2(x - y, dim=(-2, -1)), torch.fft.rfft2(y, dim=(-2, -1))
+    num = (wt * (D.real * D.real + D.imag * D.imag)).sum(dim=(-2, -1))
+    den = (wt * (Y.real * Y.real + Y.imag * Y.imag)).sum(dim=(-2, -1))
+    if not per_frame:
+        num, den = num.sum(dim=1), den.sum(dim=1)
+    return torch.sqrt(num) / torch.sqrt(den)
+
+
+class _SobolevFn(torch.autograd.Function):
+    """(x, y) as (B, T, H, W) views and the device weight table -> the ratios (reduce = 0), their sum (1) or their mean (2), 0-dim:
+    uno_sobolev_forward / uno_sobolev_backward (K25).  The weighted difference spectrum is stored only when x needs a gradient; the
+    upstream gradient stays on the device, and a reduced result hands the kernel ONE scalar."""
+
+    @staticmethod
+    def forward(ctx, x, y, w2, per_frame, reduce, need_grad):
+        from .. import _native
+        record, z = _native.sobolev_forward(x, y, w2, per_frame, want_z=need_grad)
+        B, T = x.shape[:2]
+        if need_grad:
+            ctx.save_for_backward(record, z)
+            ctx.like = x.detach()                # its shape and strides only
+        ctx.per_frame, ctx.reduce = per_frame, reduce
+        _, ratio, total = _native.sobolev_views(record, B, T, per_frame)
+        if reduce == 0:
+            return ratio
+        return total[0] if reduce == 1 else total[0] / max(1, ratio.numel())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        from .. import _native
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None, None
+        record, z = ctx.saved_tensors
+        if g.dtype != torch.float32:
+            g = g.to(torch.float32)
+        if g.numel() > 1 and all(s == 0 for s in g.stride()):      # the gradient of `.sum()`: one value expanded over the rows
+            g = g[(0,) * g.dim()]
+        g = g.reshape(-1) if g.is_contiguous() else g.contiguous().reshape(-1)
+        rows = ctx.like.shape[0] * (ctx.like.shape[1] if ctx.per_frame else 1)
+        gx = _native.sobolev_backward(z, record, g, ctx.like, ctx.per_frame, 1.0 / max(1, rows) if ctx.reduce == 2 else 1.0)
+        return gx, None, None, None, None, None
+
+
+NATIVE_SOBOLEV_MAX_SIDE, NATIVE_SOBOLEV_MAX_WORK = 256, 1.1e9
+
+
+def sobolev_native_default(B, T, H, W) -> bool:
+    """whether `native=None` takes K25 at this shape: only where its forward + backward measured faster than the stock ops
+    (tools/sobolev_loss_time.py, profiles/sobolev_loss_time.txt).  The kernel's transforms are dense sums, B T H W (W + 2 H)
+    multiply-adds per source, against rocFFT's H W log(H W): it won 1.7 ... 3.6 times at up to 128 points a side (up to 1.01 G
+    multiply-adds) and at 256^2 with 16 frames (0.81 G), tied at 256^2 with 40 frames (2.01 G: 0.91 and 1.03 of the stock time in two
+    runs), and lost at 256^2 with 80 frames (4.03 G), at 512^2 and - but for a 2 % win at 16 frames - at 421^2, where one workgroup's
+    serial chain of row tiles sets the time.  So: at most 256 points a side and at most 1.1 G multiply-adds per call; `native=True` still takes the kernel at every shape it applies to."""
+    return max(H, W) <= NATIVE_SOBOLEV_MAX_SIDE and float(B) * T * H * W * (W + 2 * H) <= NATIVE_SOBOLEV_MAX_WORK
+
+
+def _sobolev(x, y, layout, k, a, per_frame, native, reduce, who):
+    xv, yv = _sobolev_views(x, y, layout, who)
+    B, T = xv.shape[:2]
+    per_frame = bool(per_frame)
+    if B == 0 or xv.numel() == 0:               # nothing to transform: empty ratios that still hang on x
+        if native:
+            why = _sobolev_refusal(xv, yv)
+            if why is not None:
+                raise RuntimeError(f"{who}(native=True): {why}")
+        ratio = xv.flatten(2).sum(dim=2) if per_frame else xv.flatten(1).sum(dim=1)
+        return ratio if reduce == 0 else ratio.sum()
+    why = _sobolev_refusal(xv, yv)
+    if native and why is not None:
+        raise RuntimeError(f"{who}(native=True): {why}")
+    if native is None:
+        native = why is None and sobolev_native_default(B, T, *xv.shape[2:])
+    if native:
+        from .spectra import sobolev_table
+        w2 = sobolev_table(xv.shape[2], xv.shape[3], k, a, xv.device, torch.float32)
+        need = xv.requires_grad and torch.is_grad_enabled()
+        out = _SobolevFn.apply(xv, yv.detach(), w2, per_frame, reduce, need)
+    else:
+        if yv.dtype != xv.dtype or yv.device != xv.device:
+            raise ValueError(f"{who}: prediction ({xv.dtype}, {xv.device}) and target ({yv.dtype}, {yv.device}) differ")
+        out = _sobolev_stock(xv, yv, k, a, per_frame)
+        if reduce:
+            out = out.sum() if reduce == 1 else out.mean()
+    if reduce == 0 and per_frame and layout == "bhw":
+        out = out[:, 0]
+    return out
+
+
+def sobolev_rel(x, y, layout="bhw", k=1, a=None, per_frame=False, native=None):
+    """The relative Sobolev (H^k) error of x against y, differentiable in x.  With X = fft2(x) / (H W) over integer wavenumbers and
+    w2 = spectra.sobolev_weights(H, W, k, a) read at (|ky|, |kx|):
+
+        num[b, t] = sum_k w2 |X - Y|^2,  den[b, t] = sum_k w2 |Y|^2       (both Hermitian halves)
+        (B,)   sqrt(sum_t num) / sqrt(sum_t den)        per_frame=False
+        (B, T) sqrt(num) / sqrt(den)                    per_frame=True ((B,) for layout "bhw")
+
+    k = 0 is the reference's relative L2 over the flattened sample (Parseval).  layout: "bhw" (B, H, W), "bhwt" (B, H, W, T) or "bthw"
+    (B, T, H, W); views (time slices, [::r, ::r] sub-sampling) are read where they lie.  native: None - the kernel (K25: two launches
+    forward, one backward, fixed summation order, no host synchronisation) where it applies and measured faster
+    (sobolev_native_default: up to 256 points a side and 1.1 G multiply-adds per call), else stock ops; True - the kernel, a
+    RuntimeError saying why where it does not apply; False - stock ops: the same definition on torch.fft.rfft2 in the input's dtype,
+    differentiable by autograd, which serves CPU tensors, other dtypes, grids outside 8 ... 512 points per axis and a target that
+    requires grad.  No clamping; no gradient reaches y on the native path."""
+    return _sobolev(x, y, layout, k, a, per_frame, native, 0, "sobolev_rel")
+
+
+class HsLoss(object):
+    """The relative Sobolev loss as a loss object in LpLoss's shape - `rel` and `__call__`; sum (size_average=False) and mean come from
+    the kernel's own total, so a training step's loss costs two launches forward and one backward.  k = 1 is H^1, k = 2 H^2; a: the
+    coefficients a_1 ... a_k of spectra.sobolev_weights (default 1); layout and native: as sobolev_rel's."""
+
+    def __init__(self, k=1, a=None, layout="bhw", size_average=True, reduction=True, native=None):
+        super(HsLoss, self).__init__()
+        if layout not in SOBOLEV_LAYOUTS:
+            raise ValueError(f"layout {layout!r}: one of {', '.join(SOBOLEV_LAYOUTS)}")
+        from .spectra import _sobolev_a
+        self.k = int(k)
+        self.a = None if a is None else _sobolev_a(k, a)
+        self.layout = layout
+        self.reduction = reduction
+        self.size_average = size_average
+        self.native = native
+
+    def rel(self, x, y):
+        return _sobolev(x, y, self.layout, self.k, self.a, False, self.native, 0 if not self.reduction else (2 if self.size_average else 1),
+                        "HsLoss")
+
+    def __call__(self, x, y):
+        return self.rel(x, y)
+
+
 class StepErrors(NamedTuple):
     """Relative L2 errors of a (B, ..., T) prediction per time step and for the whole trajectory (device tensors)."""
     sums: torch.Tensor          # (B, T, 2): [sum (pred - target)^2, sum target^2] of every time slice

@@ -55,6 +55,49 @@ def shell_index(H: int, W: int, device=None) -> torch.Tensor:
     return _TABLES[key]
 
 
+def _sobolev_a(k, a):
+    """the k coefficients a_1 ... a_k as a tuple of floats (a: None - all 1 -, one number for every order, or k numbers)"""
+    k = int(k)
+    if k < 0:
+        raise ValueError(f"sobolev_weights: order k = {k}")
+    if a is None:
+        return (1.0,) * k
+    a = (float(a),) * k if isinstance(a, (int, float)) else tuple(float(v) for v in a)
+    if len(a) != k:
+        raise ValueError(f"sobolev_weights: {len(a)} coefficients for order k = {k}")
+    return a
+
+
+def sobolev_weights(H: int, W: int, k: int = 1, a=None) -> torch.Tensor:
+    """(H // 2 + 1, W // 2 + 1) float64 on the CPU: w2[|ky|][|kx|] = 1 + sum_{j = 1 .. k} a_j^2 (ky^2 + kx^2)^j - the weight every mode
+    (ky, kx) of the full spectrum takes in the Sobolev loss (losses.sobolev_rel); for k <= 2 the weight of FNO's HsLoss, squared.
+    a_j defaults to 1; k = 0 gives all ones (plain relative L2, by Parseval)."""
+    H, W = int(H), int(W)
+    if H < 1 or W < 1:
+        raise ValueError(f"sobolev_weights: a {H} x {W} frame")
+    a = _sobolev_a(k, a)
+    ky = torch.arange(H // 2 + 1, dtype=torch.float64).reshape(-1, 1)
+    kx = torch.arange(W // 2 + 1, dtype=torch.float64).reshape(1, -1)
+    k2 = ky * ky + kx * kx
+    w2 = torch.ones_like(k2)
+    for j, aj in enumerate(a, start=1):
+        w2 = w2 + (aj * aj) * k2 ** j
+    return w2
+
+
+_SOBOLEV_TABLES = {}
+
+
+def sobolev_table(H: int, W: int, k: int = 1, a=None, device=None, dtype=torch.float32) -> torch.Tensor:
+    """sobolev_weights on `device` in `dtype`, cached per (H, W, k, a, device, dtype) as shell_index is"""
+    device = torch.device("cpu") if device is None else torch.device(device)
+    key = (int(H), int(W), int(k), _sobolev_a(k, a), str(device), dtype)
+    if key not in _SOBOLEV_TABLES:
+        from .. import _native
+        _SOBOLEV_TABLES[key] = _native.table_to_device(sobolev_weights(H, W, k, a).to(dtype), device)
+    return _SOBOLEV_TABLES[key]
+
+
 def _frames(u, layout, name):
     """-> the (B, T, H, W) view of u"""
     if layout not in LAYOUTS:

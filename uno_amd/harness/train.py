@@ -195,18 +195,26 @@ class FlatGradients:
             dist.all_reduce(self.flat, op=dist.ReduceOp.SUM, group=group)
 
 
-def ns2d_rollout_loss(model, xx, yy, T_f, step=1, native=False):
+def ns2d_rollout_loss(model, xx, yy, T_f, step=1, native=False, loss=None):
     """Autoregressive loss of the NS-2D training step (reference ns_train_2d.py:46-62): the model predicts
     `step` frames from the last T_in, the prediction is appended to the input window, the per-step relative
     L2 losses are summed; ONE backward runs through the whole unrolled chain.
 
     native=True (opt-in): the same loss and gradients without a window tensor - the first lift reads the frames where they lie and
     the loss comes from the roll-out's own sums (_rollout_loss_native).  It needs step == 1, a model with fc / body_cf / get_grid,
-    T_in + features <= 32, a first lift of at most 64 channels and T_f <= 256, and raises where that does not hold."""
+    T_in + features <= 32, a first lift of at most 64 channels and T_f <= 256, and raises where that does not hold.
+
+    loss: a loss object called on the (B, S, S, step) prediction and target of every step instead of the relative L2 (an HsLoss of layout
+    "bhwt", summing over the batch), through the window-by-window forms; the native roll-out's step loss is fused relative L2, so
+    loss together with native=True raises."""
+    if native and loss is not None:
+        raise ValueError("ns2d_rollout_loss: loss= and native=True conflict - the native training roll-out computes its own fused relative-L2 "
+                         "step loss; pass native=False to train on another loss")
     if native:
         return _rollout_loss_native(model, xx, yy, T_f, step)
-    loss = 0
     B = yy.shape[0]
+    step_loss = (lambda im, y: lp_loss_rel_sum(im.reshape(B, -1), y.reshape(B, -1))) if loss is None else loss
+    loss = 0
     if step == 1 and hasattr(model, "forward_cf") and hasattr(model, "get_grid"):
         # the window lives channels-first next to the model's positional features: per step ONE concatenation
         # [frames 1.., new frame, features] instead of the channels-last window, its layout change and the feature concatenation
@@ -214,13 +222,13 @@ def ns2d_rollout_loss(model, xx, yy, T_f, step=1, native=False):
         z = torch.cat((xx.permute(0, 3, 1, 2), model.get_grid(xx.shape, xx.device).permute(0, 3, 1, 2)), dim=1)
         for t in range(T_f):
             im = model.forward_cf(z)                                # (B, 1, S, S)
-            loss = loss + lp_loss_rel_sum(im.reshape(B, -1), yy[..., t:t + 1].reshape(B, -1))
+            loss = loss + step_loss(im.permute(0, 2, 3, 1), yy[..., t:t + 1])
             if t + 1 < T_f:
                 z = torch.cat((z[:, 1:T_in], im, z[:, T_in:]), dim=1)
         return loss
     for t in range(0, T_f, step):
         im = model(xx)
-        loss = loss + lp_loss_rel_sum(im.reshape(B, -1), yy[..., t:t + step].reshape(B, -1))
+        loss = loss + step_loss(im, yy[..., t:t + step])
         xx = torch.cat((xx[..., step:], im), dim=-1)
     return loss
 
