@@ -295,6 +295,31 @@ int uno_mode_backward(const float* xtrunc, const float* go, const float* const* 
 /* uno_mode_wgrad with accumulate != 0: gw[c] += (in-place accumulation into a parameter's gradient buffer). */
 int uno_mode_wgrad_acc(const float* xtrunc, const float* go, float* const* gw, int B, int Ci, int Co, int ncorner,
                        int modes_per_corner, int accumulate, void* stream);
+/* Launch-plan queries (additive: added WITHOUT an ABI bump, UNO_SPECTRAL_ABI_VERSION stays 14).  Host only: no device call, no
+ * buffers.  They run the size checks and the launch decision of the calls above - the library has ONE decision function, which the
+ * launchers use too - and write it to `plan`; a call with these sizes launches exactly that.  Errors: the real call's codes and
+ * uno_last_error text (bad sizes: -1; an operand spanning 2 GiB or more per corner: -2, "... spans ..."), and -1 for a null `plan`
+ * or an op outside 0 ... 2.
+ *   uno_mode_gemm_plan: the GEMM of uno_mode_mix (op 0 / 1; w_half != 0: uno_mode_mix_f16w) or of uno_mode_wgrad(_acc) (op 2; `accumulate`
+ *   is ignored for op 0 / 1, `w_half` for op 2).  plan: UNO_MODE_GEMM_PLAN_INTS ints
+ *     [0]  family: 0 nothing to launch (B = 0), 1 LDS-staged uno::mode_gemm_kernel<qc, pipe, half, acc>,
+ *                  2 4x4x1 uno::mode_gemm_blocks_kernel<variant, half, acc>
+ *     [1..3]  the GEMM's M, N, K (op 0: B, Co, Ci; op 1: B, Ci, Co; op 2: Ci, Co, B)
+ *     [4]  qc: modes per workgroup, 16 or 8 (family 1, else 0)        [5]  pipe: pipelined K loop (family 1, else 0)
+ *     [6]  variant: 0 <4, 4, 2>, 1 <4, 2, 4>, 2 <2, 4, 4> (family 2, else -1)
+ *     [7]  KS: waves that share a K range, 1 / 2 / 4 (family 2, else 0)  [8]  adjacent: the kernel's adjacent_modes (family 2, else 0)
+ *     [9]  why the 4x4x1 form was not taken: bit 0 padded (more than 20 % idle mode blocks), bit 1 huge_out (K <= 32 and an output
+ *          above 200 MB); 0 in family 2
+ *     [10] half, [11] acc: the kernel's last two template flags (acc is 0 with half-precision weights)
+ *     [12..14] grid x, y, z       [15] dynamic LDS bytes
+ *   uno_mode_backward_plan: uno_mode_backward.  plan: UNO_MODE_BACKWARD_PLAN_INTS ints
+ *     [0]  paired: 1 = one launch of uno::mode_gemm_blocks_pair_kernel<variant of role a, acc of role b>, 0 = role b's launch, then role a's
+ *     [1]  Ga: workgroups [0, Ga) of the pair launch run role a        [2] the pair launch's grid      [3] its dynamic LDS bytes
+ *     [4..19]  role a, the input gradient (op 1), [20..35] role b, the weight gradient (op 2): each as uno_mode_gemm_plan reports it */
+#define UNO_MODE_GEMM_PLAN_INTS 16
+#define UNO_MODE_BACKWARD_PLAN_INTS 36
+int uno_mode_gemm_plan(int op, int B, int Ci, int Co, int ncorner, int modes_per_corner, int w_half, int accumulate, int* plan);
+int uno_mode_backward_plan(int B, int Ci, int Co, int ncorner, int modes_per_corner, int accumulate, int* plan);
 /* uno_spectral_conv2d_backward in all three storage formats (io_format 0: f32 images; 1: bf16 images; 2: bf16 images + fp16 (re, im)
  * weights) with accumulate_gw != 0: gw1 / gw2 += instead of =. */
 int uno_spectral_conv2d_backward_acc(const void* gy, const float* xtrunc, const void* w1, const void* w2, void* gx,

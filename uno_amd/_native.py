@@ -11,6 +11,7 @@ import ctypes as C
 import math
 import os
 import threading
+from typing import NamedTuple
 
 import torch
 
@@ -59,6 +60,8 @@ _SIGNATURES = {
     "uno_mode_mix": (C.c_int, [_fp, C.POINTER(_fp), _fp] + [_i] * 6 + [_fp]),
     "uno_mode_wgrad": (C.c_int, [_fp, _fp, C.POINTER(_fp)] + [_i] * 5 + [_fp]),
     "uno_mode_backward": (C.c_int, [_fp, _fp, C.POINTER(_fp), _fp, C.POINTER(_fp)] + [_i] * 6 + [_fp]),
+    "uno_mode_gemm_plan": (C.c_int, [_i] * 8 + [C.POINTER(_i)]),
+    "uno_mode_backward_plan": (C.c_int, [_i] * 6 + [C.POINTER(_i)]),
     "uno_spectral_conv3d_fwd_ws_bytes": (C.c_longlong, [_i] * 8),
     "uno_spectral_conv3d_bwd_ws_bytes": (C.c_longlong, [_i] * 8),
     "uno_spectral_conv3d_forward": (C.c_int, [_fp, C.POINTER(_fp), _fp, _fp, _fp] + [_i] * 12 + [_fp]),
@@ -637,6 +640,76 @@ def mode_backward(xt, go, weights, out=None, accumulate: bool = False):
                                      1 if accumulate else 0, _stream(xt))
     _check(rc, "uno_mode_backward")
     return gX, gws
+
+
+MODE_GEMM_PLAN_INTS, MODE_BACKWARD_PLAN_INTS = 16, 36          # UNO_MODE_GEMM_PLAN_INTS, UNO_MODE_BACKWARD_PLAN_INTS
+_MODE_GEMM_VARIANTS = ("4, 4, 2", "4, 2, 4", "2, 4, 4")
+
+
+class ModeGemmPlan(NamedTuple):
+    """What one per-mode GEMM launches (uno_mode_gemm_plan; the fields in the order of its int array, include/uno_spectral.h)."""
+    family: int         # 0: nothing to launch, 1: LDS-staged mode_gemm_kernel, 2: 4x4x1 mode_gemm_blocks_kernel
+    M: int
+    N: int
+    K: int
+    qc: int
+    pipe: int
+    variant: int
+    KS: int
+    adjacent: int
+    refused: int        # bit 0: padded, bit 1: huge_out
+    half: int
+    acc: int
+    grid_x: int
+    grid_y: int
+    grid_z: int
+    lds: int
+
+    @property
+    def kernel(self):
+        """the kernel's name as the launch records (profile_end) and rocprofv3 print it; None when nothing is launched"""
+        flags = "{}, {}".format("true" if self.half else "false", "true" if self.acc else "false")
+        if self.family == 1:
+            return "uno::mode_gemm_kernel<{}, {}, {}>".format(self.qc, "true" if self.pipe else "false", flags)
+        if self.family == 2:
+            return "uno::mode_gemm_blocks_kernel<{}, {}>".format(_MODE_GEMM_VARIANTS[self.variant], flags)
+        return None
+
+
+class ModeBackwardPlan(NamedTuple):
+    """What uno_mode_backward launches (uno_mode_backward_plan): one pair launch, or role b's kernel and then role a's."""
+    paired: int
+    Ga: int
+    grid: int
+    lds: int
+    a: ModeGemmPlan     # the input gradient (op 1)
+    b: ModeGemmPlan     # the weight gradient (op 2)
+
+    @property
+    def kernels(self):
+        """the kernel names in launch order"""
+        if self.paired:
+            return ["uno::mode_gemm_blocks_pair_kernel<{}, {}>".format(_MODE_GEMM_VARIANTS[self.a.variant], "true" if self.b.acc else "false")]
+        return [k for k in (self.b.kernel, self.a.kernel) if k is not None]
+
+
+def mode_gemm_plan(op: int, B: int, Ci: int, Co: int, ncorner: int, modes_per_corner: int, w_half: bool = False,
+                   accumulate: bool = False) -> ModeGemmPlan:
+    """The launch decision of mode_mix (op 0 / 1) / mode_wgrad (op 2) for these sizes, from the library's own plan function; no device
+    is touched.  Raises what the real call raises for bad sizes."""
+    buf = (C.c_int * MODE_GEMM_PLAN_INTS)()
+    rc = lib().uno_mode_gemm_plan(op, B, Ci, Co, ncorner, modes_per_corner, 1 if w_half else 0, 1 if accumulate else 0, buf)
+    _check(rc, "uno_mode_gemm_plan")
+    return ModeGemmPlan(*buf)
+
+
+def mode_backward_plan(B: int, Ci: int, Co: int, ncorner: int, modes_per_corner: int, accumulate: bool = False) -> ModeBackwardPlan:
+    """The launch decision of mode_backward for these sizes (uno_mode_backward_plan); no device is touched."""
+    buf = (C.c_int * MODE_BACKWARD_PLAN_INTS)()
+    rc = lib().uno_mode_backward_plan(B, Ci, Co, ncorner, modes_per_corner, 1 if accumulate else 0, buf)
+    _check(rc, "uno_mode_backward_plan")
+    v = list(buf)
+    return ModeBackwardPlan(*v[:4], ModeGemmPlan(*v[4:4 + MODE_GEMM_PLAN_INTS]), ModeGemmPlan(*v[4 + MODE_GEMM_PLAN_INTS:]))
 
 
 def spectral_conv3d_forward(x, ws_, Ho: int, Wo: int, To: int):

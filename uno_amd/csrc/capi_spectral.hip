@@ -62,7 +62,8 @@ static int dft2d(bool inverse, const float* in, float* out, int n_img, int H, in
 // op 0: forward mix, op 1: grad wrt input spectrum, op 2: weight grad
 // rc: 0 = launch p; 1 = nothing to launch (done); negative = error
 static int mode_gemm_params(ModeGemmParams& p, int op, const float2* act, const float2* const* w, const float2* go, float2* out_act,
-                            float2* const* out_w, int B, int Ci, int Co, int nc, int Mc, hipStream_t s, int w_half, int accumulate) {
+                            float2* const* out_w, int B, int Ci, int Co, int nc, int Mc, hipStream_t s, int w_half, int accumulate,
+                            bool plan_only = false) {
     if (B < 0 || Ci < 1 || Co < 1 || nc < 1 || nc > 4 || Mc < 1) {
         set_error("mode gemm: bad sizes B=%d Ci=%d Co=%d corners=%d modes=%d", B, Ci, Co, nc, Mc);
         return -1;
@@ -91,7 +92,7 @@ static int mode_gemm_params(ModeGemmParams& p, int op, const float2* act, const 
         p.o_sm = (long long)Co * Mc; p.o_sn = Mc;
         for (int c = 0; c < nc; ++c) { p.A.base[c] = act + (long long)c * Mc; p.B.base[c] = go + (long long)c * Mc; p.out[c] = out_w[c]; }
         if (B == 0) {
-            if (accumulate) return 1;
+            if (accumulate || plan_only) return 1;
             for (int c = 0; c < nc; ++c)
                 if (hipMemsetAsync(out_w[c], 0, sizeof(float2) * (size_t)Ci * Co * Mc, s) != hipSuccess) { set_error("memset failed"); return -5; }
             return 1;
@@ -377,6 +378,58 @@ int uno_mode_backward(const float* xtrunc, const float* go, const float* const* 
 int uno_mode_wgrad_acc(const float* xtrunc, const float* go, float* const* gw, int B, int Ci, int Co, int ncorner,
                        int modes_per_corner, int accumulate, void* stream) {
     return mode_wgrad_impl(xtrunc, go, gw, B, Ci, Co, ncorner, modes_per_corner, accumulate, stream);
+}
+
+// The operand descriptions of a call without its buffers: mode_gemm_params on placeholder addresses (the plan depends on sizes and strides
+// only; nothing is read through them), with the real call's size checks and error text.  rc as mode_gemm_params.
+static int mode_plan_params(ModeGemmParams& p, int op, int B, int Ci, int Co, int ncorner, int modes_per_corner, int w_half, int accumulate) {
+    static float2 placeholder[1];
+    const float2* const w[4] = {placeholder, placeholder, placeholder, placeholder};
+    float2* const ow[4] = {placeholder, placeholder, placeholder, placeholder};
+    if (ncorner < 1 || ncorner > 4) { set_error("%s: ncorner=%d out of range", op == 2 ? "uno_mode_wgrad" : "uno_mode_mix", ncorner); return -1; }
+    return mode_gemm_params(p, op, placeholder, w, placeholder, placeholder, ow, B, Ci, Co, ncorner, modes_per_corner, nullptr, w_half, accumulate, true);
+}
+
+static void mode_plan_ints(const ModeGemmParams& p, const ModeGemmPlan& pl, int* out) {
+    const bool lds = pl.family == 1, blocks = pl.family == 2;
+    const int v[UNO_MODE_GEMM_PLAN_INTS] = {pl.family, p.M, p.N, p.K, lds ? pl.qc : 0, lds ? pl.pipe : 0, blocks ? pl.variant : -1, blocks ? pl.KS : 0,
+                                            blocks ? pl.adjacent : 0, pl.refused, pl.half, pl.acc, pl.grid[0], pl.grid[1], pl.grid[2], pl.lds};
+    for (int i = 0; i < UNO_MODE_GEMM_PLAN_INTS; ++i) out[i] = v[i];
+}
+
+int uno_mode_gemm_plan(int op, int B, int Ci, int Co, int ncorner, int modes_per_corner, int w_half, int accumulate, int* plan) {
+    if (!plan) { set_error("uno_mode_gemm_plan: null pointer"); return -1; }
+    if (op < 0 || op > 2) { set_error("uno_mode_gemm_plan: op must be 0, 1 or 2"); return -1; }
+    for (int i = 0; i < UNO_MODE_GEMM_PLAN_INTS; ++i) plan[i] = 0;
+    ModeGemmParams p;
+    const int rc = mode_plan_params(p, op, B, Ci, Co, ncorner, modes_per_corner, w_half, accumulate);
+    if (rc != 0) return rc < 0 ? rc : 0;           // 1: nothing to launch (family 0)
+    ModeGemmPlan pl;
+    if (int e = mode_gemm_plan(p, pl)) return e;
+    mode_plan_ints(p, pl, plan);
+    return 0;
+}
+
+int uno_mode_backward_plan(int B, int Ci, int Co, int ncorner, int modes_per_corner, int accumulate, int* plan) {
+    if (!plan) { set_error("uno_mode_backward_plan: null pointer"); return -1; }
+    for (int i = 0; i < UNO_MODE_BACKWARD_PLAN_INTS; ++i) plan[i] = 0;
+    // the steps of mode_backward, planned instead of launched
+    ModeGemmParams pa, pb;
+    const int ra = mode_plan_params(pa, 1, B, Ci, Co, ncorner, modes_per_corner, 0, 0);
+    if (ra < 0) return ra;
+    const int rb = mode_plan_params(pb, 2, B, Ci, Co, ncorner, modes_per_corner, 0, accumulate);
+    if (rb < 0) return rb;
+    ModeGemmPairPlan pp = {};
+    if (ra == 0 && rb == 0) {
+        if (int e = mode_gemm_pair_plan(pa, pb, pp)) return e;
+    } else {
+        if (rb == 0) if (int e = mode_gemm_plan(pb, pp.b)) return e;
+        if (ra == 0) if (int e = mode_gemm_plan(pa, pp.a)) return e;
+    }
+    plan[0] = pp.paired; plan[1] = pp.Ga; plan[2] = pp.grid; plan[3] = pp.lds;
+    if (ra == 0) mode_plan_ints(pa, pp.a, plan + 4);
+    if (rb == 0) mode_plan_ints(pb, pp.b, plan + 4 + UNO_MODE_GEMM_PLAN_INTS);
+    return 0;
 }
 
 // `group` > 0: grouped placement of the corner-major side (CdftParams::sp_group); the callers have validated it

@@ -438,62 +438,23 @@ __global__ __launch_bounds__(256) void mode_gemm_blocks_pair_kernel(ModeGemmPara
 }
 
 template <int MTW, int NTW, int PF>
-static void launch_blocks_t(const ModeGemmParams& p, int KS, int adjacent_modes, hipStream_t s) {
-#ifdef UNO_K2_DEV
-    if (getenv("UNO_K2_KS") && atoi(getenv("UNO_K2_KS"))) KS = atoi(getenv("UNO_K2_KS"));
-    if (getenv("UNO_K2_REMAP")) adjacent_modes = atoi(getenv("UNO_K2_REMAP"));
-#endif
-    const int nq = (p.Mc + 15) / 16;
-    const int ngroups = (p.N + 4 * NTW - 1) / (4 * NTW), mgroups = (p.M + 4 * MTW - 1) / (4 * MTW);
-    const int per_wg = adjacent_modes ? 1 : 4 / KS;
-    const int ngw = (ngroups + per_wg - 1) / per_wg, per_group = ngw * mgroups;
-    const int sub = 4 / KS;
-    const int wg_groups = adjacent_modes ? (p.ncorner * nq + sub - 1) / sub : p.ncorner * nq;      // mode groups (sets of them) dealt to the XCDs
-    dim3 grid(((wg_groups + 7) / 8) * 8 * per_group);
-    const size_t lds = KS > 1 ? (size_t)4 * MTW * NTW * 8 * 64 * sizeof(float) : 0;
+static void launch_blocks_t(const ModeGemmParams& p, const ModeGemmPlan& pl, hipStream_t s) {
+    const dim3 grid(pl.grid[0]);
+    const size_t lds = (size_t)pl.lds;
     static int lds_slot[3][64];
-    const void* k = p.B.half ? reinterpret_cast<const void*>(mode_gemm_blocks_kernel<MTW, NTW, PF, true>)
-                  : p.accumulate ? reinterpret_cast<const void*>(mode_gemm_blocks_kernel<MTW, NTW, PF, false, true>)
-                                 : reinterpret_cast<const void*>(mode_gemm_blocks_kernel<MTW, NTW, PF, false>);
-    ensure_dynamic_lds(k, lds, lds_slot[p.B.half ? 0 : p.accumulate ? 1 : 2]);
-    if (p.B.half) hipLaunchKernelGGL((mode_gemm_blocks_kernel<MTW, NTW, PF, true>), grid, dim3(256), lds, s, p, KS, ngw, per_group, adjacent_modes);
-    else if (p.accumulate) hipLaunchKernelGGL((mode_gemm_blocks_kernel<MTW, NTW, PF, false, true>), grid, dim3(256), lds, s, p, KS, ngw, per_group, adjacent_modes);
-    else hipLaunchKernelGGL((mode_gemm_blocks_kernel<MTW, NTW, PF, false>), grid, dim3(256), lds, s, p, KS, ngw, per_group, adjacent_modes);
+    const void* k = pl.half ? reinterpret_cast<const void*>(mode_gemm_blocks_kernel<MTW, NTW, PF, true>)
+                  : pl.acc ? reinterpret_cast<const void*>(mode_gemm_blocks_kernel<MTW, NTW, PF, false, true>)
+                           : reinterpret_cast<const void*>(mode_gemm_blocks_kernel<MTW, NTW, PF, false>);
+    ensure_dynamic_lds(k, lds, lds_slot[pl.half ? 0 : pl.acc ? 1 : 2]);
+    if (pl.half) hipLaunchKernelGGL((mode_gemm_blocks_kernel<MTW, NTW, PF, true>), grid, dim3(256), lds, s, p, pl.KS, pl.ngw, pl.per_group, pl.adjacent);
+    else if (pl.acc) hipLaunchKernelGGL((mode_gemm_blocks_kernel<MTW, NTW, PF, false, true>), grid, dim3(256), lds, s, p, pl.KS, pl.ngw, pl.per_group, pl.adjacent);
+    else hipLaunchKernelGGL((mode_gemm_blocks_kernel<MTW, NTW, PF, false>), grid, dim3(256), lds, s, p, pl.KS, pl.ngw, pl.per_group, pl.adjacent);
 }
 
 // 16 modes: one staging buffer (33.8 KB, also holds the 34.8 KB output tile); 8 modes: two (34.8 KB)
 static size_t mode_gemm_lds(int qc, bool pipe) {
     const size_t sb = (size_t)2 * 2 * qc * (KC * 16 + 64 / qc), out = (size_t)16 * 16 * (qc + 1) * 2;
     return std::max((pipe ? 2 : 1) * sb, out) * sizeof(float);
-}
-
-// what launch_mode_gemm decides for the 4x4x1 form (its comments there): not used when the last mode group is mostly padding or the
-// output of a short-K call is huge; variant 0: <4,4,2> (short K: the weight gradient), 1: <4,2,4> (more than 8 rows), 2: <2,4,4>
-struct BlocksPlan { bool use; int variant, KS, adjacent; };
-static BlocksPlan blocks_plan(const ModeGemmParams& p) {
-    const int groups = (p.Mc + 15) / 16;
-    const bool padded = 16 * groups * 5 > p.Mc * 6;
-    const bool short_k = p.K <= 32 && p.M >= 16 && p.N >= 16;
-    const bool huge_out = short_k && 8.0 * p.M * p.N * p.Mc * p.ncorner > 200e6;
-    if (padded || huge_out) return BlocksPlan{false, 0, 1, 0};
-    const bool wide_m = p.M > 8;
-    const int tm = wide_m ? 16 : 8, tn = wide_m ? 8 : 16;
-    const long long tiles_per_group = (long long)((p.M + tm - 1) / tm) * ((p.N + tn - 1) / tn);
-    const long long tasks = (long long)p.ncorner * groups * tiles_per_group;
-    const bool adjacent = groups >= 48 && (long long)((p.ncorner * groups + 3) / 4) * tiles_per_group >= 200;
-    const int KS = (short_k || adjacent) ? 1 : (tasks < 1024 && p.K >= 32) ? 4 : (tasks < 2048 && p.K >= 16) ? 2 : 1;
-    return BlocksPlan{true, short_k ? 0 : wide_m ? 1 : 2, KS, adjacent ? 1 : 0};
-}
-struct BlocksGrid { BlocksCfg cfg; int grid; size_t lds; };
-static BlocksGrid blocks_grid(const ModeGemmParams& p, int MTW, int NTW, int KS, int adjacent_modes) {
-    const int nq = (p.Mc + 15) / 16;
-    const int ngroups = (p.N + 4 * NTW - 1) / (4 * NTW), mgroups = (p.M + 4 * MTW - 1) / (4 * MTW);
-    const int per_wg = adjacent_modes ? 1 : 4 / KS;
-    const int ngw = (ngroups + per_wg - 1) / per_wg, per_group = ngw * mgroups;
-    const int sub = 4 / KS;
-    const int wg_groups = adjacent_modes ? (p.ncorner * nq + sub - 1) / sub : p.ncorner * nq;
-    return BlocksGrid{BlocksCfg{KS, ngw, per_group, adjacent_modes}, ((wg_groups + 7) / 8) * 8 * per_group,
-                      KS > 1 ? (size_t)4 * MTW * NTW * 8 * 64 * sizeof(float) : 0};
 }
 
 static int mode_gemm_operands_ok(const ModeGemmParams& p) {
@@ -507,33 +468,105 @@ static int mode_gemm_operands_ok(const ModeGemmParams& p) {
     return 0;
 }
 
-int launch_mode_gemm(const ModeGemmParams& p, hipStream_t s);
+// THE launch decision of one per-mode GEMM: both launchers and the host-only queries (uno_mode_gemm_plan / uno_mode_backward_plan) take
+// it from here, and nothing else decides.  Touches no device.
+int mode_gemm_plan(const ModeGemmParams& p, ModeGemmPlan& pl) {
+    if (int rc = mode_gemm_operands_ok(p)) return rc;
+    pl = ModeGemmPlan{};
+    pl.half = p.B.half ? 1 : 0;
+    pl.acc = (p.accumulate && !p.B.half) ? 1 : 0;
+    // The 4x4x1 form works on whole groups of 16 modes: layers whose last group is mostly padding (2 x 36 modes = 3 groups per
+    // corner, a quarter of the third one used) stay on the LDS-staged form with its 8-mode variant; so do weight gradients
+    // with very large outputs (measured, tools/k2bench.py: 256 -> 512 channels x 4 x 216 modes, 906 MB: 263 against 332 us).
+    const int groups = (p.Mc + 15) / 16;
+    const bool padded = 16 * groups * 5 > p.Mc * 6;                         // > 20 % idle blocks
+    const bool short_k = p.K <= 32 && p.M >= 16 && p.N >= 16;               // the weight gradient: K = batch
+    const bool huge_out = short_k && 8.0 * p.M * p.N * p.Mc * p.ncorner > 200e6;
+    pl.refused = (padded ? 1 : 0) | (huge_out ? 2 : 0);
+    if (!pl.refused) {
+        // short K and many rows / columns: 16 x 16 outputs per wave (variant 0, <4, 4, 2>), so that each operand row is re-read by
+        // N / 16 (M / 16) waves like in the LDS-staged form; few rows (the batch, in the forward / input-gradient forms): all of
+        // them in one wave, more columns (variant 2, <2, 4, 4>; more than 8 rows: variant 1, <4, 2, 4>)
+        const bool wide_m = p.M > 8;
+        const int tm = wide_m ? 16 : 8, tn = wide_m ? 8 : 16;
+        const long long tiles_per_group = (long long)((p.M + tm - 1) / tm) * ((p.N + tn - 1) / tn);
+        const long long tasks = (long long)p.ncorner * groups * tiles_per_group;
+        // many mode groups per corner and at least one four-group workgroup per CU: adjacent mode groups, no K split (see the kernel)
+        const bool adjacent = groups >= 48 && (long long)((p.ncorner * groups + 3) / 4) * tiles_per_group >= 200;
+        pl.family = 2;
+        pl.variant = short_k ? 0 : wide_m ? 1 : 2;
+        pl.KS = (short_k || adjacent) ? 1 : (tasks < 1024 && p.K >= 32) ? 4 : (tasks < 2048 && p.K >= 16) ? 2 : 1;
+        pl.adjacent = adjacent ? 1 : 0;
+#ifdef UNO_K2_DEV
+        if (getenv("UNO_K2_KS") && atoi(getenv("UNO_K2_KS"))) pl.KS = atoi(getenv("UNO_K2_KS"));
+        if (getenv("UNO_K2_REMAP")) pl.adjacent = atoi(getenv("UNO_K2_REMAP"));
+#endif
+        const int MTW = pl.variant == 2 ? 2 : 4, NTW = pl.variant == 1 ? 2 : 4;
+        const int ngroups = (p.N + 4 * NTW - 1) / (4 * NTW), mgroups = (p.M + 4 * MTW - 1) / (4 * MTW);
+        const int per_wg = pl.adjacent ? 1 : 4 / pl.KS;
+        pl.ngw = (ngroups + per_wg - 1) / per_wg;
+        pl.per_group = pl.ngw * mgroups;
+        const int sub = 4 / pl.KS;
+        const int wg_groups = pl.adjacent ? (p.ncorner * groups + sub - 1) / sub : p.ncorner * groups;      // mode groups (sets of them) dealt to the XCDs
+        pl.grid[0] = ((wg_groups + 7) / 8) * 8 * pl.per_group;
+        pl.grid[1] = pl.grid[2] = 1;
+        pl.lds = pl.KS > 1 ? (int)((size_t)4 * MTW * NTW * 8 * 64 * sizeof(float)) : 0;
+        return 0;
+    }
+    const int tiles = ((p.N + 15) / 16) * ((p.M + 15) / 16);
+    // under two workgroups per CU and a long K loop: halve the mode chunk (measured, tools/k2bench.py: 256 -> 256 channels x 2 x 64
+    // modes 53 -> 36 us, 192 -> 192 x 2 x 36 modes 42 -> 28 us; with K <= 64 the 64-byte runs cost more than the extra workgroups give)
+    // (the 8-mode variant walks K two rows per pass: its clamped tail load is only right for even K - odd channel counts take the
+    // 16-mode variant)
+    const bool narrow = (long long)p.ncorner * groups * tiles < 512 && p.K >= 96 && (p.K & 1) == 0;
+    pl.family = 1;
+    pl.qc = narrow ? 8 : 16;
+    const int nq = (p.Mc + pl.qc - 1) / pl.qc;
+    // pipelined K loop: measured better with few mode chunks per layer (2 x 36 / 2 x 64 modes: 26 -> 22, 34 -> 29 us) and
+    // worse with many (2 x 196 / 2 x 324 modes: 41 -> 50, 58 -> 67 us)
+    pl.pipe = (narrow && p.ncorner * nq <= 32) ? 1 : 0;
+    pl.grid[0] = p.ncorner * nq; pl.grid[1] = (p.N + 15) / 16; pl.grid[2] = (p.M + 15) / 16;
+    pl.lds = (int)mode_gemm_lds(pl.qc, pl.pipe != 0);
+    return 0;
+}
 
 // pa: the input-gradient GEMM, pb: the weight-gradient GEMM of one backward pass (complex64 operands).  One launch where both take the
 // 4x4x1 form in the expected variants, else the two launches.
+int mode_gemm_pair_plan(const ModeGemmParams& pa, const ModeGemmParams& pb, ModeGemmPairPlan& pp) {
+    pp = ModeGemmPairPlan{};
+    if (int rc = mode_gemm_plan(pa, pp.a)) return rc;
+    if (int rc = mode_gemm_plan(pb, pp.b)) return rc;
+    pp.paired = (pp.a.family == 2 && pp.b.family == 2 && pp.a.variant != 0 && pp.b.variant == 0 && !pa.B.half && !pb.B.half && !pa.accumulate) ? 1 : 0;
+    if (pp.paired) {
+        pp.Ga = pp.a.grid[0];
+        pp.grid = pp.a.grid[0] + pp.b.grid[0];
+        pp.lds = std::max(pp.a.lds, pp.b.lds);
+    }
+    return 0;
+}
+
 int launch_mode_gemm_pair(const ModeGemmParams& pa, const ModeGemmParams& pb, hipStream_t s) {
-    if (int rc = mode_gemm_operands_ok(pa)) return rc;
-    if (int rc = mode_gemm_operands_ok(pb)) return rc;
-    const BlocksPlan A = blocks_plan(pa), Bp = blocks_plan(pb);
-    if (!A.use || !Bp.use || A.variant == 0 || Bp.variant != 0 || pa.B.half || pb.B.half || pa.accumulate) {
+    ModeGemmPairPlan pp;
+    if (int rc = mode_gemm_pair_plan(pa, pb, pp)) return rc;
+    if (!pp.paired) {
         if (int rc = launch_mode_gemm(pb, s)) return rc;
         return launch_mode_gemm(pa, s);
     }
-    const BlocksGrid ga = A.variant == 1 ? blocks_grid(pa, 4, 2, A.KS, A.adjacent) : blocks_grid(pa, 2, 4, A.KS, A.adjacent);
-    const BlocksGrid gb = blocks_grid(pb, 4, 4, Bp.KS, Bp.adjacent);
-    const size_t lds = std::max(ga.lds, gb.lds);
+    const ModeGemmPlan& A = pp.a;
+    const BlocksCfg ca{pp.a.KS, pp.a.ngw, pp.a.per_group, pp.a.adjacent}, cb{pp.b.KS, pp.b.ngw, pp.b.per_group, pp.b.adjacent};
+    const size_t lds = (size_t)pp.lds;
     const double bytes_a = (8.0 * ((double)pa.M * pa.K + (double)pa.M * pa.N) + 8.0 * (double)pa.K * pa.N) * pa.ncorner * pa.Mc;
     const double bytes_b = (8.0 * ((double)pb.M * pb.K + (double)pb.M * pb.N) + 8.0 * (double)pb.K * pb.N) * pb.ncorner * pb.Mc;
     char name[80];
     snprintf(name, sizeof(name), "uno::mode_gemm_blocks_pair_kernel<%s, %s>", A.variant == 1 ? "4, 2, 4" : "2, 4, 4", pb.accumulate ? "true" : "false");
     ProfScope prof(name, bytes_a + bytes_b - 8.0 * (double)pb.K * pb.N * pb.ncorner * pb.Mc, s);       // (gO counted once)
-    const dim3 grid(ga.grid + gb.grid);
+    const dim3 grid(pp.grid);
     static int lds_slot[4][64];
 #define UNO_PAIR(MA, NA, ACCB, SLOT)                                                                                              \
     do {                                                                                                                            \
         auto k = mode_gemm_blocks_pair_kernel<MA, NA, 4, ACCB>;                                                                     \
         ensure_dynamic_lds(reinterpret_cast<const void*>(k), lds, lds_slot[SLOT]);                                                  \
-        hipLaunchKernelGGL(k, grid, dim3(256), lds, s, pa, ga.cfg, ga.grid, pb, gb.cfg);                                            \
+        hipLaunchKernelGGL(k, grid, dim3(256), lds, s, pa, ca, pp.Ga, pb, cb);                                                      \
     } while (0)
     if (A.variant == 1) { if (pb.accumulate) UNO_PAIR(4, 2, true, 0); else UNO_PAIR(4, 2, false, 1); }
     else { if (pb.accumulate) UNO_PAIR(2, 4, true, 2); else UNO_PAIR(2, 4, false, 3); }
@@ -544,63 +577,28 @@ int launch_mode_gemm_pair(const ModeGemmParams& pa, const ModeGemmParams& pb, hi
 }
 
 int launch_mode_gemm(const ModeGemmParams& p, hipStream_t s) {
-    if (p.ncorner < 1 || p.ncorner > 4 || p.Mc < 1 || p.M < 1 || p.N < 1 || p.K < 1) {
-        set_error("mode_gemm: bad sizes M=%d N=%d K=%d corners=%d modes=%d", p.M, p.N, p.K, p.ncorner, p.Mc);
-        return -2;
-    }
-    // byte offsets inside an operand are 32-bit (raw buffer loads)
-    const long long spanA = ((long long)(p.M - 1) * p.A.s0 + (long long)(p.K - 1) * p.A.s1 + p.Mc) * 8;
-    const long long spanB = ((long long)(p.N - 1) * p.B.s1 + (long long)(p.K - 1) * p.B.s0 + p.Mc) * 8;
-    if (spanA >= (1LL << 31) || spanB >= (1LL << 31)) { set_error("mode_gemm: an operand spans %lld bytes per corner (limit 2 GiB)", spanA > spanB ? spanA : spanB); return -2; }
-    const int tiles = ((p.N + 15) / 16) * ((p.M + 15) / 16);
-    // under two workgroups per CU and a long K loop: halve the mode chunk (measured, tools/k2bench.py: 256 -> 256 channels x 2 x 64
-    // modes 53 -> 36 us, 192 -> 192 x 2 x 36 modes 42 -> 28 us; with K <= 64 the 64-byte runs cost more than the extra workgroups give)
-    // (the 8-mode variant walks K two rows per pass: its clamped tail load is only right for even K - odd channel counts take the
-    // 16-mode variant)
-    const bool narrow = (long long)p.ncorner * ((p.Mc + 15) / 16) * tiles < 512 && p.K >= 96 && (p.K & 1) == 0;
-    const int qc = narrow ? 8 : 16;
-    const int nq = (p.Mc + qc - 1) / qc;
-    dim3 grid(p.ncorner * nq, (p.N + 15) / 16, (p.M + 15) / 16);
+    ModeGemmPlan pl;
+    if (int rc = mode_gemm_plan(p, pl)) return rc;
     {
         // each operand counted once: A (M x K), B (K x N), out (M x N) complex64 per mode
         const double per_mode = 8.0 * ((double)p.M * p.K + (double)p.M * p.N) + (p.B.half ? 4.0 : 8.0) * (double)p.K * p.N;
         const double k2_bytes = per_mode * p.ncorner * p.Mc;
-        // The 4x4x1 form works on whole groups of 16 modes: layers whose last group is mostly padding (2 x 36 modes = 3 groups per
-        // corner, a quarter of the third one used) stay on the LDS-staged form with its 8-mode variant; so do weight gradients
-        // with very large outputs (measured, tools/k2bench.py: 256 -> 512 channels x 4 x 216 modes, 906 MB: 263 against 332 us).
-        const int groups = (p.Mc + 15) / 16;
-        const bool padded = 16 * groups * 5 > p.Mc * 6;                         // > 20 % idle blocks
-        const bool short_k = p.K <= 32 && p.M >= 16 && p.N >= 16;               // the weight gradient: K = batch
-        const bool huge_out = short_k && 8.0 * p.M * p.N * p.Mc * p.ncorner > 200e6;
-        if (!padded && !huge_out) {
-            // short K and many rows / columns: 16 x 16 outputs per wave, so that each operand row is re-read by N / 16 (M / 16)
-            // waves like in the LDS-staged form; few rows (the batch, in the forward /
-            // input-gradient forms): all of them in one wave, more columns
-            const bool square = short_k;
-            const bool wide_m = p.M > 8;
-            const int tm = wide_m ? 16 : 8, tn = wide_m ? 8 : 16;
-            const long long tiles_per_group = (long long)((p.M + tm - 1) / tm) * ((p.N + tn - 1) / tn);
-            const long long tasks = (long long)p.ncorner * groups * tiles_per_group;
-            // many mode groups per corner and at least one four-group workgroup per CU: adjacent mode groups, no K split (see the kernel)
-            const bool adjacent = groups >= 48 && (long long)((p.ncorner * groups + 3) / 4) * tiles_per_group >= 200;
-            const int KS = (square || adjacent) ? 1 : (tasks < 1024 && p.K >= 32) ? 4 : (tasks < 2048 && p.K >= 16) ? 2 : 1;
+        if (pl.family == 2) {
             char name[64];
-            snprintf(name, sizeof(name), "uno::mode_gemm_blocks_kernel<%s, %s, %s>", square ? "4, 4, 2" : wide_m ? "4, 2, 4" : "2, 4, 4", p.B.half ? "true" : "false",
-                     (p.accumulate && !p.B.half) ? "true" : "false");
+            snprintf(name, sizeof(name), "uno::mode_gemm_blocks_kernel<%s, %s, %s>", pl.variant == 0 ? "4, 4, 2" : pl.variant == 1 ? "4, 2, 4" : "2, 4, 4",
+                     pl.half ? "true" : "false", pl.acc ? "true" : "false");
             ProfScope prof(name, k2_bytes, s);
-            if (square) launch_blocks_t<4, 4, 2>(p, KS, adjacent ? 1 : 0, s);
-            else if (wide_m) launch_blocks_t<4, 2, 4>(p, KS, adjacent ? 1 : 0, s);
-            else launch_blocks_t<2, 4, 4>(p, KS, adjacent ? 1 : 0, s);
+            if (pl.variant == 0) launch_blocks_t<4, 4, 2>(p, pl, s);
+            else if (pl.variant == 1) launch_blocks_t<4, 2, 4>(p, pl, s);
+            else launch_blocks_t<2, 4, 4>(p, pl, s);
             const hipError_t e = hipGetLastError();
             if (e != hipSuccess) { set_error("mode_gemm launch: %s", hipGetErrorString(e)); return -5; }
             return 0;
         }
-        // pipelined K loop: measured better with few mode chunks per layer (2 x 36 / 2 x 64 modes: 26 -> 22, 34 -> 29 us) and
-        // worse with many (2 x 196 / 2 x 324 modes: 41 -> 50, 58 -> 67 us)
-        const bool pipe = narrow && p.ncorner * nq <= 32;
+        const bool pipe = pl.pipe != 0, narrow = pl.qc == 8;
+        const dim3 grid(pl.grid[0], pl.grid[1], pl.grid[2]);
         char name[64];
-        snprintf(name, sizeof(name), "uno::mode_gemm_kernel<%d, %s, %s, %s>", qc, pipe ? "true" : "false", p.B.half ? "true" : "false",
-                 (p.accumulate && !p.B.half) ? "true" : "false");
+        snprintf(name, sizeof(name), "uno::mode_gemm_kernel<%d, %s, %s, %s>", pl.qc, pipe ? "true" : "false", pl.half ? "true" : "false", pl.acc ? "true" : "false");
         ProfScope prof(name, k2_bytes, s);
         if (p.B.half) {
             if (pipe) hipLaunchKernelGGL((mode_gemm_kernel<8, true, true>), grid, dim3(256), mode_gemm_lds(8, true), s, p);

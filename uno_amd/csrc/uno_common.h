@@ -344,6 +344,23 @@ bool vol3d_fwd_applies(int n_vol, int D1, int D2, int D3, int m1, int m2, int m3
 bool vol3d_inv_applies(int n_vol, int D1, int D2, int D3, int m1, int m2, int m3);
 int launch_dft3d_fwd_volume(const Vol3dParams& p, hipStream_t s);
 int launch_dft3d_inv_volume(const Vol3dParams& p, hipStream_t s);
+// What mode_gemm.hip launches for one per-mode GEMM: decided by mode_gemm_plan alone (host only, no device call), used by both launchers
+// and reported by uno_mode_gemm_plan / uno_mode_backward_plan.
+struct ModeGemmPlan {
+    int family;                 // 1: LDS-staged mode_gemm_kernel<qc, pipe, half, acc>; 2: 4x4x1 mode_gemm_blocks_kernel<variant, half, acc>
+    int qc, pipe;               // family 1: modes per workgroup (16 / 8), pipelined K loop
+    int variant, KS, adjacent;  // family 2: 0 <4, 4, 2>, 1 <4, 2, 4>, 2 <2, 4, 4>; K split over 1 / 2 / 4 waves; adjacent_modes
+    int refused;                // why the 4x4x1 form was not taken: bit 0 padded (> 20 % idle mode blocks), bit 1 huge_out
+    int half, acc;              // the kernel's BH / ACC template flags
+    int ngw, per_group;         // family 2: the kernel's work-to-wave map
+    int grid[3], lds;           // launch grid and dynamic LDS bytes
+};
+struct ModeGemmPairPlan {
+    int paired, Ga, grid, lds;  // one launch of mode_gemm_blocks_pair_kernel<a.variant, b.acc>: workgroups [0, Ga) run role a; else two launches
+    ModeGemmPlan a, b;          // the input-gradient and the weight-gradient GEMM, each as launched alone
+};
+int mode_gemm_plan(const ModeGemmParams& p, ModeGemmPlan& plan);        // 0, or the launchers' error code with the error text set
+int mode_gemm_pair_plan(const ModeGemmParams& input_grad, const ModeGemmParams& weight_grad, ModeGemmPairPlan& plan);
 int launch_mode_gemm(const ModeGemmParams& p, hipStream_t s);
 int launch_mode_gemm_pair(const ModeGemmParams& input_grad, const ModeGemmParams& weight_grad, hipStream_t s);      // both GEMMs of a backward pass, one launch where possible
 int launch_cdft(const CdftParams& p, bool inverse, hipStream_t s);
