@@ -705,6 +705,42 @@ int uno_adam_step_multi_dev(int n_tensors, float* const* p, const float* const* 
                             const long long* n, const int* is_complex, double lr, double beta1, double beta2, double eps,
                             double weight_decay, int* step_counter, float* scalars, const double* hyper, void* stream);
 
+/* K26 (additive: these entry points were added WITHOUT an ABI bump, UNO_SPECTRAL_ABI_VERSION stays 14): the global L2 norm of a list of gradient tensors, the clip coefficient and the skip flag - all ON THE DEVICE, so that
+ * "clip the gradient norm, skip a non-finite step" needs no host read and can be captured with the update.  g, n, is_complex: the
+ * tables of uno_adam_step_multi (complex gradients count as their 2n floats).  Stage 1 writes one double partial sum of squares per
+ * 1024 floats of every tensor into `ws` (uno_grad_norm_ws_bytes(...) bytes, caller-owned, need not be initialised: every partial
+ * stage 2 reads was written by stage 1 of the same call); stage 2, one workgroup, adds them in a fixed order.  No atomics: the result
+ * is bit-reproducible.  `max_norm`: ONE double on the device, read at execution time (+inf: never clip).  `state`: the record of
+ * UNO_GRAD_NORM_RECORD doubles on the device, zeroed once by the caller:
+ *   [UNO_GRAD_NORM_NORM]      the norm of this call (sqrt of a double sum: finite whenever it is representable)
+ *   [UNO_GRAD_NORM_COEF]      min(1, max_norm / (norm + 1e-6)) (torch.nn.utils.clip_grad_norm_), evaluated in double, rounded to float
+ *                             once; 1 when the norm is not finite
+ *   [UNO_GRAD_NORM_FINITE]    1 / 0
+ *   [.._STEPS, .._CLIPPED, .._SKIPPED, .._NONFINITE, .._SUM, .._MAX]   running figures since the caller last zeroed them: calls, calls
+ *                             with coef < 1, calls with a non-finite norm under skip_nonfinite, calls with a non-finite norm, the sum
+ *                             and the maximum of the finite norms. */
+#define UNO_GRAD_NORM_NORM 0
+#define UNO_GRAD_NORM_COEF 1
+#define UNO_GRAD_NORM_FINITE 2
+#define UNO_GRAD_NORM_STEPS 3
+#define UNO_GRAD_NORM_CLIPPED 4
+#define UNO_GRAD_NORM_SKIPPED 5
+#define UNO_GRAD_NORM_NONFINITE 6
+#define UNO_GRAD_NORM_SUM 7
+#define UNO_GRAD_NORM_MAX 8
+#define UNO_GRAD_NORM_RECORD 9
+long long uno_grad_norm_ws_bytes(int n_tensors, const long long* n, const int* is_complex);
+int uno_grad_norm(int n_tensors, const float* const* g, const long long* n, const int* is_complex, const double* max_norm,
+                  int skip_nonfinite, double* ws, long long ws_bytes, double* state, void* stream);
+
+/* uno_adam_step_multi_dev guarded by the record uno_grad_norm wrote earlier on the same stream: every gradient value is multiplied by
+ * the clip coefficient BEFORE the coupled weight decay (g = coef g; g += wd p: "clip, then step()"), and - skip_nonfinite - a step
+ * whose norm is not finite writes nothing: parameters, both moments and the step counter stay as they are, bit for bit. */
+int uno_adam_step_multi_guarded(int n_tensors, float* const* p, const float* const* g, float* const* m, float* const* v,
+                                const long long* n, const int* is_complex, double lr, double beta1, double beta2, double eps,
+                                double weight_decay, int* step_counter, float* scalars, const double* hyper, const double* clip_state,
+                                int skip_nonfinite, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Mixed precision (BASELINE.json configs[4]: bf16 activations, half-precision weight storage, f32 accumulation).
  * The reference has no behaviour here (integral_operators.py:187 raises on bfloat16 input); the contract is "the float32

@@ -130,6 +130,10 @@ _SIGNATURES = {
                                       C.POINTER(_i)] + [C.c_double] * 5 + [_i, _fp]),
     "uno_adam_step_multi_dev": (C.c_int, [_i, C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp), C.POINTER(C.c_longlong),
                                           C.POINTER(_i)] + [C.c_double] * 5 + [_fp, _fp, _fp, _fp]),
+    "uno_grad_norm_ws_bytes": (C.c_longlong, [_i, C.POINTER(C.c_longlong), C.POINTER(_i)]),
+    "uno_grad_norm": (C.c_int, [_i, C.POINTER(_fp), C.POINTER(C.c_longlong), C.POINTER(_i), _fp, _i, _fp, C.c_longlong, _fp, _fp]),
+    "uno_adam_step_multi_guarded": (C.c_int, [_i, C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp), C.POINTER(C.c_longlong),
+                                              C.POINTER(_i)] + [C.c_double] * 5 + [_fp, _fp, _fp, _fp, _i, _fp]),
     "uno_spectral_conv2d_forward_mixed": (C.c_int, [_fp] * 6 + [_i] * 9 + [_fp]),
     "uno_spectral_conv2d_backward_mixed": (C.c_int, [_fp] * 8 + [_i] * 9 + [_fp]),
     "uno_mode_mix_f16w": (C.c_int, [_fp, C.POINTER(_fp), _fp] + [_i] * 6 + [_fp]),
@@ -2111,6 +2115,74 @@ class AdamPlan:
                                                weight_decay, _ptr(counter), _ptr(scalars), _opt(hyper),
                                                C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
         _check(rc, "uno_adam_step_multi_dev")
+
+    def step_guarded(self, counter, scalars, lr: float, beta1: float, beta2: float, eps: float, weight_decay: float, hyper, clip_state,
+                     skip_nonfinite: bool):
+        """step_dev under the record GradNormPlan.run wrote for this step (`clip_state`): gradients scaled by its clip coefficient; a
+        non-finite norm leaves parameters, moments and `counter` untouched when skip_nonfinite"""
+        if scalars.numel() < 4 or scalars.dtype != torch.float32 or counter.dtype != torch.int32:
+            raise RuntimeError("uno_amd: Adam device scratch must be an int32 counter and four float32 scalars")
+        if hyper is not None and (hyper.dtype != torch.float64 or hyper.numel() < 3 or hyper.device != self.device):
+            raise RuntimeError("uno_amd: Adam device hyper-parameters must be three float64 values on the parameters' device")
+        _clip_record_ok(clip_state, self.device)
+        with torch.cuda.device(self.device):
+            rc = lib().uno_adam_step_multi_guarded(self.n, self.p, self.g, self.m, self.v, self.sizes, self.cplx, lr, beta1, beta2, eps,
+                                                   weight_decay, _ptr(counter), _ptr(scalars), _opt(hyper), _ptr(clip_state),
+                                                   1 if skip_nonfinite else 0, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        _check(rc, "uno_adam_step_multi_guarded")
+
+
+# K26's state record (include/uno_spectral.h: UNO_GRAD_NORM_*)
+GRAD_NORM_RECORD = 9
+GRAD_NORM_FIELDS = ("norm", "coef", "finite", "steps", "clipped", "skipped", "nonfinite", "sum", "max")
+
+
+def _clip_record_ok(state, device):
+    if state.dtype != torch.float64 or state.numel() != GRAD_NORM_RECORD or state.device != device or not state.is_contiguous():
+        raise RuntimeError(f"uno_amd: the gradient-norm record must be {GRAD_NORM_RECORD} contiguous float64 values on the gradients' device")
+
+
+def grad_norm_partials(sizes, cplx) -> int:
+    """doubles of scratch K26 needs for tensors of these entry counts (one per 1024 floats of each tensor)"""
+    n = len(sizes)
+    b = lib().uno_grad_norm_ws_bytes(n, (C.c_longlong * n)(*sizes), (_i * n)(*[1 if c else 0 for c in cplx]))
+    if b < 0:
+        _check(-1, "uno_grad_norm_ws_bytes")
+    return b // 8
+
+
+class GradNormPlan:
+    """Pointer table of a fixed list of gradient tensors (float32 / complex64, contiguous, one device) for K26.  The gradients are not
+    kept alive: the caller re-validates `key` before every use, as with AdamPlan."""
+
+    def __init__(self, grads):
+        self.device = grads[0].device
+        self.n = len(grads)
+        reals = []
+        for g in grads:
+            gr = torch.view_as_real(g) if g.is_complex() else g
+            _require(gr, torch.float32, "grad")
+            if gr.device != self.device:
+                raise RuntimeError("uno_amd: the gradients of one norm must share a device")
+            reals.append((gr.data_ptr(), g.numel(), 1 if g.is_complex() else 0))
+        self.g = (_fp * self.n)(*[r[0] for r in reals])
+        self.sizes = (C.c_longlong * self.n)(*[r[1] for r in reals])
+        self.cplx = (_i * self.n)(*[r[2] for r in reals])
+        self.partials = lib().uno_grad_norm_ws_bytes(self.n, self.sizes, self.cplx) // 8
+        self.key = tuple(reals)
+
+    def run(self, max_norm, skip_nonfinite: bool, scratch, state):
+        """stage 1 + stage 2 on the current stream.  max_norm: one float64 on the device; scratch: float64, at least self.partials
+        entries (never read before it is written); state: the GRAD_NORM_RECORD float64 record"""
+        _clip_record_ok(state, self.device)
+        if max_norm.dtype != torch.float64 or max_norm.numel() != 1 or max_norm.device != self.device:
+            raise RuntimeError("uno_amd: max_norm must be one float64 value on the gradients' device")
+        if scratch.dtype != torch.float64 or scratch.device != self.device or not scratch.is_contiguous() or scratch.numel() < self.partials:
+            raise RuntimeError(f"uno_amd: the gradient-norm scratch must hold {self.partials} contiguous float64 values on the gradients' device")
+        with torch.cuda.device(self.device):
+            rc = lib().uno_grad_norm(self.n, self.g, self.sizes, self.cplx, _ptr(max_norm), 1 if skip_nonfinite else 0, _ptr(scratch),
+                                     8 * scratch.numel(), _ptr(state), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        _check(rc, "uno_grad_norm")
 
 
 NS2D_SIZES = (32, 64, 128, 256)

@@ -433,6 +433,47 @@ int uno_adam_step_multi_dev(int n_tensors, float* const* p, const float* const* 
     return launch_adam_multi(n_tensors, p, g, m, v, n, is_complex, lr, beta1, beta2, eps, weight_decay, 1, (hipStream_t)stream, scalars);
 }
 
+static int grad_norm_tables_ok(const char* who, int n_tensors, const long long* n, const int* is_complex) {
+    if (n_tensors < 0 || (n_tensors > 0 && (!n || !is_complex))) { set_error("%s: bad arguments", who); return 0; }
+    for (int t = 0; t < n_tensors; ++t)
+        if (n[t] < 0 || n[t] > (1LL << 60)) { set_error("%s: tensor %d has n=%lld", who, t, n[t]); return 0; }
+    return 1;
+}
+
+long long uno_grad_norm_ws_bytes(int n_tensors, const long long* n, const int* is_complex) {
+    if (!grad_norm_tables_ok("uno_grad_norm_ws_bytes", n_tensors, n, is_complex)) return -1;
+    return 8 * grad_norm_partials(n_tensors, n, is_complex);
+}
+
+int uno_grad_norm(int n_tensors, const float* const* g, const long long* n, const int* is_complex, const double* max_norm,
+                  int skip_nonfinite, double* ws, long long ws_bytes, double* state, void* stream) {
+    if (!grad_norm_tables_ok("uno_grad_norm", n_tensors, n, is_complex)) return -1;
+    if ((n_tensors > 0 && !g) || !max_norm || !state) { set_error("uno_grad_norm: null pointer"); return -1; }
+    for (int t = 0; t < n_tensors; ++t)
+        if (n[t] > 0 && !g[t]) { set_error("uno_grad_norm: null pointer (tensor %d)", t); return -1; }
+    const long long need = 8 * grad_norm_partials(n_tensors, n, is_complex);
+    if (ws_bytes < need || (need > 0 && !ws)) { set_error("uno_grad_norm: workspace of %lld bytes, %lld needed", ws_bytes, need); return -1; }
+    return launch_grad_norm(n_tensors, g, n, is_complex, max_norm, skip_nonfinite, ws, state, (hipStream_t)stream);
+}
+
+int uno_adam_step_multi_guarded(int n_tensors, float* const* p, const float* const* g, float* const* m, float* const* v,
+                                const long long* n, const int* is_complex, double lr, double beta1, double beta2, double eps,
+                                double weight_decay, int* step_counter, float* scalars, const double* hyper, const double* clip_state,
+                                int skip_nonfinite, void* stream) {
+    if (n_tensors < 0 || (n_tensors > 0 && (!p || !g || !m || !v || !n || !is_complex)) || !step_counter || !scalars || !clip_state) {
+        set_error("uno_adam_step_multi_guarded: bad arguments");
+        return -1;
+    }
+    if (!(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f)) { set_error("uno_adam_step_multi_guarded: bad betas (%g, %g)", beta1, beta2); return -1; }
+    for (int t = 0; t < n_tensors; ++t) {
+        if (n[t] < 0) { set_error("uno_adam_step_multi_guarded: tensor %d has n=%lld", t, n[t]); return -1; }
+        if (n[t] > 0 && (!p[t] || !g[t] || !m[t] || !v[t])) { set_error("uno_adam_step_multi_guarded: null pointer (tensor %d)", t); return -1; }
+    }
+    const int skip = skip_nonfinite ? 1 : 0;
+    if (int rc = launch_adam_advance(step_counter, scalars, hyper, lr, eps, weight_decay, beta1, beta2, (hipStream_t)stream, clip_state, skip)) return rc;
+    return launch_adam_multi(n_tensors, p, g, m, v, n, is_complex, lr, beta1, beta2, eps, weight_decay, 1, (hipStream_t)stream, scalars, clip_state, skip);
+}
+
 static int gelu_project_forward_impl(const void* pre, const float* w, const float* bias, void* out, int B, int C, long long P, int bf16, void* stream) {
     if (B < 0 || C < 1 || P < 0) { set_error("uno_gelu_project_forward: bad sizes B=%d C=%d P=%lld", B, C, P); return -1; }
     if (B == 0 || P == 0) return 0;

@@ -420,9 +420,13 @@ int launch_channel_mix(const void* x, const float* w, const float* bias, void* y
 long long channel_mix_ws_bytes(int Ci, int Co, long long P, int bf16);       // scratch that lets a call of this shape use pre-split weights (0: none)
 int launch_adam_multi(int n_tensors, float* const* p, const float* const* g, float* const* m, float* const* v, const long long* n,
                       const int* is_complex, double lr, double beta1, double beta2, double eps, double wd, int step, hipStream_t s,
-                      const float* dev_scalars = nullptr);
+                      const float* dev_scalars = nullptr, const double* guard = nullptr, int skip_nonfinite = 0);
 int launch_adam_advance(int* step, float* scalars, const double* hyper, double lr, double eps, double wd, double beta1, double beta2,
-                        hipStream_t s);
+                        hipStream_t s, const double* guard = nullptr, int skip_nonfinite = 0);
+// K26 (adam.hip): the global gradient norm and the clip / skip state record the guarded update reads
+long long grad_norm_partials(int n_tensors, const long long* n, const int* is_complex);
+int launch_grad_norm(int n_tensors, const float* const* g, const long long* n, const int* is_complex, const double* max_norm,
+                     int skip_nonfinite, double* partials, double* state, hipStream_t s);
 int launch_adam(float* p, const float* g, float* m, float* v, long long n, int is_complex, double lr, double beta1, double beta2,
                 double eps, double wd, int step, hipStream_t s);
 // K11's second source (pointwise_fused.hip): entries [C1, C) of w belong to s (B, C - C1, P), activated when act; gs (backward): may be null

@@ -22,13 +22,22 @@ loop by the relative Sobolev loss (losses.HsLoss, K25 on device tensors); valida
 L2, so records stay comparable.  graph=True replays every full-size training batch through a GraphedStep whose
 optimiser update is inside the graph (and NS-2D's evaluation roll-outs through a GraphedRollout); a short last batch runs eagerly.
 
+max_grad_norm= / skip_nonfinite= (command line: --clip-norm X, --no-skip-nonfinite) guard every update through ComplexAdam: the global
+gradient norm is clipped and a step with a non-finite norm is skipped, both on the device (K26 and the guarded K10; inside the graph
+when graph=True); an epoch's figures (mean and largest pre-clip norm, clipped and skipped steps) cost ONE more read-back per epoch.
+checkpoint=(path, every) (--save-every N: <out>.ckpt) writes, after every `every`-th epoch, all that the run needs to go on: model,
+optimiser and scheduler state, the record so far, the batch-order generator and torch's random states.  resume=path (--resume)
+continues from it and gives the weights, optimiser state and figures of the uninterrupted run (EpochRecord.seconds apart); it refuses
+a checkpoint written under other settings.
+
 The runners take any model with the reference's call convention and import nothing from the oracle."""
 from __future__ import annotations
 
 import argparse
 import json
+import os
 import time
-from dataclasses import dataclass, field
+from dataclasses import asdict, dataclass, field
 from typing import List, Optional, Tuple
 
 import torch
@@ -46,6 +55,11 @@ class EpochRecord:
     seconds: float
     train: float
     val: Optional[float]            # None: the loop does not validate in this epoch
+    # with max_grad_norm / skip_nonfinite only (ComplexAdam.clip_stats() of the epoch's updates):
+    grad_norm: Optional[float] = None       # the mean pre-clip gradient norm of the steps whose norm was finite
+    grad_norm_max: Optional[float] = None
+    clipped: int = 0                # steps whose gradient was scaled down
+    skipped: int = 0                # steps left out because their norm was not finite
 
 
 @dataclass
@@ -108,18 +122,26 @@ class _Sum:
 class _Trainer:
     """optimiser + scheduler + the training step of one runner, eager or replayed"""
 
-    def __init__(self, model, loss_fn, lr, weight_decay, scheduler_step, scheduler_gamma, graph):
+    def __init__(self, model, loss_fn, lr, weight_decay, scheduler_step, scheduler_gamma, graph, max_grad_norm=None, skip_nonfinite=None):
         self.model, self.loss_fn = model, loss_fn
         self.graph = bool(graph) and _device_of(model).type == "cuda"
         if graph and not self.graph:
             raise RuntimeError("graph=True needs the model on the GPU (HIP graph capture)")
-        self.opt = ComplexAdam(model.parameters(), lr=lr, weight_decay=weight_decay, capturable=self.graph)
+        guard = {k: v for k, v in (("max_grad_norm", max_grad_norm), ("skip_nonfinite", skip_nonfinite)) if v is not None}
+        self.opt = ComplexAdam(model.parameters(), lr=lr, weight_decay=weight_decay, capturable=self.graph, **guard)
         self.scheduler = torch.optim.lr_scheduler.StepLR(self.opt, step_size=scheduler_step, gamma=scheduler_gamma)
         self.extra = None           # a second figure of the step (NS-3D: the step error), set by loss_fn
         self._graphed, self._shapes, self._extra_static = None, None, None
 
     def lr(self):
         return float(self.opt.param_groups[0]["lr"])
+
+    def clip_fields(self):
+        """the EpochRecord fields of the guard, from the optimiser's counters since the last call (one read-back; none unguarded)"""
+        if not self.opt.guarded:
+            return {}
+        s = self.opt.clip_stats()
+        return {"grad_norm": s["grad_norm"], "grad_norm_max": s["grad_norm_max"], "clipped": s["clipped"], "skipped": s["skipped"]}
 
     def _eager(self, x, y):
         self.opt.zero_grad(set_to_none=True)
@@ -175,6 +197,70 @@ class _Best:
                                    else self.record.state_dict)
 
 
+CHECKPOINT_FORMAT = 1
+
+
+class _Checkpoint:
+    """The state of a run at an epoch boundary, written to `path` after every `every`-th epoch (a temporary file, then os.replace: a
+    process lost while writing leaves the previous checkpoint), and read back by begin() when `resume` names one."""
+
+    def __init__(self, settings, checkpoint, resume, model, trainer, record, generator):
+        self.path, self.every = (None, 0) if checkpoint is None else (str(checkpoint[0]), int(checkpoint[1]))
+        if checkpoint is not None and self.every < 1:
+            raise ValueError(f"checkpoint=(path, every): every = {checkpoint[1]}")
+        self.settings = dict(settings, skip_nonfinite=trainer.opt.skip_nonfinite, graph=trainer.graph)
+        self.resume, self.model, self.trainer, self.record, self.generator = resume, model, trainer, record, generator
+
+    def begin(self) -> int:
+        """-> the first epoch to run: 0, or the checkpoint's next epoch with everything else restored from it"""
+        if self.resume is None:
+            return 0
+        device = _device_of(self.model)
+        ck = torch.load(self.resume, map_location="cpu")
+        if ck.get("format") != CHECKPOINT_FORMAT:
+            raise ValueError(f"resume: {self.resume} is not a checkpoint of format {CHECKPOINT_FORMAT}")
+        was = ck["settings"]
+        for k in list(self.settings) + [k for k in was if k not in self.settings]:
+            if k not in was or k not in self.settings or was[k] != self.settings[k]:
+                raise ValueError(f"resume: setting {k} is {self.settings.get(k)!r} here and {was.get(k)!r} in {self.resume}")
+        if (ck["generator"] is None) != (self.generator is None):
+            raise ValueError(f"resume: setting generator is {'given' if self.generator is not None else 'None'} here, not so in {self.resume}")
+        self.model.load_state_dict(ck["model"])
+        self.trainer.opt.load_state_dict(ck["optimizer"])
+        self.trainer.scheduler.load_state_dict(ck["scheduler"])
+        if self.trainer.graph:
+            self.trainer.opt.init_state()           # moments and counters from the loaded state, before the capture
+        rec = ck["record"]
+        self.record.epochs = [EpochRecord(**e) for e in rec["epochs"]]
+        self.record.best_epoch, self.record.best_val = rec["best_epoch"], rec["best_val"]
+        self.record.state_dict = None if rec["state_dict"] is None else {k: v.to(device) for k, v in rec["state_dict"].items()}
+        if self.generator is not None:
+            self.generator.set_state(ck["generator"])
+        torch.set_rng_state(ck["rng_cpu"])
+        if device.type == "cuda":
+            torch.cuda.set_rng_state(ck["rng_device"], device)
+        return int(ck["epoch"])
+
+    def epoch_done(self, ep):
+        if self.path is None or (ep + 1) % self.every:
+            return
+        device = _device_of(self.model)
+        rec = self.record
+        ck = {"format": CHECKPOINT_FORMAT, "settings": self.settings, "epoch": ep + 1, "model": self.model.state_dict(),
+              "optimizer": self.trainer.opt.state_dict(), "scheduler": self.trainer.scheduler.state_dict(),
+              "record": {"epochs": [asdict(e) for e in rec.epochs], "best_epoch": rec.best_epoch, "best_val": rec.best_val,
+                         "state_dict": rec.state_dict},
+              "generator": None if self.generator is None else self.generator.get_state(), "rng_cpu": torch.get_rng_state(),
+              "rng_device": torch.cuda.get_rng_state(device) if device.type == "cuda" else None}
+        torch.save(ck, self.path + ".tmp")
+        os.replace(self.path + ".tmp", self.path)
+
+
+def _run_settings(loop, loss, user, **kw):
+    """what a checkpoint is checked against: the runner's own arguments, then the caller's (the command line's)"""
+    return {"loop": loop, **kw, "loss": None if loss is None else type(loss).__name__, **(user or {})}
+
+
 def _evaluate(model, batches, figures):
     """eval mode, no_grad: figures(model, x, y) -> 1-D device tensor per batch, summed -> (list of floats, sample count); one read-back"""
     was_training = model.training
@@ -190,11 +276,14 @@ def _evaluate(model, batches, figures):
 
 
 def fit_darcy(model, train, val, test, batch_size=None, epochs=150, lr=1e-4, scheduler_step=50, scheduler_gamma=0.5, weight_decay=1e-3,
-              weight_path=None, native=True, graph=False, generator=None, log=print, loss=None) -> FitRecord:
+              weight_path=None, native=True, graph=False, generator=None, log=print, loss=None, max_grad_norm=None, skip_nonfinite=None,
+              checkpoint=None, resume=None, settings=None) -> FitRecord:
     """train_darcy.py:35-100.  train / val / test: a DeviceDataset (batch_size then applies, training batches shuffled) or an iterable
     of (x (B, s, s, 1), y (B, s, s)) batches.  Figures: sums of per-sample relative L2 errors over the split's sample count.  loss: an
     HsLoss of layout "bhw" the training batches are scored with instead (called on (B, s, s) prediction and target; the training
-    figure is then its sum over the sample count); validation and test stay relative L2."""
+    figure is then its sum over the sample count); validation and test stay relative L2.  max_grad_norm, skip_nonfinite, checkpoint,
+    resume: see the module text (the same for the three runners); settings: a dict stored in the checkpoint beside the runner's own
+    arguments and compared on resume (the command line's)."""
     device = _device_of(model)
     myloss = LpLoss(size_average=False) if native else lp_loss_rel_sum
 
@@ -205,11 +294,15 @@ def fit_darcy(model, train, val, test, batch_size=None, epochs=150, lr=1e-4, sch
     def train_fn(x, y):
         return loss(model(x).reshape(y.shape), y)
 
-    trainer = _Trainer(model, loss_fn if loss is None else train_fn, lr, weight_decay, scheduler_step, scheduler_gamma, graph)
+    trainer = _Trainer(model, loss_fn if loss is None else train_fn, lr, weight_decay, scheduler_step, scheduler_gamma, graph, max_grad_norm,
+                       skip_nonfinite)
     record = FitRecord()
     best = _Best(model, weight_path, record, epochs)
+    ckpt = _Checkpoint(_run_settings("darcy", loss, settings, batch_size=batch_size, lr=lr, scheduler_step=scheduler_step,
+                                     scheduler_gamma=scheduler_gamma, weight_decay=weight_decay, native=native, max_grad_norm=max_grad_norm),
+                       checkpoint, resume, model, trainer, record, generator)
     t1 = time.perf_counter()
-    for ep in range(epochs):
+    for ep in range(ckpt.begin(), epochs):
         model.train()
         t1 = time.perf_counter()
         lr_now = trainer.lr()
@@ -223,7 +316,8 @@ def fit_darcy(model, train, val, test, batch_size=None, epochs=150, lr=1e-4, sch
         t2 = time.perf_counter()
         best.offer(val_l2, ep, log, "..Saving Model..")
         log(ep, t2 - t1, train_l2, val_l2)
-        record.epochs.append(EpochRecord(ep, lr_now, t2 - t1, train_l2, val_l2))
+        record.epochs.append(EpochRecord(ep, lr_now, t2 - t1, train_l2, val_l2, **trainer.clip_fields()))
+        ckpt.epoch_done(ep)
     best.restore()
     (t,), ntest = _evaluate(model, _batches(test, batch_size, False, None, device), lambda m, x, y: loss_fn(x, y).reshape(1))
     record.test = (t / ntest,)
@@ -232,7 +326,8 @@ def fit_darcy(model, train, val, test, batch_size=None, epochs=150, lr=1e-4, sch
 
 
 def fit_ns2d(model, train, val, test, T_f=10, step=1, batch_size=None, epochs=150, lr=1e-4, scheduler_step=100, scheduler_gamma=0.5,
-             weight_decay=1e-3, weight_path=None, native=True, graph=False, generator=None, log=print, loss=None) -> FitRecord:
+             weight_decay=1e-3, weight_path=None, native=True, graph=False, generator=None, log=print, loss=None, max_grad_norm=None,
+             skip_nonfinite=None, checkpoint=None, resume=None, settings=None) -> FitRecord:
     """ns_train_2d.py:34-168.  Batches: xx (B, S, S, T_in), yy (B, S, S, T_f).  Odd epochs train only; even epochs validate, step the
     scheduler and offer their weights.  native: the cat-free training roll-out (ns2d_rollout_loss(native=True)) and the native
     evaluation roll-out; native=False: the reference's window-by-window forms.  graph=True needs the native evaluation roll-out's
@@ -260,7 +355,7 @@ roll-outs stay as `native` says, in relative L2."""
             xx = torch.cat((xx[..., step:], im), dim=-1)
         return torch.stack((loss, lp_loss_rel_sum(pred.reshape(B, -1), yy.reshape(B, -1))))
 
-    trainer = _Trainer(model, loss_fn, lr, weight_decay, scheduler_step, scheduler_gamma, graph)
+    trainer = _Trainer(model, loss_fn, lr, weight_decay, scheduler_step, scheduler_gamma, graph, max_grad_norm, skip_nonfinite)
     rollout = {}                    # graph=True: the captured evaluation roll-out, by batch shape
 
     def errors_graphed(m, xx, yy):
@@ -275,7 +370,10 @@ roll-outs stay as `native` says, in relative L2."""
     figures = errors_graphed if trainer.graph and native and step == 1 else errors
     record = FitRecord()
     best = _Best(model, weight_path, record, epochs)
-    for ep in range(epochs):
+    ckpt = _Checkpoint(_run_settings("ns2d", loss, settings, T_f=T_f, step=step, batch_size=batch_size, lr=lr, scheduler_step=scheduler_step,
+                                     scheduler_gamma=scheduler_gamma, weight_decay=weight_decay, native=native, max_grad_norm=max_grad_norm),
+                       checkpoint, resume, model, trainer, record, generator)
+    for ep in range(ckpt.begin(), epochs):
         model.train()
         t1 = time.perf_counter()
         lr_now = trainer.lr()
@@ -286,7 +384,8 @@ roll-outs stay as `native` says, in relative L2."""
         if ep % 2 == 1:
             t2 = time.perf_counter()
             log("epochs", ep, "time", t2 - t1, "train_loss", train_loss)
-            record.epochs.append(EpochRecord(ep, lr_now, t2 - t1, train_loss, None))
+            record.epochs.append(EpochRecord(ep, lr_now, t2 - t1, train_loss, None, **trainer.clip_fields()))
+            ckpt.epoch_done(ep)
             continue
         (v, _), nval = _evaluate(model, _batches(val, batch_size, False, None, device), figures)
         val_loss = v / nval / per
@@ -294,7 +393,8 @@ roll-outs stay as `native` says, in relative L2."""
         trainer.scheduler.step()
         best.offer(val_loss, ep, log, "model saved")
         log("epochs", ep, "time", t2 - t1, "train_loss ", train_loss, "val_loss", val_loss)
-        record.epochs.append(EpochRecord(ep, lr_now, t2 - t1, train_loss, val_loss))
+        record.epochs.append(EpochRecord(ep, lr_now, t2 - t1, train_loss, val_loss, **trainer.clip_fields()))
+        ckpt.epoch_done(ep)
     log("Traning Ended")
     best.restore()
     (s, f), ntest = _evaluate(model, _batches(test, batch_size, False, None, device), figures)
@@ -304,7 +404,8 @@ roll-outs stay as `native` says, in relative L2."""
 
 
 def fit_ns3d(model, train, val, test, T_f=10, batch_size=None, epochs=150, lr=1e-4, scheduler_step=50, scheduler_gamma=0.5,
-             weight_decay=1e-3, weight_path=None, native=True, graph=False, generator=None, log=print, loss=None) -> FitRecord:
+             weight_decay=1e-3, weight_path=None, native=True, graph=False, generator=None, log=print, loss=None, max_grad_norm=None,
+             skip_nonfinite=None, checkpoint=None, resume=None, settings=None) -> FitRecord:
     """ns_train_3d.py:34-147.  Batches: x (B, S, S, T_in, 1), y (B, S, S, T_f).  The training figure is the per-step error of every
     batch's own forward pass; validation (per-step error) runs on even epochs only; the test pass reports the whole-trajectory and the
     per-step error.  native: loss and step error of a training batch from ONE step_losses call; native=False: lp_loss_rel_sum and the
@@ -327,10 +428,13 @@ prediction and target); the training figure stays the per-step relative L2 error
         e = (step_errors if native else _step_errors_stock)(m(x).view(B, S, S, T_f), y.reshape(B, S, S, T_f))
         return torch.stack((e.full_sum, e.step_sum))
 
-    trainer = _Trainer(model, loss_fn, lr, weight_decay, scheduler_step, scheduler_gamma, graph)
+    trainer = _Trainer(model, loss_fn, lr, weight_decay, scheduler_step, scheduler_gamma, graph, max_grad_norm, skip_nonfinite)
     record = FitRecord()
     best = _Best(model, weight_path, record, epochs)
-    for ep in range(epochs):
+    ckpt = _Checkpoint(_run_settings("ns3d", loss, settings, T_f=T_f, batch_size=batch_size, lr=lr, scheduler_step=scheduler_step,
+                                     scheduler_gamma=scheduler_gamma, weight_decay=weight_decay, native=native, max_grad_norm=max_grad_norm),
+                       checkpoint, resume, model, trainer, record, generator)
+    for ep in range(ckpt.begin(), epochs):
         t1 = time.perf_counter()
         lr_now = trainer.lr()
         model.train()
@@ -343,7 +447,8 @@ prediction and target); the training figure stays the per-step relative L2 error
         if ep % 2 == 1:
             t2 = time.perf_counter()
             log("epochs", ep, "time", t2 - t1, "train_loss ", train_loss)
-            record.epochs.append(EpochRecord(ep, lr_now, t2 - t1, train_loss, None))
+            record.epochs.append(EpochRecord(ep, lr_now, t2 - t1, train_loss, None, **trainer.clip_fields()))
+            ckpt.epoch_done(ep)
             continue
         if native:
             counted = _Counted(_batches(val, batch_size, False, None, device))
@@ -354,7 +459,8 @@ prediction and target); the training figure stays the per-step relative L2 error
         t2 = time.perf_counter()
         log("epochs", ep, "time", t2 - t1, "train_loss ", train_loss, "Val_loss  ", val_loss)
         best.offer(val_loss, ep, log, "model saved")
-        record.epochs.append(EpochRecord(ep, lr_now, t2 - t1, train_loss, val_loss))
+        record.epochs.append(EpochRecord(ep, lr_now, t2 - t1, train_loss, val_loss, **trainer.clip_fields()))
+        ckpt.epoch_done(ep)
     log("Traning Ended")
     best.restore()
     (f, s), ntest = _evaluate(model, _batches(test, batch_size, False, None, device), figures)
@@ -407,7 +513,7 @@ def checkpoint_record(a, model, record) -> dict:
     data = {"sub": int(a.sub)} if a.loop == "darcy" else {"size": int(a.size), "samples": a.samples, "gen_batch": int(a.gen_batch)}
     return {"format": RECORD_FORMAT, "loop": a.loop, "model": type(model).__name__, "ctor": ctor, "t_in": int(a.t_in), "t_f": int(a.t_f), **data,
             "ntrain": int(a.ntrain), "nval": int(a.nval), "ntest": int(a.ntest), "seed": int(a.seed),
-            **_loss_record(a),
+            **_loss_record(a), **_guard_record(a, record),
             "best_epoch": int(record.best_epoch), "best_val": float(record.best_val), "test": [float(v) for v in record.test]}
 
 
@@ -419,6 +525,14 @@ def _loss_record(a) -> dict:
     name = getattr(a, "loss", "l2")
     hs_a = getattr(a, "hs_a", None)
     return {"loss": name, **({"hs_a": [float(v) for v in hs_a]} if name != "l2" and hs_a else {})}
+
+
+def _guard_record(a, record) -> dict:
+    """the guard's settings and what it did (harness.predict ignores them; absent from records written before they existed)"""
+    clip = getattr(a, "clip_norm", None)
+    skip = clip is not None and not getattr(a, "no_skip_nonfinite", False)
+    return {"clip_norm": None if clip is None else float(clip), "skip_nonfinite": bool(skip),
+            "skipped_steps": int(sum(e.skipped for e in record.epochs))}
 
 
 def _hs_loss(a):
@@ -468,10 +582,25 @@ def main(argv=None) -> FitRecord:
     ap.add_argument("--loss", choices=tuple(LOSSES), default="l2", help="the training objective: relative L2 (the reference's), or the relative "
                     "Sobolev loss H^1 / H^2; validation and test figures stay relative L2")
     ap.add_argument("--hs-a", type=float, nargs="+", default=None, metavar="A", help="--loss h1 / h2: the coefficients a_1 [a_2] (default 1)")
+    ap.add_argument("--clip-norm", type=float, default=None, metavar="X", help="clip the global gradient norm to X (on the device) and skip "
+                    "the steps whose norm is not finite")
+    ap.add_argument("--no-skip-nonfinite", action="store_true", help="with --clip-norm: take a step with a non-finite gradient norm anyway")
+    ap.add_argument("--save-every", type=int, default=None, metavar="N", help="write <out>.ckpt after every N-th epoch")
+    ap.add_argument("--resume", action="store_true", help="continue from <out>.ckpt (same settings, --epochs may differ)")
     ap.add_argument("--seed", type=int, default=10001, help="of the weights, the split and the batch order")
     ap.add_argument("--device", default=None)
     ap.add_argument("--out", required=True, help="where the best state_dict goes")
     a = ap.parse_args(argv)
+    if a.clip_norm is not None and not a.clip_norm > 0:
+        ap.error(f"--clip-norm {a.clip_norm}: a positive number")
+    if a.no_skip_nonfinite and a.clip_norm is None:
+        ap.error("--no-skip-nonfinite goes with --clip-norm")
+    if a.save_every is not None and a.save_every < 1:
+        ap.error(f"--save-every {a.save_every}: a positive number of epochs")
+    if a.resume and not os.path.exists(a.out + ".ckpt"):
+        ap.error(f"--resume: there is no {a.out}.ckpt")
+    # what a checkpoint must agree with: every setting but how long to run and where to write
+    cli = {k: v for k, v in sorted(vars(a).items()) if k not in ("epochs", "resume", "save_every", "device")}
 
     device = torch.device(a.device if a.device else ("cuda" if torch.cuda.is_available() else "cpu"))
     total = a.ntrain + a.nval + a.ntest
@@ -500,14 +629,27 @@ def main(argv=None) -> FitRecord:
     hs = _hs_loss(a)
     if hs is not None:
         common["loss"] = hs
+    if a.clip_norm is not None:
+        common.update(max_grad_norm=a.clip_norm, skip_nonfinite=not a.no_skip_nonfinite)
+    if a.save_every is not None:
+        common["checkpoint"] = (a.out + ".ckpt", a.save_every)
+    if a.save_every is not None or a.resume:
+        common["settings"] = cli
+    if a.resume:
+        common["resume"] = a.out + ".ckpt"
     if a.scheduler_step is not None:
         common["scheduler_step"] = a.scheduler_step
-    if a.loop == "darcy":
-        record = fit_darcy(model, *parts, **common)
-    elif a.loop == "ns2d":
-        record = fit_ns2d(model, *parts, T_f=a.t_f, **common)
-    else:
-        record = fit_ns3d(model, *parts, T_f=a.t_f, **common)
+    try:
+        if a.loop == "darcy":
+            record = fit_darcy(model, *parts, **common)
+        elif a.loop == "ns2d":
+            record = fit_ns2d(model, *parts, T_f=a.t_f, **common)
+        else:
+            record = fit_ns3d(model, *parts, T_f=a.t_f, **common)
+    except ValueError as e:
+        if a.resume and str(e).startswith("resume:"):
+            raise SystemExit(f"--{e}") from None
+        raise
     write_record(a.out + ".json", checkpoint_record(a, model, record))
     return record
 
